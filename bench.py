@@ -19,15 +19,22 @@ dictionary is sharded by flow hash: LAN packets whose key another GPU owns
 are looked up there through an RCCL all-to-all of 16-byte keys and 4-byte
 answers over xGMI. --shard-mode replicated keeps the whole dictionary on
 every GPU: steady-state packets need no data-path collective, only small
-all-gathers per batch. The other placement is measured in the same run
-(extra key other_shard_mode). In both, new flows are
+all-gathers per batch. With --full the other placement is measured in the
+same run (extra key other_shard_mode). In both, new flows are
 all-gathered so every rank allocates identically. Results equal
 one nf.c over the concatenated batch in both modes (DESIGN.md §6,
 tests/test_shard_gpu.py). value = all ranks' packets / max-over-ranks time.
 `--gpus N` without a torch.distributed environment starts the N ranks
 itself.
 
-Also reported:
+A plain run sets up, warms up, times the --steps steps and prints the result
+line (metric, value, ms_per_step, configuration; roofline.frac_step from the
+step time). --dump-outputs DIR also writes what the last timed step returned
+(dump_outputs). Everything below runs only with --full, after the headline
+pass.
+
+--full also reports:
+  parity        the last timed batch against the reference's digest of it
   roofline      algorithmic HBM-read bytes per packet (92 B)
                 x packets per launch / average classify-kernel time (HIP
                 events on the context's stream, in a second timed pass over
@@ -36,6 +43,9 @@ Also reported:
                 them), vs 8 TB/s
   cpu_baseline  the oracle (clean-room C restatement of nf.c + vignat) on
                 one host core, warm 1M-flow table, bounded sample
+  and the secondary order, the end-to-end rates, the per-packet drop-in and
+  the other workloads (BASELINE configs[2], [3], random keys, churn); N > 1:
+  the chunked owner pipeline and the other placement
 """
 from __future__ import annotations
 
@@ -709,57 +719,123 @@ def cpu_model() -> str:
     return "unknown"
 
 
+STEP_BUFS = 64  # step buffers in HBM at a time (64 GiB at the default shape)
+
+
+def step_buffers(steps: int, nbytes: int, dev) -> int:
+    """How many `nbytes` step buffers timed_steps keeps at a time: one per
+    step up to STEP_BUFS, within half of the memory that is free (or held by
+    torch's allocator for reuse)."""
+    free, _ = torch.cuda.mem_get_info(dev)
+    free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+    return max(1, min(steps, STEP_BUFS, free // 2 // nbytes))
+
+
+DUMP_BYTES = 32 << 20  # of float32 frame bytes per run (all ranks together)
+DUMP_SEED = 0xD0F5
+
+
+def dump_outputs(path: str, frames: torch.Tensor, out: torch.Tensor, B: int, slot: int,
+                 world: int = 1, rank: int = 0):
+    """--dump-outputs: what the last timed vp_process_device call returned to
+    its caller, for comparing two builds output for output. A fixed sample of
+    the batch's packets (DUMP_SEED; every packet where the batch is small
+    enough), the same in every run with the same arguments:
+      packet_index.npy  float64 [K]        the sampled packets, ascending
+      frames.npy        float32 [K, slot]  their rewritten slots, byte by byte
+      out_dev.npy       float32 [K]        their out ports (0xFFFF = flood)
+      frames_colsum.npy float64 [slot]     every byte column summed over the
+                                           whole batch (exact below 2^53)
+      out_dev_sum.npy   float64 [1]        all B out ports summed
+    N > 1: rank r writes its slice's as <name>_rank<r>.npy."""
+    K = min(B, DUMP_BYTES // (4 * slot * world))
+    if K < B:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(B, K, replace=False))
+    else:
+        idx = np.arange(B, dtype=np.int64)
+    i_t = torch.from_numpy(idx).to(frames.device)
+    fv = frames.view(B, slot)
+    ports = out.to(torch.int32) & 0xFFFF
+    arrays = {
+        "packet_index": idx.astype(np.float64),
+        "frames": fv.index_select(0, i_t).cpu().numpy().astype(np.float32),
+        "out_dev": ports.index_select(0, i_t).cpu().numpy().astype(np.float32),
+        "frames_colsum": fv.sum(0, dtype=torch.int64).cpu().numpy().astype(np.float64),
+        "out_dev_sum": np.array([float(ports.sum(dtype=torch.int64).item())]),
+    }
+    os.makedirs(path, exist_ok=True)
+    sfx = "_rank%d" % rank if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + sfx + ".npy"), a)
+
+
 def timed_steps(nat, bank, dev, lens, in_dev, out, B, slot, world, rank, first, steps,
                 order="rr", host_comm=False, stages=None, wd=None, label="timed",
                 knames=None):
     """Fill one buffer per step (batches first .. first + steps - 1 of this
     rank's slices, `order`), then time exactly `steps` prepared
-    vp_process_device calls between barriers + synchronisations. Returns
-    (elapsed s, max over ranks; [(kernel ms, launches)] per step; buffers).
-    wd: the N > 1 watchdog (vigor_amd.watchdog), one marker per step.
-    knames: a dict counting the tile kernel each step launched last
+    vp_process_device calls between barriers + synchronisations. At most
+    STEP_BUFS buffers exist at a time: a longer run is timed in rounds of
+    that many steps, the buffers refilled between the rounds (untimed), and
+    its time is the sum of the rounds'. Returns (elapsed s, max over ranks;
+    [(kernel ms, launches)] per step; the last round's buffers, the last
+    step's last). wd: the N > 1 watchdog (vigor_amd.watchdog), one marker per
+    step. knames: a dict counting the tile kernel each step launched last
     (vp_last_kernel)."""
     mark = wd.stage if wd is not None else (lambda name: None)
     def gstart(k):  # global position of this rank's slice of global batch k
         return (k * world + rank) * B
-    bufs = []
-    for k in range(steps):
-        b = torch.empty(B * slot, dtype=torch.uint8, device=dev)
-        bank.fill(b, gstart(first + k), order)
-        bufs.append(b)
+    bufs = [torch.empty(B * slot, dtype=torch.uint8, device=dev)
+            for _ in range(step_buffers(steps, B * slot, dev))]
     # the headline pass: the calls in a C loop (host/steps.c), as nf.c makes
     # them; the timing pass reads per-step values back between calls (Python)
     c_loop = knames is None and stages is None and not PY_LOOP
-    if c_loop:
-        run = nat.device_steps(bufs, lens, in_dev, out, slot)
-        nows = [T.NOW0 + gstart(first + k) for k in range(steps)]
-    else:
-        calls = [nat.device_step(b, lens, in_dev, out, slot) for b in bufs]
-    torch.cuda.synchronize()
     kms = []
-    mark("%s: barrier" % label)
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    if c_loop:
-        mark("%s: %d steps (C loop)" % (label, steps))
-        run(nows, 1)
-    for k in range(0 if c_loop else steps):
-        mark("%s: step %d/%d" % (label, k + 1, steps))
-        calls[k](T.NOW0 + gstart(first + k), 1)
-        kms.append(nat.last_kernel_ms())
-        if knames is not None:
-            kn = nat.last_kernel()
-            knames[kn] = knames.get(kn, 0) + 1
-        if stages is not None:  # owner mode's phase-A stages (timing pass)
-            for name, ms in nat.last_stage_ms().items():
-                stages[name] = stages.get(name, 0.0) + ms / steps
-    mark("%s: end barrier" % label)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = 0.0
+    # round robin over flows that divide the global batch: every batch of this
+    # rank holds the same frames, so a later round's refill is a copy of one
+    same = order == "rr" and (B * world) % bank.n == 0
+    fresh = None
+    for k0 in range(0, steps, len(bufs)):
+        n = min(len(bufs), steps - k0)
+        if k0 and same and fresh is None:
+            fresh = torch.empty_like(bufs[0])
+            bank.fill(fresh, gstart(first), order)
+        for k in range(n):
+            if fresh is not None:
+                bufs[k].copy_(fresh)
+            else:
+                bank.fill(bufs[k], gstart(first + k0 + k), order)
+        if c_loop:
+            run = nat.device_steps(bufs[:n], lens, in_dev, out, slot)
+            nows = [T.NOW0 + gstart(first + k0 + k) for k in range(n)]
+        else:
+            calls = [nat.device_step(b, lens, in_dev, out, slot) for b in bufs[:n]]
+        torch.cuda.synchronize()
+        mark("%s: barrier" % label)
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if c_loop:
+            mark("%s: steps %d-%d/%d (C loop)" % (label, k0 + 1, k0 + n, steps))
+            run(nows, 1)
+        for k in range(0 if c_loop else n):
+            mark("%s: step %d/%d" % (label, k0 + k + 1, steps))
+            calls[k](T.NOW0 + gstart(first + k0 + k), 1)
+            kms.append(nat.last_kernel_ms())
+            if knames is not None:
+                kn = nat.last_kernel()
+                knames[kn] = knames.get(kn, 0) + 1
+            if stages is not None:  # owner mode's phase-A stages (timing pass)
+                for name, ms in nat.last_stage_ms().items():
+                    stages[name] = stages.get(name, 0.0) + ms / steps
+        mark("%s: end barrier" % label)
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        elapsed += time.perf_counter() - t0
+    bufs = bufs[:n]
     if world > 1:
         t = torch.tensor([elapsed], device="cpu" if host_comm else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -855,7 +931,7 @@ def main():
                     help="N > 1: flow dictionary sharded by flow hash with an "
                          "all-to-all of keys and answers (owner, north_star's "
                          "design: the headline value) or replicated on every "
-                         "GPU; the other mode is measured too (extra key "
+                         "GPU; --full measures the other mode too (extra key "
                          "other_shard_mode) unless --no-extra")
     ap.add_argument("--route-all", action="store_true",
                     help="profiling: one GPU running the owner-mode pipeline "
@@ -863,14 +939,34 @@ def main():
                          "RCCL) exchange (VIGPATH_ROUTE_ALL=1)")
     ap.add_argument("--port-array", action="store_true",
                     help="pass a per-packet port array instead of the burst's one port")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline pass, everything else this file "
+                         "measures or checks: the timed batch against the "
+                         "reference's digest, the kernel-timing pass and the "
+                         "roofline figures, the shape ceiling, the secondary "
+                         "measurements, the end-to-end rates and the CPU "
+                         "baselines (each of which --no-cpu, --no-e2e and "
+                         "--no-extra leave out again). Without it: set-up, "
+                         "warm-up, the timed steps and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step returned (rewritten frames and out ports, a "
+                         "fixed sample of its packets) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="--full without the CPU baselines")
     ap.add_argument("--no-e2e", action="store_true",
-                    help="skip the host-resident end-to-end rate")
+                    help="--full without the host-resident end-to-end rates")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the secondary measurements (uniform order; "
-                         "N > 1: the other dictionary placement)")
+                    help="--full without the secondary measurements (uniform "
+                         "order; N > 1: the other dictionary placement)")
     args = ap.parse_args()
+    full = args.full
+    cpu_on = full and not args.no_cpu
+    e2e_on = full and not args.no_e2e
+    extra_on = full and not args.no_extra
     slot = args.slot
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     if slot < 64 or slot % 16:
         raise SystemExit("bench.py: --slot must be a multiple of 16, >= 64")
     B = args.batch
@@ -984,8 +1080,11 @@ def main():
     # the last timed batch, byte for byte, against the reference's output of
     # the same batch (after timing; the golden exists for the default shape);
     # wider slots: a size-independent check of a sample (checksums verify)
+    if args.dump_outputs:
+        mark("dump outputs")
+        dump_outputs(args.dump_outputs, bufs[-1], out, B, slot, world, rank)
     want = (golden_batch_digest(args.flows, B)
-            if world == 1 and slot == SLOT and args.order == "rr" else None)
+            if full and world == 1 and slot == SLOT and args.order == "rr" else None)
     parity = None
     if want is not None:
         got = T.batch_digest(bufs[-1].cpu().numpy(), out.cpu().numpy().view(np.uint16),
@@ -994,7 +1093,7 @@ def main():
                   "match": got == want,
                   "source": "tests/golden/nat_bench_shape.npz (reference libVig)"}
         assert got == want, "timed batch differs from the reference: %s" % parity
-    elif slot != SLOT:
+    elif full and slot != SLOT:
         parity = verify_sample(bufs[-1], slot, T.ip4(192, 168, 4, 2))
         parity["source"] = "RFC 791/768 checksum verification of a sample (property)"
         assert parity["match"], parity
@@ -1002,35 +1101,37 @@ def main():
     mpps = B * args.steps * world / elapsed / 1e6
     # the kernel-timing pass: the next `steps` batches of the same workload,
     # each classify launch between HIP events on the stream it runs on
-    nat.kernel_timing(True)
     owner_run = (world > 1 and mode == "owner") or args.route_all
-    stages = {} if owner_run else None
+    stages = {} if owner_run and full else None
     knames = {}
-    el_k, kms, bufs = timed_steps(nat, bank, dev, lens, in_dev, out, B, slot, world, rank,
-                                  args.warmup + args.steps, args.steps, args.order, host_comm,
-                                  stages, wd=wd, label="kernel timing", knames=knames)
-    del bufs
     stages_max = None
-    if stages and world > 1:  # the slowest rank per stage
-        mark("stage times all-reduce")
-        names = sorted(stages)
-        t = torch.tensor([stages[k] for k in names], dtype=torch.float64,
-                         device="cpu" if host_comm else dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        stages_max = {k: float(v) for k, v in zip(names, t.tolist())}
-    per_launch_s, pkts_per_launch, achieved = kernel_rate(kms, B, args.steps, alg_bytes)
+    if full:
+        nat.kernel_timing(True)
+        el_k, kms, bufs = timed_steps(nat, bank, dev, lens, in_dev, out, B, slot, world, rank,
+                                      args.warmup + args.steps, args.steps, args.order,
+                                      host_comm, stages, wd=wd, label="kernel timing",
+                                      knames=knames)
+        del bufs
+        if stages and world > 1:  # the slowest rank per stage
+            mark("stage times all-reduce")
+            names = sorted(stages)
+            t = torch.tensor([stages[k] for k in names], dtype=torch.float64,
+                             device="cpu" if host_comm else dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            stages_max = {k: float(v) for k, v in zip(names, t.tolist())}
+        per_launch_s, pkts_per_launch, achieved = kernel_rate(kms, B, args.steps, alg_bytes)
     # the classify tile's memory-shape ceiling on this box (vp_probe_slots:
     # the same grid and 1 KiB access shape, every slot read and written back
     # whole, nothing else), beside the kernel it bounds
     kname = kernel_label(knames, NAT64 if slot == SLOT else "nat_classify_wide")
     ceiling = None
-    if world == 1 and slot in (64, 128) and not args.route_all:
+    if full and world == 1 and slot in (64, 128) and not args.route_all:
         mark("shape ceiling probe")
         ceiling = shape_ceiling(nat.L, B, slot, dev, waves=probe_waves(kname) if slot == SLOT
                                 else 4)
     traffic = None  # PMC bytes of the same kernel (profiles/, per launch)
     tpath = os.path.join(ROOT, "profiles", TRAFFIC_PROFILE)
-    if (os.path.exists(tpath) and B == 1 << 24 and args.flows == 1 << 20
+    if (full and os.path.exists(tpath) and B == 1 << 24 and args.flows == 1 << 20
             and world == 1 and slot == SLOT and args.order == "rr"):
         with open(tpath) as fh:
             tb = json.load(fh)["traffic_bytes_per_launch"]
@@ -1056,7 +1157,7 @@ def main():
     if ((world > 1 and mode == "owner") or args.route_all) and "+" not in kname:
         kname += "+nat_remote64"
     extra = {}
-    if not args.no_extra and world == 1 and args.order == "rr":
+    if extra_on and world == 1 and args.order == "rr":
         # SURVEY.md §8(d) secondary order on the same warm table
         mark("secondary order")
         kn2 = {}
@@ -1077,7 +1178,7 @@ def main():
             "frac": round(ach2 / HBM_PEAK_GBS, 4)}
     nat.kernel_timing(False)
     e2e = None
-    if world == 1 and not args.no_e2e and slot == SLOT and args.order == "rr":
+    if world == 1 and e2e_on and slot == SLOT and args.order == "rr":
         mark("end to end")
         e2e = {"value": round(end_to_end(nat, bank, dev, (args.warmup + 3 * args.steps) * B), 1),
                "unit": "Mpps",
@@ -1102,7 +1203,7 @@ def main():
                            "for comparison; frames in pageable host memory",
                    "packets": 20000, "flows": 1024})
         extra["per_packet_drop_in"] = pp
-    if (world == 1 and not args.no_extra and slot == SLOT and args.order == "rr"
+    if (world == 1 and extra_on and slot == SLOT and args.order == "rr"
             and not args.route_all and args.flows == 1 << 20):
         L0 = nat.L
         nat.close()
@@ -1137,7 +1238,7 @@ def main():
                     extra[k]["shape_ceiling_ms"] = round(rw, 4)
                     extra[k]["kernel_over_ceiling"] = round(
                         extra[k]["kernel_ms_per_step"] / rw, 4)
-    if owner_run and world > 1 and not args.no_extra:
+    if owner_run and world > 1 and extra_on:
         # the chunked owner pipeline (VIGPATH_OWN_CHUNK, read per call; the
         # same on every rank), same context and workload, the next batches:
         # one pass for the rate, one with events for its stages
@@ -1166,7 +1267,7 @@ def main():
                     "one chunk beside the next chunk's pass 1 and the last one's probe "
                     "and pass 2); the headline value stays the unchunked owner "
                     "pipeline" % OWN_CHUNK}
-    if world > 1 and not args.no_extra:
+    if world > 1 and extra_on:
         # the other dictionary placement, same workload
         other = "replicated" if mode == "owner" else "owner"
         mark("other shard mode: %s" % other)
@@ -1190,7 +1291,7 @@ def main():
     mark("report")
     if rank == 0:
         cpu = None
-        if not args.no_cpu and world == 1 and slot == SLOT:
+        if cpu_on and world == 1 and slot == SLOT:
             cmpps, rates, sample, core, warm = cpu_baseline(args.flows, args.cpu_sample)
             cpu = {"value": round(cmpps, 3), "unit": "Mpps", "cores": 1,
                    "kind": "port",
@@ -1222,32 +1323,32 @@ def main():
                                else "one per burst (vp_dev_batch.in_port)",
                        "parallelism": ("%s%d" % (mode, world))
                        if world > 1 else "single"},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4),
+            "roofline": {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac_step": round(mpps / world * 1e6 * alg_bytes / 1e9
                                             / HBM_PEAK_GBS, 4),
-                         "traffic": traffic,
-                         "traffic_source": "profiles/%s: (2 x FETCH_SIZE + "
-                                           "WRITE_SIZE) per launch / this "
-                                           "run's kernel time" % TRAFFIC_PROFILE
-                                           if traffic else None,
-                         "kernel": kname,
-                         "kernel_ms_per_launch": round(per_launch_s * 1e3, 4),
-                         "kernel_timing": "a second timed pass of %d steps (the next "
-                                          "batches), each launch between HIP events "
-                                          "on its stream; that pass: %.4f ms per step"
-                                          % (args.steps, el_k / args.steps * 1e3),
-                         "alg_bytes_per_packet": alg_bytes,
-                         **(ceiling_fields(ceiling, per_launch_s, elapsed / args.steps)
-                            if ceiling else {}),
-                         "kernel_mpps": round(pkts_per_launch / per_launch_s
-                                              / 1e6, 1)},
+                         "alg_bytes_per_packet": alg_bytes},
             "cpu_baseline": cpu,
             "parity": parity,
             "new_flow_mpps": round(new_flow_mpps, 2) if new_flow_mpps else None,
             "end_to_end": e2e,
         }
+        if full:  # the kernel-timing pass's figures
+            line["roofline"].update({
+                "achieved": round(achieved, 1),
+                "frac": round(achieved / HBM_PEAK_GBS, 4),
+                "traffic": traffic,
+                "traffic_source": "profiles/%s: (2 x FETCH_SIZE + WRITE_SIZE) per launch "
+                                  "/ this run's kernel time" % TRAFFIC_PROFILE
+                                  if traffic else None,
+                "kernel": kname,
+                "kernel_ms_per_launch": round(per_launch_s * 1e3, 4),
+                "kernel_timing": "a second timed pass of %d steps (the next batches), "
+                                 "each launch between HIP events on its stream; that "
+                                 "pass: %.4f ms per step"
+                                 % (args.steps, el_k / args.steps * 1e3),
+                **(ceiling_fields(ceiling, per_launch_s, elapsed / args.steps)
+                   if ceiling else {}),
+                "kernel_mpps": round(pkts_per_launch / per_launch_s / 1e6, 1)})
         if stages:
             line["stages_ms"] = {
                 "rank0": {k: round(v, 4) for k, v in stages.items()},

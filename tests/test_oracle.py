@@ -4,25 +4,30 @@
    FlowId_hash KAT and the vignat byte-level frames of
    Appendix A (flow 0, LAN->WAN / WAN->LAN reverse path, anti-spoof drop,
    expiry drop).
-2. The restated libVig vs the REFERENCE's own libVig sources (oracle/_ref,
-   built from /root/reference/libvig/verified/*.c) on random operation
-   streams: dchain (allocation order, LRU order, free-list LIFO, timestamps,
-   expiry), the chain-counter map (colliding hash), the CHT table + lookups.
-3. Whole-NF traces (vignat / vigbridge / viglb) with the same glue over both
-   libVig builds: identical out ports and frame bytes.
-The _ref tests skip when /root/reference is absent (e.g. on the GPU box).
+2. The restated libVig vs the REFERENCE's own libVig sources on random
+   operation streams: dchain (allocation order, LRU order, free-list LIFO,
+   timestamps, expiry), the chain-counter map (colliding hash), the CHT table
+   + lookups.
+3. Whole-NF traces (vignat / vigbridge / viglb / vigfw / vigpol) with the same
+   glue over both libVig builds: identical out ports, frame bytes and state.
+Parts 2 and 3 run the seeded cases of tests/oracle_cases.py over the
+restatement and compare with the reference libVig's answers to the same
+cases, stored in tests/golden/ref_libvig.npz (tests/golden/
+make_ref_golden.py writes them from oracle/_ref where the reference is
+present). The known-answer tests of part 1 also run over oracle/_ref itself
+where it can be built.
 """
 import os
 
 import numpy as np
 import pytest
 
+import oracle_cases as OC
 import orc
-from tracegen import mixed_fw_trace, mixed_nat_trace, mixed_pol_trace
+from oracle_cases import DEV3_MACS, END3_MACS, fw_oracle, pol_oracle
 from vigor_amd import traces as T
 
 HAVE_REF = os.path.isdir("/root/reference/libvig/verified")
-needs_ref = pytest.mark.skipif(not HAVE_REF, reason="reference not present")
 IMPLS = [False, True] if HAVE_REF else [False]
 
 DEV_MACS = [T.mac("02:03:04:05:06:07"), T.mac("12:13:14:15:16:17")]
@@ -41,16 +46,8 @@ def test_flowid_hash_kat(ref):
     assert orc.lib(ref).orc_flowid_hash(1, 2, 3, 4, 5, 6) == 0xAE93F0FF
 
 
-@needs_ref
 def test_crc_software_equals_hardware():
-    rng = np.random.default_rng(1)
-    a, b = orc.lib(False), orc.lib(True)
-    for _ in range(2000):
-        c, v = (int(x) for x in rng.integers(0, 2**32, 2, dtype=np.uint64))
-        assert a.orc_crc32c_u32(c, v) == b.orc_crc32c_u32(c, v)
-    for _ in range(200):
-        m = bytes(rng.integers(0, 256, 6, dtype=np.uint8))
-        assert a.orc_ether_hash(m) == b.orc_ether_hash(m)
+    OC.check("crc")
 
 
 @pytest.mark.parametrize("ref", IMPLS)
@@ -139,197 +136,42 @@ def test_appendix_a_expiry(ref):
 
 # --------------------------------------------------------- libVig vs ref --
 
-def _rand_dchain_ops(rng, range_, n):
-    op = rng.integers(0, 5, n).astype(np.int32)
-    arg = rng.integers(-1, range_ + 1, n).astype(np.int32)
-    arg = np.clip(arg, 0, range_ - 1).astype(np.int32)
-    t = np.cumsum(rng.integers(0, 4, n)).astype(np.int64)
-    # expiry cut-offs a little behind "now"
-    t = np.where(op == 2, t - rng.integers(0, 20, n), t).astype(np.int64)
-    return op, arg, t
-
-
-def _run_dchain(ref, range_, op, arg, t):
-    L = orc.lib(ref)
-    n = op.shape[0]
-    res = np.zeros(n, np.int32)
-    ao = np.zeros(range_, np.int32)
-    fo = np.zeros(range_, np.int32)
-    na = np.zeros(1, np.int32)
-    nf = np.zeros(1, np.int32)
-    ts = np.zeros(range_, np.int64)
-    P = orc._ptr
-    assert L.orc_test_dchain(range_, n, P(op), P(arg), P(t), P(res), P(ao),
-                             P(na), P(fo), P(nf), P(ts))
-    return res, ao[:na[0]], fo[:nf[0]], ts
-
-
-@needs_ref
 @pytest.mark.parametrize("seed", range(6))
 def test_dchain_matches_reference(seed):
-    rng = np.random.default_rng(seed)
-    range_ = int(rng.choice([1, 2, 5, 64, 300]))
-    op, arg, t = _rand_dchain_ops(rng, range_, 3000)
-    a = _run_dchain(False, range_, op, arg, t)
-    b = _run_dchain(True, range_, op, arg, t)
-    for x, y in zip(a[:3], b[:3]):
-        np.testing.assert_array_equal(x, y)
-    # the reference mallocs timestamps uninitialised (double-chain.c:113-157):
-    # only stamps of allocated indices are defined
-    np.testing.assert_array_equal(a[3][a[1]], b[3][b[1]])
+    OC.check("dchain", seed)
 
 
-@needs_ref
 @pytest.mark.parametrize("seed", range(6))
 def test_map_matches_reference(seed):
-    rng = np.random.default_rng(100 + seed)
-    cap = int(rng.choice([8, 64, 1024]))
-    hmod = int(rng.choice([1, 3, 7, 1000003]))
-    live = {}
-    free = list(range(cap))
-    ops, keys, vals = [], [], []
-    for _ in range(4000):
-        r = rng.random()
-        if r < 0.4 and free:
-            k = int(rng.integers(0, 50 * cap))
-            if k in live:
-                continue
-            s = free.pop(int(rng.integers(0, len(free))))
-            live[k] = s
-            ops.append(0), keys.append(k), vals.append(s)
-        elif r < 0.7 and live:
-            k = list(live)[int(rng.integers(0, len(live)))]
-            s = live.pop(k)
-            free.append(s)
-            ops.append(2), keys.append(k), vals.append(s)
-        else:
-            k = int(rng.integers(0, 50 * cap)) if rng.random() < .5 or not live \
-                else list(live)[int(rng.integers(0, len(live)))]
-            ops.append(1), keys.append(k), vals.append(0)
-    op = np.array(ops, np.int32)
-    key = np.array(keys, np.uint32)
-    val = np.array(vals, np.int32)
-    out = []
-    for ref in (False, True):
-        res = np.zeros(op.shape[0], np.int32)
-        P = orc._ptr
-        assert orc.lib(ref).orc_test_map(cap, hmod, op.shape[0], P(op), P(key),
-                                         P(val), P(res))
-        out.append(res)
-    np.testing.assert_array_equal(out[0], out[1])
+    OC.check("map", seed)
 
 
-@needs_ref
 @pytest.mark.parametrize("height,cap", [(97, 32), (257, 256), (7, 4), (13, 1)])
 def test_cht_matches_reference(height, cap):
-    rng = np.random.default_rng(height)
-    active = (rng.random(cap) < 0.6).astype(np.uint8)
-    hashes = rng.integers(0, 2**63, 500, dtype=np.uint64)
-    outs = []
-    for ref in (False, True):
-        tab = np.zeros(height * cap, np.uint32)
-        ch = np.zeros(500, np.int32)
-        P = orc._ptr
-        assert orc.lib(ref).orc_test_cht(height, cap, P(tab), P(active), 500,
-                                         P(hashes), P(ch))
-        outs.append((tab, ch))
-    np.testing.assert_array_equal(outs[0][0], outs[1][0])
-    np.testing.assert_array_equal(outs[0][1], outs[1][1])
+    OC.check("cht", height, cap)
 
 
 # ------------------------------------------------------ whole-NF vs ref --
+# (out ports, frame bytes, and the dumped state: allocation flags, the time
+# stamps of allocated indices, keys and values)
 
-@needs_ref
 @pytest.mark.parametrize("seed,max_flows,expire_us,n_flows",
                          [(0, 64, 60_000_000, 40), (1, 64, 1, 100),
                           (2, 16, 60_000_000, 40), (3, 256, 5, 300)])
 def test_nat_trace_matches_reference(seed, max_flows, expire_us, n_flows):
-    rng = np.random.default_rng(seed)
-    fr, ln, dv, now = mixed_nat_trace(rng, 5000, n_flows, max_idx=max_flows)
-    res = []
-    for ref in (False, True):
-        cfg = orc.nat_cfg(wan=1, ext_ip=T.ip4(192, 168, 4, 2),
-                          expire_us=expire_us, max_flows=max_flows,
-                          device_macs=DEV_MACS, endpoint_macs=END_MACS)
-        o = orc.Oracle("nat", cfg, ref=ref)
-        f = fr.copy()
-        out = o.run(f, ln, dv, now, 64)
-        res.append((out, f, o.nat_dump(max_flows)))
-    np.testing.assert_array_equal(res[0][0], res[1][0])
-    np.testing.assert_array_equal(res[0][1], res[1][1])
-    (a0, t0, k0), (a1, t1, k1) = res[0][2], res[1][2]
-    np.testing.assert_array_equal(a0, a1)
-    np.testing.assert_array_equal(t0[a0 == 1], t1[a1 == 1])
-    np.testing.assert_array_equal(k0, k1)
+    OC.check("nat", seed, max_flows, expire_us, n_flows)
 
 
-@needs_ref
 @pytest.mark.parametrize("seed,cap,expire_us", [(0, 64, 300_000_000),
                                                 (1, 16, 2), (2, 1024, 10)])
 def test_bridge_trace_matches_reference(seed, cap, expire_us):
-    rng = np.random.default_rng(seed)
-    n = 4000
-    fr, ln, dv, now = T.bridge_trace(n, 100)
-    f2 = fr.reshape(n, 64)
-    f2[:, 11] = rng.integers(0, 40, n)  # fewer stations, random mixes
-    f2[:, 5] = rng.integers(0, 40, n)
-    dv = rng.integers(0, 3, n).astype(np.uint16)
-    now = T.NOW0 + np.cumsum(rng.integers(0, 4, n)).astype(np.int64)
-    statics = [(bytes([2, 0, 0, 0, 0, 7]), 0, 2), (bytes([2, 0, 0, 0, 0, 9]),
-                                                   1, -2)]
-    res = []
-    for ref in (False, True):
-        cfg = orc.BridgeCfg(expiration_time=expire_us, dyn_capacity=cap,
-                            n_devices=3)
-        o = orc.Oracle("bridge", cfg, ref=ref, statics=statics)
-        f = fr.copy()
-        res.append((o.run(f, ln, dv, now, 64), f, o.bridge_dump(cap)))
-    np.testing.assert_array_equal(res[0][0], res[1][0])
-    np.testing.assert_array_equal(res[0][1], res[1][1])
-    (a0, t0, m0, p0), (a1, t1, m1, p1) = res[0][2], res[1][2]
-    np.testing.assert_array_equal(a0, a1)
-    np.testing.assert_array_equal(t0[a0 == 1], t1[a1 == 1])
-    np.testing.assert_array_equal(m0, m1)
-    np.testing.assert_array_equal(p0, p1)
+    OC.check("bridge", seed, cap, expire_us)
 
 
-def lb_cfg(flow_cap=1024, bcap=32, height=97, fexp=60_000_000, bexp=3_600_000):
-    c = orc.LbCfg(flow_capacity=flow_cap, flow_expiration_time=fexp,
-                  backend_capacity=bcap, cht_height=height,
-                  backend_expiration_time=bexp, wan_device=2, n_devices=3)
-    for d in range(3):
-        for i in range(6):
-            c.device_macs[d][i] = 0x10 * d + i
-    return c
-
-
-@needs_ref
 @pytest.mark.parametrize("seed,fexp,bexp", [(0, 60_000_000, 3_600_000_000),
                                             (1, 3, 50), (2, 20, 2)])
 def test_lb_trace_matches_reference(seed, fexp, bexp):
-    rng = np.random.default_rng(seed)
-    hb = T.lb_heartbeats(20)
-    tr = T.lb_traffic(3000, 500, order="uniform", seed=seed)
-    fr = np.concatenate([hb[0], tr[0]])
-    ln = np.concatenate([hb[1], tr[1]])
-    dv = np.concatenate([hb[2], tr[2]])
-    # interleave some more heartbeats inside the traffic
-    dv = dv.copy()
-    k = rng.random(dv.shape[0]) < 0.05
-    dv[k] = rng.integers(0, 2, k.sum())
-    now = T.NOW0 + np.cumsum(rng.integers(0, 3, dv.shape[0])).astype(np.int64)
-    res = []
-    for ref in (False, True):
-        o = orc.Oracle("lb", lb_cfg(fexp=fexp, bexp=bexp), ref=ref)
-        f = fr.copy()
-        res.append((o.run(f, ln, dv, now, 64), f, o.lb_dump(1024, 32)))
-    np.testing.assert_array_equal(res[0][0], res[1][0])
-    np.testing.assert_array_equal(res[0][1], res[1][1])
-    for x, y in zip(res[0][2], res[1][2]):  # flows, then backends
-        live = x[0] == 1
-        np.testing.assert_array_equal(x[0], y[0])
-        for a, b in zip(x[1:], y[1:]):
-            np.testing.assert_array_equal(a[live], b[live])
+    OC.check("lb", seed, fexp, bexp)
 
 
 # ---------------------------------------------------------------- vigfw --
@@ -345,19 +187,6 @@ def test_fw_flowid_hash_is_crc_chain(ref):
         for v in (sp, dp, sip, dip, pr):
             h = L.orc_crc32c_u32(h, v)
         assert L.orc_fw_flowid_hash(sp, dp, sip, dip, pr) == h
-
-
-def fw_oracle(ref, max_flows=64, expire_us=60_000_000, n_dev=3, wan=1):
-    cfg = orc.fw_cfg(wan=wan, expire_us=expire_us, max_flows=max_flows,
-                     device_macs=DEV3_MACS[:n_dev], endpoint_macs=END3_MACS[:n_dev],
-                     n_devices=n_dev)
-    return orc.Oracle("fw", cfg, ref=ref)
-
-
-DEV3_MACS = [T.mac("02:03:04:05:06:07"), T.mac("12:13:14:15:16:17"),
-             T.mac("22:23:24:25:26:27")]
-END3_MACS = [T.mac("01:23:45:67:89:00"), T.mac("01:23:45:67:89:01"),
-             T.mac("01:23:45:67:89:02")]
 
 
 @pytest.mark.parametrize("ref", IMPLS)
@@ -390,31 +219,11 @@ def test_fw_semantics_kat(ref):
     assert alloc.sum() == 1 and dev[0] == 2 and ts[0] == T.NOW0 + 1
 
 
-@needs_ref
 @pytest.mark.parametrize("seed,max_flows,expire_us,n_flows",
                          [(0, 64, 60_000_000, 40), (1, 64, 1, 100),
                           (2, 16, 60_000_000, 40), (3, 256, 5, 300)])
 def test_fw_trace_matches_reference(seed, max_flows, expire_us, n_flows):
-    rng = np.random.default_rng(seed)
-    fr, ln, dv, now = mixed_fw_trace(rng, 5000, n_flows)
-    res = []
-    for ref in (False, True):
-        o = fw_oracle(ref, max_flows=max_flows, expire_us=expire_us)
-        f = fr.copy()
-        out = o.run(f, ln, dv, now, 64)
-        res.append((out, f, o.fw_dump(max_flows)))
-    np.testing.assert_array_equal(res[0][0], res[1][0])
-    np.testing.assert_array_equal(res[0][1], res[1][1])
-    (a0, t0, k0, d0), (a1, t1, k1, d1) = res[0][2], res[1][2]
-    np.testing.assert_array_equal(a0, a1)
-    np.testing.assert_array_equal(t0[a0 == 1], t1[a1 == 1])
-    np.testing.assert_array_equal(k0, k1)
-    np.testing.assert_array_equal(d0, d1)
-
-
-def pol_oracle(ref, cap=64, rate=1_000_000, burst=1000, n_dev=3, lan=1, wan=0):
-    return orc.Oracle("pol", orc.pol_cfg(lan=lan, wan=wan, rate=rate, burst=burst,
-                                         capacity=cap, n_devices=n_dev), ref=ref)
+    OC.check("fw", seed, max_flows, expire_us, n_flows)
 
 
 @pytest.mark.parametrize("ref", IMPLS)
@@ -449,24 +258,10 @@ def test_pol_semantics_kat(ref):
     assert alloc.sum() == 0
 
 
-@needs_ref
 @pytest.mark.parametrize("seed,cap,n_dsts,burst,gap", [
     (0, 64, 40, 3000, 500), (1, 16, 60, 1000, 2000), (2, 256, 300, 2000, 50),
     (3, 64, 20, 1000, 10)])
 def test_pol_trace_matches_reference(seed, cap, n_dsts, burst, gap):
-    rng = np.random.default_rng(seed)
-    fr, ln, dv, now = mixed_pol_trace(rng, 6000, n_dsts, gap_ns=gap)
-    res = []
-    for ref in (False, True):
-        o = pol_oracle(ref, cap=cap, burst=burst)
-        f = fr.copy()
-        out = o.run(f, ln, dv, now, 64)
-        res.append((out, f, o.pol_dump(cap)))
-    np.testing.assert_array_equal(res[0][0], res[1][0])
-    np.testing.assert_array_equal(res[0][1], fr)
-    (a0, t0, *v0), (a1, t1, *v1) = res[0][2], res[1][2]
-    np.testing.assert_array_equal(a0, a1)
-    np.testing.assert_array_equal(t0[a0 == 1], t1[a1 == 1])
-    for x, y in zip(v0, v1):
-        np.testing.assert_array_equal(x, y)
-    assert (res[0][0] == 1).sum() > 100 and (res[0][0] == 0).sum() > 100
+    out, rewritten = OC.check("pol", seed, cap, n_dsts, burst, gap)[:2]
+    assert not rewritten.any()  # vigpol leaves the frames untouched
+    assert (out == 1).sum() > 100 and (out == 0).sum() > 100

@@ -4,7 +4,7 @@
 # Steps (each under its own time limit, chained: the first failure ends it):
 #   tests    pytest -m gpu (one process)          -> gpurun_out/TAG_pytest.log
 #   smoke    __graft_entry__.smoke()              -> gpurun_out/TAG_smoke.log
-#   bench    python3 bench.py (defaults)          -> gpurun_out/TAG_bench.log
+#   bench    python3 bench.py --full              -> TAG_bench.log in the output folder
 #   trace    rocprofv3 --kernel-trace --stats of bench.py --no-cpu
 #                                                 -> gpurun_out/TAG_kt/
 #   pmc      two --pmc passes (FETCH_SIZE, WRITE_SIZE) of bench.py --no-cpu
@@ -40,17 +40,17 @@ for step in "$@"; do
              --timeout-method thread -k "$k" > $O/${TAG}_pytest_${k//[^A-Za-z0-9]/_}.log 2>&1 || exit $? ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" \
              > $O/${TAG}_smoke.log 2>&1 || exit $? ;;
-    bench) run bench 600 python3 bench.py $BA > $O/${TAG}_bench.log 2>&1 || exit $? ;;
+    bench) run bench 600 python3 bench.py --full $BA > $O/${TAG}_bench.log 2>&1 || exit $? ;;
     trace) rm -rf $O/${TAG}_kt
            run trace 400 rocprofv3 --kernel-trace --stats --output-format csv \
-             -d $O/${TAG}_kt -- python3 bench.py --steps 10 --warmup 2 --no-cpu --no-e2e --no-extra $BA \
+             -d $O/${TAG}_kt -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu --no-e2e --no-extra $BA \
              > $O/${TAG}_kt.log 2>&1 || exit $? ;;
     pmc) rm -rf $O/${TAG}_fetch $O/${TAG}_write
          run pmc_fetch 180 rocprofv3 --pmc FETCH_SIZE --output-format csv \
-           -d $O/${TAG}_fetch -- python3 bench.py --steps 5 --warmup 2 --no-cpu --no-e2e --no-extra $BA \
+           -d $O/${TAG}_fetch -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu --no-e2e --no-extra $BA \
            > $O/${TAG}_fetch.log 2>&1 || exit $?
          run pmc_write 180 rocprofv3 --pmc WRITE_SIZE --output-format csv \
-           -d $O/${TAG}_write -- python3 bench.py --steps 5 --warmup 2 --no-cpu --no-e2e --no-extra $BA \
+           -d $O/${TAG}_write -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu --no-e2e --no-extra $BA \
            > $O/${TAG}_write.log 2>&1 || exit $? ;;
     pmcnf:*) nf=${step#pmcnf:}
          rm -rf $O/${TAG}_${nf}_fetch $O/${TAG}_${nf}_write
@@ -60,11 +60,11 @@ for step in "$@"; do
          run pmcnf_write 240 rocprofv3 --pmc WRITE_SIZE --output-format csv \
            -d $O/${TAG}_${nf}_write -- python3 tools/bench_nf.py --only $nf --no-cpu --steps 3 \
            > $O/${TAG}_${nf}_write.log 2>&1 || exit $? ;;
-    shard2) VIGPATH_COMM=host run shard2 600 python3 bench.py --gpus 2 --no-cpu --no-e2e $BA \
+    shard2) VIGPATH_COMM=host run shard2 600 python3 bench.py --full --gpus 2 --no-cpu --no-e2e $BA \
              > $O/${TAG}_shard2.log 2>&1 || exit $? ;;
     e2e) run e2e 600 python3 tools/bench_e2e.py > $O/${TAG}_e2e.log 2>&1 || exit $? ;;
     slots:*) for sl in $(echo ${step#slots:} | tr , ' '); do
-               run "slot$sl" 300 python3 bench.py --slot $sl --no-cpu --no-e2e --no-extra $BA \
+               run "slot$sl" 300 python3 bench.py --full --slot $sl --no-cpu --no-e2e --no-extra $BA \
                  >> $O/${TAG}_slots.log 2>&1 || exit $?
              done ;;
     probe|probe:*) a=${step#probe}; a=${a#:}

@@ -6,5 +6,5 @@ TAG=$1; shift
 O=gpurun_out; mkdir -p $O; export TMPDIR=/tmp
 rm -rf $O/${TAG}_tcc
 timeout -s KILL 180 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv \
-  -d $O/${TAG}_tcc -- python3 bench.py --steps 5 --warmup 2 --no-cpu --no-e2e --no-extra "$@" \
+  -d $O/${TAG}_tcc -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu --no-e2e --no-extra "$@" \
   > $O/${TAG}_tcc.log 2>&1
