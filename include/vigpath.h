@@ -193,7 +193,15 @@ int vp_unregister_host(vp_ctx *ctx, void *base);
  * scattered on the host through pinned staging. Bytes past a frame's length
  * read as 0 and are never written. Per-packet arrays in page-locked memory
  * are DMA'd in place. Frames and out_dev hold the results when the call
- * returns. */
+ * returns.
+ * vignat on one GPU serves a call of up to VIGPATH_SERVE_BURST packets
+ * (default 256; 0: none) from vp_process_one's resident kernel instead, as
+ * burst requests of up to 64 frames, one lane of a wave per packet, while no
+ * flow expiry is due anywhere in the call, every frame is at most 2048 bytes
+ * and the times do not go back: no launch, no copy call, and the kernel stays
+ * for the next call (nf.c's VIGOR_BATCH_SIZE loop, nf.c:178-215). A burst
+ * holding a frame with IPv4 options is handed back and takes the path above
+ * (vp_serve_stats_get counts both). */
 typedef struct vp_mbuf_batch {
   uint32_t n;
   uint8_t *const *frames;
@@ -207,7 +215,8 @@ typedef struct vp_mbuf_batch {
 int vp_process_mbufs(vp_ctx *ctx, const vp_mbuf_batch *batch);
 
 /* The same with a per-packet time array (the batch form of nf_process the
- * nf.h shims call). */
+ * nf.h shims call); a small vignat burst is served by the resident kernel,
+ * which it does not end, exactly as through vp_process_mbufs. */
 int vp_process_batch(vp_ctx *ctx, uint32_t n, const uint16_t *in_dev,
                      uint8_t *const *frames, const uint16_t *len,
                      const int64_t *now, uint16_t *out_dev);
@@ -219,8 +228,9 @@ int vp_process_batch(vp_ctx *ctx, uint32_t n, const uint16_t *in_dev,
  * host-coherent mailbox (no launch per packet) while no flow expiry is due at
  * `now`; otherwise, and for the other NFs, it is vp_process_batch with n = 1.
  * The kernel leaves after VIGPATH_SERVE_IDLE_MS (default 20) without a
- * packet, at any other call on the context, and at exit; VIGPATH_SERVE=0
- * turns it off. */
+ * packet, at any other call on the context -- except a vp_process_batch /
+ * vp_process_mbufs call small enough to be served by it as a burst -- and at
+ * exit; VIGPATH_SERVE=0 turns it off. */
 int vp_process_one(vp_ctx *ctx, uint16_t in_dev, uint8_t *frame, uint16_t len,
                    int64_t now, uint16_t *out_dev);
 
@@ -346,6 +356,19 @@ typedef struct vp_table_stats {
   uint32_t pad;
 } vp_table_stats;
 int vp_table_stats_get(vp_ctx *ctx, int table, vp_table_stats *out);
+
+/* vignat's resident kernel (vp_process_one, and vp_process_batch /
+ * vp_process_mbufs calls small enough to be served as burst requests) since
+ * the context was created. A read of host-side counters: the kernel stays.
+ * All zeros for the other NFs. */
+typedef struct vp_serve_stats {
+  uint64_t packets_one;   /* packets served by vp_process_one's kernel */
+  uint64_t bursts;        /* burst requests served */
+  uint64_t burst_packets; /* packets in them */
+  uint64_t declined;      /* bursts the kernel handed back (byte-path frame) */
+  uint64_t launches;      /* launches of the resident kernel */
+} vp_serve_stats;
+int vp_serve_stats_get(vp_ctx *ctx, vp_serve_stats *out);
 
 /* Why the calling thread's last failing vp_* call failed: the HIP error and
  * the call site for VP_EIO / VP_ENOMEM, the broken invariant for VP_ESTATE

@@ -39,6 +39,13 @@ class TableStatsC(C.Structure):
                 ("pad", C.c_uint32)]
 
 
+class ServeStatsC(C.Structure):
+    """vp_serve_stats (include/vigpath.h)."""
+    _fields_ = [("packets_one", C.c_uint64), ("bursts", C.c_uint64),
+                ("burst_packets", C.c_uint64), ("declined", C.c_uint64),
+                ("launches", C.c_uint64)]
+
+
 MacTable = (C.c_uint8 * 6) * MAX_DEV
 
 
@@ -127,7 +134,7 @@ EXPORTS = ["vp_nat_create", "vp_bridge_create", "vp_lb_create", "vp_fw_create",
            "vp_kernel_timing", "vp_last_kernel_ms", "vp_version", "vp_table_stats_get",
            "vp_last_error", "vp_register_host", "vp_unregister_host", "vp_process_mbufs",
            "vp_last_stage_ms", "vp_stage_ms", "vp_comm_abort", "vp_probe_slots",
-           "vp_probe_slots_w", "vp_process_one", "vp_last_kernel"]
+           "vp_probe_slots_w", "vp_process_one", "vp_last_kernel", "vp_serve_stats_get"]
 
 _libs = {}
 
@@ -224,6 +231,8 @@ def lib(path: str | None = None):
     L.vp_kernel_timing.restype = C.c_int
     L.vp_table_stats_get.argtypes = [C.c_void_p, C.c_int, C.POINTER(TableStatsC)]
     L.vp_table_stats_get.restype = C.c_int
+    L.vp_serve_stats_get.argtypes = [C.c_void_p, C.POINTER(ServeStatsC)]
+    L.vp_serve_stats_get.restype = C.c_int
     L.vp_last_error.argtypes = []
     L.vp_last_error.restype = C.c_char_p
     _libs[path] = L

@@ -372,12 +372,38 @@ struct ServeBox {
   uint64_t ans;      // device: request number | (out | fresh << 16) << 32 (relaunch state)
   uint64_t prof[10];  // device: wall-clock stamps of the last request (VIGPATH_SERVE_PROF)
   alignas(16) uint8_t frame[kServeFrame];  // longer frames in; every result out
+  // A burst request (nat_process_burst): up to kServeBurst frames, one lane
+  // of the serving wave each. The host writes the body below first, then the
+  // tagged chunk 0 alone, whose word 0 is kServeBurstOp | n << 16 (no frame is
+  // 0xFFFF bytes long, and n <= kServeBurst keeps it apart from kServeLeave)
+  // and whose words 1-2 are unused; the server reads the body only after it
+  // has seen the tag (a second PCIe round trip, once per burst). The answer
+  // comes back the same way: the first 64 bytes of every rewritten frame and
+  // bout[] (system-coherent stores, waited for), then answer chunk 0 = {status,
+  // n, 0, request number}.
+  alignas(128) uint8_t bframe[64][kServeFrame];
+  int64_t bnow[64];
+  uint32_t bmeta[64];  // len | in_dev << 16, as a one-packet request's word 0
+  // out port | fresh << 16 | rewritten << 17 (only rewritten frames are copied back)
+  alignas(16) uint32_t bout[64];
 };
+constexpr uint32_t kServeBurst = 64;       // frames per burst request
+constexpr uint32_t kServeBurstOp = 0xFFFFu;  // message word 0, low half: a burst
+constexpr uint32_t kBurstServed = 0, kBurstDeclined = 1;  // answer chunk 0, word 0
+static_assert(sizeof(((ServeBox *)nullptr)->bframe) == kServeBurst * kServeFrame, "burst slots");
 // One packet through the persistent kernel (vignat, one GPU, no expiry due):
 // 0 done; 1 not eligible (the caller takes the batch path, the server is
 // stopped); < 0 an error.
 int nat_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, int64_t now,
                     uint16_t *out);
+// Packets [first, first + count) of a host batch through the same kernel as
+// burst requests of up to kServeBurst frames (vignat, one GPU, no expiry due
+// anywhere in the range, count within the routing limit): 0 all done; 1
+// nothing of it done (not routed, or the kernel declined the first request:
+// the caller runs today's pipeline); < 0 an error. *served = the packets done
+// (a later request declined: the caller runs the rest through the pipeline).
+int nat_process_burst(vp_ctx *c, const vp_mbuf_batch *b, uint32_t first, uint32_t count,
+                      uint32_t *served);
 // Stop the context's persistent kernel, if it runs (every other entry point
 // calls this first: the kernel owns the table while it runs).
 int serve_stop(vp_ctx *c);
@@ -474,4 +500,5 @@ struct vp_ctx {
   // take it (serve_launch: resident kernels share the hardware queues)
   std::recursive_mutex srv_mu;
   double srv_prof[11] = {};  // VIGPATH_SERVE_PROF: summed stage times (us), counts
+  vp_serve_stats srv_stats{};  // vp_serve_stats_get (counted under srv_mu)
 };

@@ -2150,6 +2150,178 @@ __device__ __forceinline__ uint32_t nat_one_reg(const NatArgs &a, const uint32_t
   return dst;
 }
 
+// A burst request (ServeBox: nf.c's VIGOR_BATCH_SIZE loop, nf.c:178-215): n
+// frames as nf_process would take them one after another, lane i = packet i
+// at sequence seq0 + i; the whole wave calls it. The host sends a burst only
+// while no expiry is due anywhere in it (nat_process_burst), so no flow
+// leaves during the burst: a lookup that hits is final the moment it is made,
+// and only the misses depend on the packets before them. They are settled in
+// packet order by a bounded loop, one new LAN flow per round. Returns
+// kBurstServed, or kBurstDeclined -- before any table write -- when a frame
+// needs the byte-addressed path (nat_one: IP options); the host then runs the
+// burst through the batch pipeline.
+__device__ __forceinline__ uint32_t serve_burst(const NatArgs &a, const uint32_t *T,
+                                                ServeBox *box, uint32_t n, uint64_t seq0,
+                                                uint32_t lane) {
+  typedef unsigned v4u __attribute__((ext_vector_type(4)));
+  typedef unsigned v2u __attribute__((ext_vector_type(2)));
+  constexpr int kSys = 17;  // sc0 | sc1: system-coherent (bypasses the GPU caches)
+  constexpr uint32_t kBody = kServeBurst * kServeFrame;
+  const TableDev &t = a.t;
+  const auto fs = __builtin_amdgcn_make_buffer_rsrc(box->bframe, 0, (int)kBody, 0x00020000);
+  const auto ns = __builtin_amdgcn_make_buffer_rsrc(box->bnow, 0, 8 * kServeBurst, 0x00020000);
+  const auto es = __builtin_amdgcn_make_buffer_rsrc(box->bmeta, 0, 4 * kServeBurst, 0x00020000);
+  const auto os = __builtin_amdgcn_make_buffer_rsrc(box->bout, 0, 4 * kServeBurst, 0x00020000);
+  const bool act = lane < n;
+  // (lanes past the burst read zeros and store nothing: offsets past the resources)
+  const uint32_t slot0 = act ? lane * kServeFrame : kBody;
+  v4u q[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+    q[j] = __builtin_amdgcn_raw_buffer_load_b128(fs, (int)(slot0 + 16 * j), 0, kSys);
+  const uint32_t meta =
+      __builtin_amdgcn_raw_buffer_load_b32(es, act ? (int)(4 * lane) : (int)(4 * kServeBurst), 0, kSys);
+  const v2u nw =
+      __builtin_amdgcn_raw_buffer_load_b64(ns, act ? (int)(8 * lane) : (int)(8 * kServeBurst), 0, kSys);
+  const uint32_t len = min(meta & 0xFFFFu, kServeFrame), in = meta >> 16;
+  const int64_t now = (int64_t)((uint64_t)nw[0] | ((uint64_t)nw[1] << 32));
+  RFrame f;  // the first 64 bytes; bytes past len read as 0
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const uint4 v = chunk_keep(make_uint4(q[j][0], q[j][1], q[j][2], q[j][3]), 0, (int)len - 16 * j);
+    f.w[4 * j] = v.x;
+    f.w[4 * j + 1] = v.y;
+    f.w[4 * j + 2] = v.z;
+    f.w[4 * j + 3] = v.w;
+  }
+  // nat_one_reg's tests (nat_main.c:30-38); a frame parse_l34 would follow
+  // past a longer IPv4 header is the byte-addressed path's
+  const uint32_t et = f.w[3] & 0xFFFF, ihl = (f.w[3] >> 16) & 0x0F;
+  const uint32_t tl = bswap16((uint16_t)(f.w[4] & 0xFFFF));
+  const uint16_t unread = (uint16_t)(len - 14);
+  const uint32_t proto = f.w[5] >> 24;
+  const bool ip = act && et == 0x0008 && unread >= 20 && unread >= tl;
+  if (__ballot(ip && ihl > 5)) return kBurstDeclined;
+  const bool go =
+      ip && ihl == 5 && ((proto == 6) | (proto == 17)) && (uint32_t)(len - 34) >= 4u;
+  // the L4 checksum's bytes past 64, [64, min(14 + total_length, len)), summed
+  // straight from the mailbox: each lane its own frame, eight loads in flight
+  uint32_t tail = 0;
+  {
+    const uint32_t end = go ? min(14 + tl, len) : 0u;
+    for (uint32_t base = 64; __ballot(base < end); base += 128) {
+      v4u x[8];
+#pragma unroll
+      for (uint32_t u = 0; u < 8; u++) {
+        const uint32_t cc = base + 16 * u;
+        x[u] = __builtin_amdgcn_raw_buffer_load_b128(fs, (int)(cc < end ? slot0 + cc : kBody), 0,
+                                                     kSys);
+      }
+#pragma unroll
+      for (uint32_t u = 0; u < 8; u++) {
+        const uint32_t cc = base + 16 * u;
+        tail = sum16x4(
+            chunk_keep(make_uint4(x[u][0], x[u][1], x[u][2], x[u][3]), 0, (int)end - (int)cc),
+            tail);
+      }
+    }
+  }
+  const uint32_t sp = f.w[8] >> 16, dp = f.w[9] & 0xFFFF;
+  const uint32_t sip = f.u32at2(26), dip = f.u32at2(30);
+  const bool lanp = go && in != a.wan;
+  const uint32_t key[4] = {sp | (dp << 16), sip, dip, in | (proto << 16)};
+  const uint32_t hh = flowid_hash_batched(T, sp, dp, sip, dip, in, proto);
+  const int wi = (int)dp - (int)a.start_port;
+  const bool wanp = go && in == a.wan && wi >= 0 && wi < (int)t.cap;  // (else: a drop)
+  const uint32_t widx = wanp ? (uint32_t)wi : 0u;
+  // round 0: every lane looks its flow up in the table as the burst found it
+  uint32_t idx = kNone, fresh = 0;
+  if (lanp) idx = tbl_probe(t, hh, key);
+  if (wanp && t.slot_of[widx] != kNone) idx = widx;
+  bool lpend = lanp && idx == kNone, wpend = wanp && idx == kNone;
+  // the misses in packet order: the lowest pending LAN lane m looks again (an
+  // earlier lane of this burst may have inserted its key) and allocates as a
+  // packet of its own would (one_lan: kNone when the table is full, a drop);
+  // a pending WAN lane below m has every flow born before it in the table
+  // and is final, hit or drop. At most one round per lane.
+  for (uint32_t r = 0; r < kServeBurst; r++) {
+    const uint64_t lp = __ballot(lpend);
+    if (!lp) break;
+    const uint32_t m = (uint32_t)__ffsll((unsigned long long)lp) - 1;
+    if (wpend && lane < m) {
+      if (t.slot_of[widx] != kNone) idx = widx;
+      wpend = false;
+    }
+    if (lane == m) {
+      idx = one_lan(t, hh, key, now, seq0 + lane, &fresh);
+      lpend = false;
+    }
+    // (lane m's insert before the later lanes' lookups: one wave, workgroup
+    // scope; an agent-scope release would write the XCD's L2 back)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
+  if (wpend && t.slot_of[widx] != kNone) idx = widx;  // (no LAN miss before them is left)
+  // Stamps. idx != kNone: a LAN packet with a flow (a table-full drop stamps
+  // nothing) or a WAN packet whose port holds one (stamped before the
+  // anti-spoof check). For every index the burst's last packet that touched
+  // it must win: the highest lane holding an index stores both words, the
+  // others store nothing (no order between lanes' stores is relied on).
+  bool last = idx != kNone;
+  for (uint32_t j = 1; j < n; j++) {
+    const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)idx, (int)j);
+    if (j > lane && o == idx) last = false;
+  }
+  if (last) one_stamp(t, idx, now, seq0 + lane);
+  // the rewrite, each lane its own frame
+  uint32_t out = in, rew = 0;
+  if (idx != kNone) {
+    uint32_t dst = a.wan;
+    if (lanp) {
+      f.set32at2(26, a.ext_ip);
+      f.set16(34, (uint16_t)(a.start_port + idx));
+      rew = 1;
+    } else {
+      const uint4 k = tbl_key_of(t, idx);
+      if (!((k.z != sip) | ((k.x >> 16) != sp) | (((k.w >> 16) & 0xFF) != proto))) {
+        f.set32at2(30, k.y);        // dst_addr = flow.src_ip
+        f.set16(36, k.x & 0xFFFF);  // dst_port = flow.src_port
+        dst = k.w & 0xFFFF;
+        rew = 1;
+      }
+    }
+    if (rew) {
+      uint32_t mw[3];
+      macs_for(a, dst, mw);
+      fast_checksums(f, proto, tl, tail);
+      f.w[0] = mw[0];
+      f.w[1] = mw[1];
+      f.w[2] = mw[2];
+      out = dst;
+    }
+  }
+  // back: a rewritten frame's first 64 bytes (a rewrite touches nothing past
+  // byte 51; the host copies min(len, 64) of them), then the out words, four
+  // lanes' in one store
+  if (rew) {
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+      __builtin_amdgcn_raw_buffer_store_b128(
+          (v4u){f.w[4 * j], f.w[4 * j + 1], f.w[4 * j + 2], f.w[4 * j + 3]}, fs,
+          (int)(slot0 + 16 * j), 0, kSys);
+  }
+  const uint32_t res = out | (fresh << 16) | (rew << 17);
+  v4u o4;
+#pragma unroll
+  for (int k = 0; k < 4; k++) o4[k] = (uint32_t)__shfl((int)res, (int)((4 * lane + k) & 63));
+  if (4 * lane < n) __builtin_amdgcn_raw_buffer_store_b128(o4, os, (int)(16 * lane), 0, kSys);
+  // (all of it complete before the answer chunk that announces it)
+  __atomic_signal_fence(__ATOMIC_SEQ_CST);
+  __builtin_amdgcn_s_waitcnt(0);
+  __atomic_signal_fence(__ATOMIC_SEQ_CST);
+  return kBurstServed;
+}
+
 // The server: one wave. Every poll reads the request chunks whole (ServeBox,
 // vp_internal.h: one PCIe read brings the doorbell, the time and a frame of up
 // to kServeInline bytes), one poll in flight per wave (VIGPATH_SERVE_WAVES
@@ -2157,7 +2329,10 @@ __device__ __forceinline__ uint32_t nat_one_reg(const NatArgs &a, const uint32_t
 // wave sums the L4 bytes past byte 64, lane 0 runs the packet, the frame goes
 // back (16-byte system-coherent stores) and the answer word follows once
 // every store has completed. Packets take global sequence numbers seq, seq +
-// 1, ... It leaves on the leave request or after `idle` wall-clock ticks
+// 1, ... A burst request (a small vp_process_batch / vp_process_mbufs call,
+// nat_process_burst) brings up to kServeBurst frames in the burst body; the
+// wave that claims it serves it whole, one lane per packet (serve_burst), and
+// it takes as many sequence numbers. It leaves on the leave request or after `idle` wall-clock ticks
 // without a request; a request posted as it leaves finds the stream idle and
 // the host launches it again (nat_process_one). flags: bit 0, the stage
 // clock (VIGPATH_SERVE_PROF); bits 3-9: the waves' stagger in wall-clock
@@ -2169,16 +2344,17 @@ __global__ __launch_bounds__(256) void nat_serve(NatArgs a, ServeBox *box, uint6
   __shared__ uint4 fr[kServeFrame / 16];
   __shared__ uint32_t done_s, claim_s;  // the last answered / claimed request
   __shared__ uint64_t t0_s;             // the last answer's wall clock
+  __shared__ uint64_t seq_s;            // the next packet's sequence (a burst takes n)
   const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   if (threadIdx.x == 0) {
     const uint32_t d = (uint32_t)__hip_atomic_load(&box->ans, __ATOMIC_ACQUIRE,
                                                    __HIP_MEMORY_SCOPE_SYSTEM);
     done_s = d;
     claim_s = d;
+    seq_s = seq0;
     t0_s = wall_clock64();
   }
   load_nat_tables(T, a);  // (its barrier covers the words above)
-  const uint32_t done0 = done_s;
   const bool prof = flags & 1u;
   typedef unsigned v4u __attribute__((ext_vector_type(4)));
   constexpr int kSys = 17;  // sc0 | sc1: system-coherent (bypasses the GPU caches)
@@ -2200,7 +2376,9 @@ __global__ __launch_bounds__(256) void nat_serve(NatArgs a, ServeBox *box, uint6
     if (tag0 != want) return -1;
     const uint32_t hi = __builtin_amdgcn_readfirstlane(c[0]);
     if (hi == kServeLeave) return 1;
-    const uint32_t len = min(hi & 0xFFFFu, kServeFrame), in = hi >> 16;
+    // a burst: chunk 0 alone, the frames in the burst body (ServeBox)
+    const bool burst = (hi & 0xFFFFu) == kServeBurstOp;
+    const uint32_t len = burst ? 0u : min(hi & 0xFFFFu, kServeFrame), in = hi >> 16;
     const bool inl = len <= kServeInline;
     const uint32_t need = inl ? (12 + len + 11) / 12 : 1u;  // chunks carrying it
     if (__ballot(lane < need && c[3] != want)) return -1;  // not whole yet: poll again
@@ -2210,7 +2388,26 @@ __global__ __launch_bounds__(256) void nat_serve(NatArgs a, ServeBox *box, uint6
     if (!__builtin_amdgcn_readfirstlane(won)) return -1;
     const uint64_t s0 = wall_clock64();
     const uint64_t t0_prev = prof ? t0_s : 0;  // (the last answer's clock)
-    const uint64_t seq = seq0 + (want - done0 - 1);
+    // (written by the wave that served the request before, ahead of done_s)
+    const uint64_t seq = __hip_atomic_load(&seq_s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (burst) {
+      // the wave that claimed the request serves all of it, whatever
+      // VIGPATH_SERVE_WAVES is: lane i = packet i (serve_burst)
+      const uint32_t bn = min(max(in, 1u), kServeBurst);
+      const uint32_t st = serve_burst(a, T, box, bn, seq, lane);
+      if (lane == 0) {
+        __builtin_amdgcn_raw_buffer_store_b128((v4u){st, bn, 0u, want}, as, 0, 0, kSys);
+        __hip_atomic_store(&box->ans, (uint64_t)want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        t0_s = wall_clock64();
+        if (st == kBurstServed) seq_s = seq + bn;
+      }
+      // (every lane's table writes before the next request's wave reads them)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      if (lane == 0)
+        __hip_atomic_store(&done_s, want, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      wave_lds_sync();
+      return 0;
+    }
     const int64_t now =
         (int64_t)((uint64_t)__builtin_amdgcn_readfirstlane(c[1]) |
                   ((uint64_t)__builtin_amdgcn_readfirstlane(c[2]) << 32));
@@ -2295,6 +2492,7 @@ __global__ __launch_bounds__(256) void nat_serve(NatArgs a, ServeBox *box, uint6
       const uint64_t ans = (uint64_t)want | ((uint64_t)res << 32);
       __hip_atomic_store(&box->ans, ans, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       t0_s = wall_clock64();
+      seq_s = seq + 1;
       if (prof) {
         auto put = [&](int k, uint64_t v) {
           __hip_atomic_store(&box->prof[k], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -3270,6 +3468,7 @@ static int serve_launch(vp_ctx *c) {
                                              (g_srv_prof ? 1u : 0u) | (gap << 3) |
                                                  (after << 10) | (adapt << 18) | (up << 19));
   VP_HIP(hipGetLastError());
+  c->srv_stats.launches += 1;
   if (!c->srv_on) {
     static std::once_flag once;
     std::call_once(once, [] { atexit(serve_stop_all); });
@@ -3280,21 +3479,16 @@ static int serve_launch(vp_ctx *c) {
   return 0;
 }
 
-int nat_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, int64_t now,
-                    uint16_t *out) {
-  std::lock_guard<std::recursive_mutex> sg(c->srv_mu);
+static bool serve_off() {  // VIGPATH_SERVE=0
   static const bool off = [] {
     const char *e = getenv("VIGPATH_SERVE");
     return e && !atoi(e);
   }();
-  FlowTable &t = c->ft;
-  // no expiry due at this packet (run_batch's test for a segment of one)
-  const bool ok = !off && !c->comm && len <= kServeFrame && now >= 0 && now >= c->last_now &&
-                  nat_cutoff(c, now) <= (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)now);
-  if (!ok) {
-    VP_TRY(serve_stop(c));
-    return 1;
-  }
+  return off;
+}
+
+// The mailbox exists and the server runs (the caller holds c->srv_mu).
+static int serve_ready(vp_ctx *c) {
   if (!c->sbox || !c->srv_on) VP_HIP(hipSetDevice(c->gpu));  // (HIP calls below)
   if (!c->sbox) {
     VP_HIP(hipHostMalloc((void **)&c->sbox, sizeof(ServeBox),
@@ -3312,6 +3506,52 @@ int nat_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, in
     // queued behind it on the same stream
     VP_TRY(serve_launch(c));
   }
+  return 0;
+}
+
+// Wait for the answer to request `req`: chunk 0's tag, then the other chunks'
+// (`need`: as many as the request took), each chunk's bytes final once its tag
+// is the request's. A kernel that left (idle) before it saw the request is
+// launched again.
+static int serve_wait(vp_ctx *c, uint32_t req, uint32_t need) {
+  ServeBox *bx = c->sbox;
+  auto last = std::chrono::steady_clock::now();
+  auto answered = [&]() {
+    for (uint32_t k = 0; k < need; k++)
+      if (__atomic_load_n(&bx->amsg[k][3], __ATOMIC_ACQUIRE) != req) return false;
+    return true;
+  };
+  uint32_t spins = 0;
+  while (!answered()) {
+    __builtin_ia32_pause();
+    if (++spins & 255) continue;  // (the clock read every 256 spins, not each)
+    const auto nw = std::chrono::steady_clock::now();
+    if (nw - last < std::chrono::microseconds(200)) continue;
+    last = nw;
+    // the kernel left (idle) before it saw the request: launch it again
+    VP_HIP(hipSetDevice(c->gpu));
+    const hipError_t q = hipStreamQuery(c->stream);
+    if (q == hipErrorNotReady) continue;
+    VP_HIP(q);
+    if (answered()) continue;
+    VP_TRY(serve_launch(c));
+  }
+  return 0;
+}
+
+int nat_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, int64_t now,
+                    uint16_t *out) {
+  std::lock_guard<std::recursive_mutex> sg(c->srv_mu);
+  FlowTable &t = c->ft;
+  // no expiry due at this packet (run_batch's test for a segment of one)
+  const bool ok = !serve_off() && !c->comm && len <= kServeFrame && now >= 0 &&
+                  now >= c->last_now &&
+                  nat_cutoff(c, now) <= (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)now);
+  if (!ok) {
+    VP_TRY(serve_stop(c));
+    return 1;
+  }
+  VP_TRY(serve_ready(c));
   ServeBox *bx = c->sbox;
   const auto h0 = std::chrono::steady_clock::now();
   // the request chunks (ServeBox): payload words first, then each chunk's
@@ -3334,29 +3574,8 @@ int nat_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, in
     bx->msg[k][2] = m[3 * k + 2];
     __atomic_store_n(&bx->msg[k][3], req, __ATOMIC_RELEASE);
   }
-  // the answer: chunk 0's tag, then (frames of up to kServeInline bytes) the
-  // other chunks' tags, each chunk's bytes final once its tag is the request's
-  auto last = h0;  // (need: the chunks the request took, as many as the answer takes)
-  auto answered = [&]() {
-    for (uint32_t k = 0; k < need; k++)
-      if (__atomic_load_n(&bx->amsg[k][3], __ATOMIC_ACQUIRE) != req) return false;
-    return true;
-  };
-  uint32_t spins = 0;
-  while (!answered()) {
-    __builtin_ia32_pause();
-    if (++spins & 255) continue;  // (the clock read every 256 spins, not each)
-    const auto nw = std::chrono::steady_clock::now();
-    if (nw - last < std::chrono::microseconds(200)) continue;
-    last = nw;
-    // the kernel left (idle) before it saw the request: launch it again
-    VP_HIP(hipSetDevice(c->gpu));
-    const hipError_t q = hipStreamQuery(c->stream);
-    if (q == hipErrorNotReady) continue;
-    VP_HIP(q);
-    if (answered()) continue;
-    VP_TRY(serve_launch(c));
-  }
+  // (need: the chunks the request took, as many as the answer takes)
+  VP_TRY(serve_wait(c, req, need));
   const uint32_t res = bx->amsg[0][0];
   if (len <= kServeInline) {
     uint32_t m2[3 * kServeChunks];
@@ -3374,6 +3593,7 @@ int nat_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, in
   if ((ans >> 48) & 1u) t.ts_floor = std::min<uint64_t>(t.ts_floor, (uint64_t)now);
   c->seq += 1;
   c->last_now = now;
+  c->srv_stats.packets_one += 1;
   if (g_srv_prof) {  // (device stamps: wall clock ticks, 100 MHz)
     const double us_tick = 1e3 / (double)(c->srv_idle / c->srv_idle_ms);
     c->srv_prof[0] +=
@@ -3391,6 +3611,78 @@ int nat_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, in
     c->srv_prof[4] += us_tick * (double)(p[7] - p[6]);
     c->srv_prof[10] += (double)(p[9] - p[8]);  // (shader cycles over `packet`: MHz)
     c->srv_prof[5] += 1;
+  }
+  return 0;
+}
+
+// The largest host batch routed to the server as burst requests: the largest
+// n for which the served path measured faster per packet than the batch
+// pipeline on the MI355X (profiles/r07_burst_sweep.txt: 0.24 against 0.30 us
+// at 256, 0.26 against 0.20 at 384); larger calls take the pipeline. A call
+// above kServeBurst goes as consecutive requests, one in flight.
+// VIGPATH_SERVE_BURST overrides it; 0 routes nothing.
+constexpr uint32_t kServeBurstRoute = 256;
+
+int nat_process_burst(vp_ctx *c, const vp_mbuf_batch *b, uint32_t first, uint32_t count,
+                      uint32_t *served) {
+  *served = 0;
+  std::lock_guard<std::recursive_mutex> sg(c->srv_mu);
+  static const uint32_t limit = [] {
+    const char *e = getenv("VIGPATH_SERVE_BURST");
+    return e ? (uint32_t)std::max(0, atoi(e)) : kServeBurstRoute;
+  }();
+  if (serve_off() || c->comm || count == 0 || count > limit) return 1;
+  FlowTable &t = c->ft;
+  auto at = [&](uint32_t i) {
+    return b->now ? b->now[first + i] : b->now0 + (int64_t)(first + i) * b->now_step;
+  };
+  // the whole range or none of it: frames the mailbox holds, times that do
+  // not go back, and no expiry due anywhere in it -- the cutoff is monotone in
+  // time and flows born in the range are stamped >= its first time, so the
+  // last packet's cutoff against the floor as the range finds it decides
+  const int64_t n0 = at(0), n1 = at(count - 1);
+  if (n0 < 0 || n0 < c->last_now) return 1;
+  int64_t prev = n0;
+  for (uint32_t i = 0; i < count; i++) {
+    const int64_t ti = at(i);
+    if (b->len[first + i] > kServeFrame || ti < prev) return 1;
+    prev = ti;
+  }
+  if (nat_cutoff(c, n1) > (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)n0)) return 1;
+  VP_TRY(serve_ready(c));
+  ServeBox *bx = c->sbox;
+  for (uint32_t a0 = 0; a0 < count; a0 += kServeBurst) {
+    const uint32_t m = std::min(kServeBurst, count - a0);
+    // the body first, then the tagged chunk that announces it (ServeBox)
+    for (uint32_t i = 0; i < m; i++) {
+      const uint32_t p = first + a0 + i;
+      if (b->len[p]) memcpy(bx->bframe[i], b->frames[p], b->len[p]);
+      bx->bmeta[i] = b->len[p] | ((uint32_t)b->in_dev[p] << 16);
+      bx->bnow[i] = at(a0 + i);
+    }
+    const uint32_t req = ++c->srv_req;
+    bx->msg[0][0] = kServeBurstOp | (m << 16);
+    bx->msg[0][1] = 0;
+    bx->msg[0][2] = 0;
+    __atomic_store_n(&bx->msg[0][3], req, __ATOMIC_RELEASE);
+    VP_TRY(serve_wait(c, req, 1));
+    if (bx->amsg[0][0] != kBurstServed) {  // a byte-path frame: nothing of it was done
+      c->srv_stats.declined += 1;
+      return 1;
+    }
+    bool fresh = false;
+    for (uint32_t i = 0; i < m; i++) {
+      const uint32_t p = first + a0 + i, r = bx->bout[i];
+      b->out_dev[p] = (uint16_t)r;
+      fresh |= (r >> 16) & 1u;
+      if ((r >> 17) & 1u) memcpy(b->frames[p], bx->bframe[i], std::min<uint32_t>(b->len[p], 64));
+    }
+    if (fresh) t.ts_floor = std::min<uint64_t>(t.ts_floor, (uint64_t)at(a0));
+    c->seq += m;
+    c->last_now = at(a0 + m - 1);
+    c->srv_stats.bursts += 1;
+    c->srv_stats.burst_packets += m;
+    *served += m;
   }
   return 0;
 }

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import (BridgeConfigC, DevBatchC, FwConfigC, LbConfigC, MbufBatchC,
-               NatConfigC, PolConfigC, TableStatsC, _check, lib)
+               NatConfigC, PolConfigC, ServeStatsC, TableStatsC, _check, lib)
 
 
 def _dptr(t):
@@ -294,6 +294,15 @@ class Nat(NfBase):
         self.cfg = cfg
         self._ck(self.L.vp_nat_create(C.byref(cfg), gpu, C.byref(self.h)),
                "vp_nat_create")
+
+    def serve_stats(self) -> dict:
+        """vp_serve_stats_get: what the resident kernel served so far --
+        packets_one (vp_process_one), bursts / burst_packets (small
+        vp_process_batch / vp_process_mbufs calls), declined, launches. A
+        host-side counter read: the kernel stays."""
+        st = ServeStatsC()
+        self._ck(self.L.vp_serve_stats_get(self.h, C.byref(st)), "vp_serve_stats_get")
+        return {k: int(getattr(st, k)) for k, _ in ServeStatsC._fields_}
 
     def dump(self):
         n = self.cfg.max_flows
