@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""The drop-in boundary, timed for one NF: host/nf_loop_<nf> (nf.c's loop
+restated over a trace file, linked against lib<nf>_nf.so) the way bench.py's
+per_packet_drop_in times vignat -- `--flows` flows opened by an untimed
+warm-up, then `--packets` steady LAN hits round robin, each with its own time
+stamp; every packet through nf_process one at a time (batch 0, nf.c:150-176)
+and through vp_process_batch in bursts (nf.c:178-215).
+
+  tools/bench_dropin.py --nf fw                      # batch 0 / 32 / 1024
+  tools/bench_dropin.py --nf fw --sweep 32,64,128    # burst routing limit
+
+--sweep N,...: each burst size twice in this run, VIGPATH_SERVE_BURST forcing
+the resident kernel (a limit above every N) and the batch pipeline (0): the
+routing limit (kServeBurstRoute / kFwBurstRoute) is the largest N at which
+the served path is the faster one per packet.
+
+--tree DIR: another build of the library (a checkout of another commit with
+its own host/ and vigor_amd/), for A/B on one machine in one session.
+
+Prints one JSON line per measurement; --out appends them to a file.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from vigor_amd import traces as T  # noqa: E402
+
+SLOT = 64
+NF = {
+    "nat": dict(loop="nf_loop", trace=T.nat_lan_trace,
+                args=["--expire", "60000000", "--starting-port", "0", "--wan", "1",
+                      "--extip", "192.168.4.2", "--eth-dest", "0,90:e2:ba:55:12:20",
+                      "--eth-dest", "1,90:e2:ba:55:12:21"]),
+    "fw": dict(loop="nf_loop_fw", trace=T.fw_trace,
+               args=["--expire", "60000000", "--wan", "1",
+                     "--eth-dest", "0,90:e2:ba:55:12:20",
+                     "--eth-dest", "1,90:e2:ba:55:12:21"]),
+}
+
+
+def run_loop(tree, nf, tin, tout, flows, batch, env):
+    """One nf_loop run: us per timed packet (its out ports are left in tout)."""
+    cmd = [os.path.join(tree, "host", NF[nf]["loop"]), tin, tout, "--warm", str(flows)]
+    if batch:
+        cmd += ["--batch", str(batch)]
+    cmd += ["--"] + NF[nf]["args"] + ["--max-flows", str(flows)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, **env))
+    if r.returncode != 0:
+        raise RuntimeError("%s failed (%d): %s" % (cmd[0], r.returncode, r.stderr[-500:]))
+    line = [x for x in r.stderr.splitlines() if x.startswith("timed ")][-1]
+    return float(line.split(",")[1].split()[0])
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__,
+                                 formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--nf", choices=sorted(NF), default="fw")
+    ap.add_argument("--packets", type=int, default=20000)
+    ap.add_argument("--flows", type=int, default=1024)
+    ap.add_argument("--batches", default="0,32,1024")
+    ap.add_argument("--sweep", default="", help="burst sizes, each served and through the pipeline")
+    ap.add_argument("--repeat", type=int, default=3, help="runs per point (all reported)")
+    ap.add_argument("--tree", default=ROOT)
+    ap.add_argument("--label", default="")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    n = a.flows + a.packets
+    fr, ln, dv, now = NF[a.nf]["trace"](n, a.flows)
+    points = []
+    if a.sweep:
+        for bt in [int(x) for x in a.sweep.split(",")]:
+            points.append((bt, "served", {"VIGPATH_SERVE_BURST": "1000000"}))
+            points.append((bt, "pipeline", {"VIGPATH_SERVE_BURST": "0"}))
+    else:
+        points = [(int(x), "default", {}) for x in a.batches.split(",")]
+    with tempfile.TemporaryDirectory() as d:
+        tin, tout = os.path.join(d, "t.in"), os.path.join(d, "t.out")
+        with open(tin, "wb") as f:
+            f.write(b"VPTR" + np.array([n, SLOT], np.uint32).tobytes())
+            f.write(dv.astype(np.uint16).tobytes() + ln.astype(np.uint16).tobytes())
+            f.write(now.astype(np.int64).tobytes() + fr.tobytes())
+        for bt, path, env in points:
+            us = []
+            for _ in range(a.repeat):
+                us.append(run_loop(a.tree, a.nf, tin, tout, a.flows, bt, env))
+                out = np.frombuffer(open(tout, "rb").read(), np.uint16, n, 12)
+                assert (out[a.flows:] == 1).all()  # every steady packet out on the WAN port
+            rec = {"nf": a.nf, "label": a.label, "batch": bt, "path": path,
+                   "packets": a.packets, "flows": a.flows,
+                   "us_per_packet": [round(x, 3) for x in us],
+                   "us_per_packet_min": round(min(us), 3)}
+            line = json.dumps(rec)
+            print(line, flush=True)
+            if a.out:
+                with open(a.out, "a") as f:
+                    f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

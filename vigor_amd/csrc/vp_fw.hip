@@ -23,7 +23,9 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <algorithm>
 #include <cstring>
+#include <mutex>
 #include <vector>
 
 #include "vp_table.h"
@@ -375,6 +377,381 @@ __global__ void fw_defer_finish(FwArgs a, const uint32_t *list, uint32_t n) {
   }
 }
 
+// ========================================================= one packet ==
+// nf.c calls nf_process once per packet (nf.c:150-176) or once per small
+// burst (its VIGOR_BATCH_SIZE loop, nf.c:178-215). Through the batch path
+// each call costs a launch sequence and a host round trip; vp_process_one and
+// small vp_process_mbufs calls instead go to fw_serve, one wave that stays
+// resident and polls the host-coherent mailbox (ServeBox, vp_internal.h), as
+// nat_serve does for vignat: no launch and no copy call per packet. The host
+// sends requests only while no expiry is due (fw_process_one /
+// fw_process_burst), so the kernel restates fw_main.c:21-80 without the
+// expiry step.
+
+// The FlowId a packet looks up (fw_key) and its hash from the LDS tables.
+__device__ __forceinline__ uint32_t fw_key_hash(const uint32_t *T, bool wan, uint32_t sp,
+                                                uint32_t dp, uint32_t sip, uint32_t dip,
+                                                uint32_t proto, uint32_t key[4]) {
+  fw_key(wan, sp, dp, sip, dip, proto, key);
+  const uint32_t s0 = key[0] & 0xFFFF, d0 = key[0] >> 16, si = key[1], di = key[2];
+  return crc13_lds(T, s0 & 0xFF, (s0 >> 8) & 0xFF, d0 & 0xFF, (d0 >> 8) & 0xFF, si & 0xFF,
+                   (si >> 8) & 0xFF, (si >> 16) & 0xFF, si >> 24, di & 0xFF, (di >> 8) & 0xFF,
+                   (di >> 16) & 0xFF, di >> 24, proto & 0xFF);
+}
+
+// flow_manager_allocate_or_refresh_flow (fw_flowmanager.c:38-62) for one LAN
+// FlowId from device `in` at global sequence seq: the flow's index, allocated
+// when new (*fresh = 1; dchain_allocate_new_index: the freed stack first, then
+// the never-used range); kNone with nothing stored when no index is free.
+__device__ __forceinline__ uint32_t fw_one_lan(const TableDev &t, uint32_t hh,
+                                               const uint32_t key[4], uint32_t in, uint64_t seq,
+                                               uint32_t *fresh) {
+  uint32_t idx = tbl_probe<0xFFu>(t, hh, key);
+  if (idx != kNone) return idx;
+  Ctl *c = t.ctl;
+  const uint32_t st = c->stack_top, fn = c->fresh_next;
+  if (st) {
+    idx = t.stack[st - 1];
+    c->stack_top = st - 1;
+  } else if (fn < t.cap) {
+    idx = fn;
+    c->fresh_next = fn + 1;
+  } else {
+    return kNone;  // fw_flowmanager.c:47-51
+  }
+  // (int_devices in the key's padding bytes, as fw_miss_finish stores it)
+  const uint32_t k[4] = {key[0], key[1], key[2], key[3] | (in << 8)};
+  bool tomb = false;
+  uint32_t disp = 0;
+  const uint32_t e = tbl_insert(t, hh, k, idx, &tomb, &disp);
+  if (tomb) c->n_tomb -= 1;
+  c->n_live += 1;
+  c->sh_live += 1;
+  c->disp_count += disp;
+  t.slot_of[idx] = e;
+  t.hash_of[idx] = hh;
+  t.birth[idx] = seq;
+  *fresh = 1;
+  return idx;
+}
+
+// The touch of index idx at (now, seq), right behind the lookup.
+__device__ __forceinline__ void fw_stamp(const TableDev &t, uint32_t idx, int64_t now,
+                                         uint64_t seq) {
+  t.ts[idx] = (uint64_t)now;
+  t.tseq[idx] = seq;
+}
+
+// fw_main.c:44-72 for one TCP/UDP packet: the device it goes out on, or kNone
+// for a WAN packet of no known flow (a drop). A LAN packet goes out on the
+// WAN device whether or not its flow found an index.
+__device__ __forceinline__ uint32_t fw_one_flow(const FwArgs &a, const uint32_t *T, uint32_t in,
+                                                uint32_t sp, uint32_t dp, uint32_t sip,
+                                                uint32_t dip, uint32_t proto, int64_t now,
+                                                uint64_t seq, uint32_t *fresh) {
+  const bool wan = in == a.wan;
+  uint32_t key[4];
+  const uint32_t hh = fw_key_hash(T, wan, sp, dp, sip, dip, proto, key);
+  uint32_t idx, dst = a.wan;
+  if (wan) {
+    uint32_t w3 = 0;
+    idx = tbl_probe<0xFFu>(a.t, hh, key, &w3);
+    if (idx == kNone) return kNone;
+    dst = w3 >> 8;
+  } else {
+    idx = fw_one_lan(a.t, hh, key, in, seq, fresh);
+  }
+  if (idx != kNone) fw_stamp(a.t, idx, now, seq);
+  return dst;
+}
+
+// A burst request (ServeBox): n frames as nf_process would take them one after
+// another, lane i = packet i at sequence seq0 + i; the whole wave calls it.
+// No flow leaves during a burst (the host sends one only while no expiry is
+// due anywhere in it), so a lookup that hits is final and only the misses
+// depend on the packets before them: they settle in packet order, one new LAN
+// flow per round (serve_burst, vp_nat.hip, is vignat's form of the same
+// loop). Only the first 64 bytes of a frame are read and only its first 16
+// can change. Returns kBurstServed, or kBurstDeclined -- before any table
+// write -- when a frame has IPv4 options (the byte-addressed path's).
+__device__ __forceinline__ uint32_t fw_burst(const FwArgs &a, const uint32_t *T, ServeBox *box,
+                                             uint32_t n, uint64_t seq0, uint32_t lane) {
+  typedef unsigned v4u __attribute__((ext_vector_type(4)));
+  typedef unsigned v2u __attribute__((ext_vector_type(2)));
+  constexpr int kSys = 17;  // sc0 | sc1: system-coherent (bypasses the GPU caches)
+  constexpr uint32_t kBody = kServeBurst * kServeFrame;
+  const TableDev &t = a.t;
+  const auto fs = __builtin_amdgcn_make_buffer_rsrc(box->bframe, 0, (int)kBody, 0x00020000);
+  const auto ns = __builtin_amdgcn_make_buffer_rsrc(box->bnow, 0, 8 * kServeBurst, 0x00020000);
+  const auto es = __builtin_amdgcn_make_buffer_rsrc(box->bmeta, 0, 4 * kServeBurst, 0x00020000);
+  const auto os = __builtin_amdgcn_make_buffer_rsrc(box->bout, 0, 4 * kServeBurst, 0x00020000);
+  const bool act = lane < n;
+  // (lanes past the burst read zeros and store nothing: offsets past the resources)
+  const uint32_t slot0 = act ? lane * kServeFrame : kBody;
+  v4u q[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+    q[j] = __builtin_amdgcn_raw_buffer_load_b128(fs, (int)(slot0 + 16 * j), 0, kSys);
+  const uint32_t meta =
+      __builtin_amdgcn_raw_buffer_load_b32(es, act ? (int)(4 * lane) : (int)(4 * kServeBurst), 0, kSys);
+  const v2u nw =
+      __builtin_amdgcn_raw_buffer_load_b64(ns, act ? (int)(8 * lane) : (int)(8 * kServeBurst), 0, kSys);
+  const uint32_t len = min(meta & 0xFFFFu, kServeFrame), in = meta >> 16;
+  const int64_t now = (int64_t)((uint64_t)nw[0] | ((uint64_t)nw[1] << 32));
+  RFrame f;  // the first 64 bytes; bytes past len read as 0
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const uint4 v = chunk_keep(make_uint4(q[j][0], q[j][1], q[j][2], q[j][3]), 0, (int)len - 16 * j);
+    f.w[4 * j] = v.x;
+    f.w[4 * j + 1] = v.y;
+    f.w[4 * j + 2] = v.z;
+    f.w[4 * j + 3] = v.w;
+  }
+  // fw_issue's tests (fw_main.c:26-40); a frame parse_l34 would follow past a
+  // longer IPv4 header is the byte-addressed path's
+  const uint32_t et = f.w[3] & 0xFFFF, ihl = (f.w[3] >> 16) & 0x0F;
+  const uint32_t tl = bswap16((uint16_t)(f.w[4] & 0xFFFF));
+  const uint16_t unread = (uint16_t)(len - 14);
+  const uint32_t proto = f.w[5] >> 24;
+  const bool ip = act && et == 0x0008 && unread >= 20 && unread >= tl;
+  if (__ballot(ip && ihl > 5)) return kBurstDeclined;
+  const bool go =
+      ip && ihl == 5 && ((proto == 6) | (proto == 17)) && (uint32_t)(len - 34) >= 4u;
+  const uint32_t sp = f.w[8] >> 16, dp = f.w[9] & 0xFFFF;
+  const uint32_t sip = f.u32at2(26), dip = f.u32at2(30);
+  const bool wan = in == a.wan;
+  const bool lanp = go && !wan, wanp = go && wan;
+  uint32_t key[4];
+  const uint32_t hh = fw_key_hash(T, wan, sp, dp, sip, dip, proto, key);
+  // round 0: every lane looks its flow up in the table as the burst found it
+  uint32_t idx = kNone, fresh = 0, w3 = 0;
+  if (go) idx = tbl_probe<0xFFu>(t, hh, key, &w3);
+  bool lpend = lanp && idx == kNone, wpend = wanp && idx == kNone;
+  // the misses in packet order: the lowest pending LAN lane m looks again (an
+  // earlier lane of this burst may have inserted its FlowId) and allocates as
+  // a packet of its own would (fw_one_lan: kNone when no index is free, and
+  // nothing is written); a pending WAN lane below m has every flow born
+  // before it in the table and is final, hit or drop. At most one round per
+  // lane.
+  for (uint32_t r = 0; r < kServeBurst; r++) {
+    const uint64_t lp = __ballot(lpend);
+    if (!lp) break;
+    const uint32_t m = (uint32_t)__ffsll((unsigned long long)lp) - 1;
+    if (wpend && lane < m) {
+      idx = tbl_probe<0xFFu>(t, hh, key, &w3);
+      wpend = false;
+    }
+    if (lane == m) {
+      idx = fw_one_lan(t, hh, key, in, seq0 + lane, &fresh);
+      lpend = false;
+    }
+    // (lane m's insert before the later lanes' lookups: one wave, workgroup
+    // scope; an agent-scope release would write the XCD's L2 back)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
+  if (wpend) idx = tbl_probe<0xFFu>(t, hh, key, &w3);  // (no LAN miss before them is left)
+  // Stamps: for every index the burst's last packet that touched it must win.
+  // The highest lane holding an index stores both words, the others store
+  // nothing (no order between lanes' stores is relied on).
+  bool last = idx != kNone;
+  for (uint32_t j = 1; j < n; j++) {
+    const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)idx, (int)j);
+    if (j > lane && o == idx) last = false;
+  }
+  if (last) fw_stamp(t, idx, now, seq0 + lane);
+  // the rewrite: a LAN packet goes out on the WAN device with or without a
+  // flow (fw_flowmanager.c:49-53), a WAN packet to its flow's internal device
+  uint32_t out = in, rew = 0;
+  if (lanp || (wanp && idx != kNone)) {
+    out = lanp ? (uint32_t)a.wan : (w3 >> 8);
+    uint32_t mw[3];
+    fw_macs(a, out, mw);
+    // back: the frame's first 16 bytes (the MACs are bytes 0-11)
+    __builtin_amdgcn_raw_buffer_store_b128((v4u){mw[0], mw[1], mw[2], f.w[3]}, fs, (int)slot0, 0,
+                                           kSys);
+    rew = 1;
+  }
+  // the out words, four lanes' in one store
+  const uint32_t res = (out & 0xFFFFu) | (fresh << 16) | (rew << 17);
+  v4u o4;
+#pragma unroll
+  for (int k = 0; k < 4; k++) o4[k] = (uint32_t)__shfl((int)res, (int)((4 * lane + k) & 63));
+  if (4 * lane < n) __builtin_amdgcn_raw_buffer_store_b128(o4, os, (int)(16 * lane), 0, kSys);
+  // (all of it complete before the answer chunk that announces it)
+  __atomic_signal_fence(__ATOMIC_SEQ_CST);
+  __builtin_amdgcn_s_waitcnt(0);
+  __atomic_signal_fence(__ATOMIC_SEQ_CST);
+  return kBurstServed;
+}
+
+// The server: one wave (<<<1, 64>>>). Every poll reads the request chunks
+// whole (ServeBox: one PCIe read brings the doorbell, the time and the frame's
+// first kServeInline bytes -- vigfw reads nothing past byte 14 + 60 + 4 = 78,
+// so `frame` is never used). Lane 0 runs the packet: a frame with a 20-byte
+// IPv4 header in registers (fw_issue's tests), any other byte-addressed over
+// its LDS copy (parse_l34, as fw_generic_a). Only the MACs can change, so the
+// answer is chunk 0 (out | fresh << 16) and chunk 1 (frame bytes 0-11) in one
+// store instruction. Packets take global sequence numbers seq0, seq0 + 1, ...;
+// a burst request (fw_burst) takes as many as it has frames. The kernel
+// leaves on the leave request or after `idle` wall-clock ticks without a
+// request; the host launches it again (serve_wait). flags as nat_serve's:
+// bits 10-17 the first poll's delay after an answer, bit 18 adapt it, bits
+// 19-23 the ticks a late poll adds.
+__global__ __launch_bounds__(64) void fw_serve(FwArgs a, ServeBox *box, uint64_t seq0,
+                                               uint64_t idle, uint32_t flags) {
+  __shared__ uint32_t T[kFwTabWords];
+  __shared__ uint4 fr[(kServeInline + 15) / 16];
+  const uint32_t lane = threadIdx.x;
+  fw_load_tables(T, a);
+  if (a.t.mix == kMixLin) a.t.lin = fw_lin(T);  // (the layout's byte tables: their LDS copy)
+  typedef unsigned v4u __attribute__((ext_vector_type(4)));
+  constexpr int kSys = 17;  // sc0 | sc1: system-coherent (bypasses the GPU caches)
+  const auto ms = __builtin_amdgcn_make_buffer_rsrc(box->msg, 0, 16 * kServeChunks, 0x00020000);
+  const auto as = __builtin_amdgcn_make_buffer_rsrc(box->amsg, 0, 16 * kServeChunks, 0x00020000);
+  // (lanes past the chunks read nothing: an offset past the resource)
+  const int moff = lane < kServeChunks ? (int)(16 * lane) : (int)(16 * kServeChunks);
+  uint32_t *fword = reinterpret_cast<uint32_t *>(fr);
+  // the last answered request (a relaunched server goes on from the answer
+  // word), the next packet's sequence, the last answer's wall clock
+  uint32_t done = __builtin_amdgcn_readfirstlane((uint32_t)__hip_atomic_load(
+      &box->ans, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM));
+  uint64_t seq = seq0;
+  uint64_t t0 = wall_clock64();
+  // one poll's chunks: -1 nothing new (or not yet whole), 0 a request served,
+  // 1 leave
+  auto serve = [&](const v4u &c) -> int {
+    const uint32_t want = done + 1;
+    if (__builtin_amdgcn_readfirstlane(c[3]) != want) return -1;
+    const uint32_t hi = __builtin_amdgcn_readfirstlane(c[0]);
+    if (hi == kServeLeave) return 1;
+    const uint32_t in = hi >> 16;
+    if ((hi & 0xFFFFu) == kServeBurstOp) {  // chunk 0 alone, the frames in the burst body
+      const uint32_t bn = min(max(in, 1u), kServeBurst);
+      const uint32_t st = fw_burst(a, T, box, bn, seq, lane);
+      if (lane == 0) {
+        __builtin_amdgcn_raw_buffer_store_b128((v4u){st, bn, 0u, want}, as, 0, 0, kSys);
+        __hip_atomic_store(&box->ans, (uint64_t)want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+      if (st == kBurstServed) seq += bn;
+      t0 = wall_clock64();
+      done = want;
+      // (every lane's table writes before the next request reads them)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      return 0;
+    }
+    const uint32_t len = min(hi & 0xFFFFu, kServeFrame);
+    const uint32_t got = min(len, kServeInline);    // frame bytes in the chunks
+    const uint32_t need = (12 + got + 11) / 12;      // chunks carrying the request
+    if (__ballot(lane < need && c[3] != want)) return -1;  // not whole yet: poll again
+    const int64_t now = (int64_t)((uint64_t)__builtin_amdgcn_readfirstlane(c[1]) |
+                                  ((uint64_t)__builtin_amdgcn_readfirstlane(c[2]) << 32));
+    if (lane >= 1 && lane < need) {  // chunk k >= 1: frame bytes 12k - 12 .. 12k - 1
+      fword[3 * lane - 3] = c[0];
+      fword[3 * lane - 2] = c[1];
+      fword[3 * lane - 1] = c[2];
+    }
+    wave_lds_sync();
+    uint32_t res = 0, m0 = 0, m1 = 0, m2 = 0;
+    if (lane == 0) {
+      RFrame f;  // the first 64 bytes; bytes past len read as 0
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const uint4 v = chunk_keep(fr[j], 0, (int)len - 16 * j);
+        f.w[4 * j] = v.x;
+        f.w[4 * j + 1] = v.y;
+        f.w[4 * j + 2] = v.z;
+        f.w[4 * j + 3] = v.w;
+      }
+      const uint32_t et = f.w[3] & 0xFFFF, ihl = (f.w[3] >> 16) & 0x0F;
+      uint32_t sp = 0, dp = 0, sip = 0, dip = 0, proto = 0;
+      bool ok;
+      if (et == 0x0008 && ihl == 5) {
+        // nf_then_get_rte_ipv4_header / nf_then_get_tcpudp_header with IHL = 5
+        const uint32_t tl = bswap16((uint16_t)(f.w[4] & 0xFFFF));
+        const uint16_t unread = (uint16_t)(len - 14);
+        proto = f.w[5] >> 24;
+        ok = (unread >= 20) & (unread >= tl) & ((proto == 6) | (proto == 17)) &
+             ((uint32_t)(len - 34) >= 4u);
+        sp = f.w[8] >> 16, dp = f.w[9] & 0xFFFF;
+        sip = f.u32at2(26), dip = f.u32at2(30);
+      } else {  // byte-addressed over the LDS copy (bytes past it read as 0)
+        const GFrame g{reinterpret_cast<uint8_t *>(fr), got};
+        const L34 h = parse_l34(g, len);
+        ok = h.ok;
+        if (ok) {
+          proto = g.r8(h.ip + 9);
+          sp = g.r16(h.l4), dp = g.r16(h.l4 + 2);
+          sip = g.r32(h.ip + 12), dip = g.r32(h.ip + 16);
+        }
+      }
+      uint32_t fresh = 0;
+      const uint32_t dst =
+          ok ? fw_one_flow(a, T, in, sp, dp, sip, dip, proto, now, seq, &fresh) : kNone;
+      m0 = f.w[0], m1 = f.w[1], m2 = f.w[2];
+      uint32_t out = in;
+      if (dst != kNone) {  // fw_main.c:76-77
+        uint32_t mw[3];
+        fw_macs(a, dst, mw);
+        m0 = mw[0], m1 = mw[1], m2 = mw[2];
+        out = dst;
+      }
+      res = (out & 0xFFFFu) | (fresh << 16);
+    }
+    res = __builtin_amdgcn_readfirstlane(res);
+    m0 = __builtin_amdgcn_readfirstlane(m0);
+    m1 = __builtin_amdgcn_readfirstlane(m1);
+    m2 = __builtin_amdgcn_readfirstlane(m2);
+    // the answer chunks: the result and frame bytes 0-11, one store
+    if (lane < min(need, 2u)) {
+      const v4u v = lane == 0 ? (v4u){res, 0u, 0u, want} : (v4u){m0, m1, m2, want};
+      __builtin_amdgcn_raw_buffer_store_b128(v, as, (int)(16 * lane), 0, kSys);
+    }
+    // (the answer word: where a relaunched server starts counting; the host
+    // reads the answer chunks. No release fence at system scope, which would
+    // write back the whole L2)
+    if (lane == 0)
+      __hip_atomic_store(&box->ans, (uint64_t)want | ((uint64_t)res << 32), __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_SYSTEM);
+    seq += 1;
+    t0 = wall_clock64();
+    done = want;
+    // (lane 0's table writes before the next request's lanes read them)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    wave_lds_sync();  // (lane 0's reads of fr before the next request's writes)
+    return 0;
+  };
+  // After an answer the next request cannot come before the answer has
+  // crossed to the host and the host's loop has turned round: the first poll
+  // after an answer waits `after` wall-clock ticks so that it reads about when
+  // the request lands, and the delay adapts -- a request the first poll caught
+  // takes a tick off it, one that needed a later poll adds `up` (nat_serve).
+  uint32_t after = (flags >> 10) & 0xFFu;
+  const uint32_t up = (flags >> 19) & 0x1Fu;
+  const bool adapt = (flags >> 18) & 1u;
+  uint32_t polls = 0;  // polls since the last answer
+  for (;;) {
+    const v4u q = __builtin_amdgcn_raw_buffer_load_b128(ms, moff, 0, kSys);
+    const int st = serve(q);
+    if (st == 1) break;
+    polls++;
+    if (st < 0) {
+      if (wall_clock64() - t0 > idle) break;
+      __builtin_amdgcn_s_sleep(1);
+      continue;
+    }
+    if (adapt && polls == 1 && after > 0) after--;
+    if (adapt && polls > 1 && polls < 64) after = min(after + up, 200u);
+    polls = 0;
+    if (after) {
+      const uint64_t w = wall_clock64();
+      while (wall_clock64() - w < after) __builtin_amdgcn_s_sleep(1);
+    }
+  }
+}
+
 // =============================================================== host ==
 
 // fw_flowmanager.c:66-73: FlowManager.expiration_time is a vigor_time_t, so
@@ -496,6 +873,138 @@ static int fw_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
 int fw_process_device(vp_ctx *c, const vp_dev_batch *b) {
   ExpiringTable tabs[1] = {{&c->ft, fw_cutoff}};
   return run_batch(c, b, tabs, 1, fw_segment);
+}
+
+// ---------------------------------------------------- vp_process_one --
+// vigfw's launcher of the resident kernel (serve_launch, vp_serve.hip).
+int fw_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
+  FwArgs a{};
+  a.t = tbl_dev(c->ft);
+  a.crc_tab = c->crc_tab;
+  a.macw = c->macw;
+  a.wan = c->fw.wan_device;
+  a.n_dev = c->fw.n_devices;
+  fw_serve<<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags);
+  VP_HIP(hipGetLastError());
+  return 0;
+}
+
+int fw_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, int64_t now,
+                   uint16_t *out) {
+  std::lock_guard<std::recursive_mutex> sg(c->srv_mu);
+  FlowTable &t = c->ft;
+  // no expiry due at this packet (run_batch's test for a segment of one)
+  const bool ok = !serve_off() && !c->comm && len <= kServeFrame && now >= 0 &&
+                  now >= c->last_now &&
+                  fw_cutoff(c, now) <= (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)now);
+  if (!ok) {
+    VP_TRY(serve_stop(c));
+    return 1;
+  }
+  VP_TRY(serve_ready(c));
+  ServeBox *bx = c->sbox;
+  // the request chunks (ServeBox): payload words first, then each chunk's
+  // tag; chunk 0 last. The frame's first kServeInline bytes are all vigfw
+  // reads (fw_serve), whatever len is.
+  const uint32_t req = ++c->srv_req;
+  const uint32_t got = std::min<uint32_t>(len, kServeInline);
+  uint32_t m[3 * kServeChunks] = {};
+  m[0] = len | ((uint32_t)in_dev << 16);
+  m[1] = (uint32_t)(uint64_t)now;
+  m[2] = (uint32_t)((uint64_t)now >> 32);
+  memcpy(&m[3], frame, got);
+  const uint32_t need = (12 + got + 11) / 12;
+  for (uint32_t k = need; k-- > 0;) {
+    bx->msg[k][0] = m[3 * k];
+    bx->msg[k][1] = m[3 * k + 1];
+    bx->msg[k][2] = m[3 * k + 2];
+    __atomic_store_n(&bx->msg[k][3], req, __ATOMIC_RELEASE);
+  }
+  // the answer: chunk 0, and chunk 1 = frame bytes 0-11 (only the MACs change)
+  const uint32_t nans = std::min(need, 2u);
+  VP_TRY(serve_wait(c, req, nans));
+  const uint32_t res = bx->amsg[0][0];
+  if (nans > 1) {
+    const uint32_t mac[3] = {bx->amsg[1][0], bx->amsg[1][1], bx->amsg[1][2]};
+    memcpy(frame, mac, std::min<uint32_t>(len, 12));
+  }
+  *out = (uint16_t)res;
+  if ((res >> 16) & 1u) t.ts_floor = std::min<uint64_t>(t.ts_floor, (uint64_t)now);
+  c->seq += 1;
+  c->last_now = now;
+  c->srv_stats.packets_one += 1;
+  return 0;
+}
+
+// The largest host batch routed to the server as burst requests: the largest
+// swept n at which the served path measured faster per packet than the batch
+// pipeline on the MI355X (profiles/r08_fw_serve.txt: 0.19 against 0.25 us at
+// 256, a tie at 384, 0.19 against 0.14 at 512); larger calls take the
+// pipeline. The same value as vignat's kServeBurstRoute (vp_nat.hip), from
+// vigfw's own sweep. VIGPATH_SERVE_BURST overrides it; 0 routes nothing.
+constexpr uint32_t kFwBurstRoute = 256;
+
+int fw_process_burst(vp_ctx *c, const vp_mbuf_batch *b, uint32_t first, uint32_t count,
+                     uint32_t *served) {
+  *served = 0;
+  std::lock_guard<std::recursive_mutex> sg(c->srv_mu);
+  const uint32_t limit = serve_burst_limit(kFwBurstRoute);
+  if (serve_off() || c->comm || count == 0 || count > limit) return 1;
+  FlowTable &t = c->ft;
+  auto at = [&](uint32_t i) {
+    return b->now ? b->now[first + i] : b->now0 + (int64_t)(first + i) * b->now_step;
+  };
+  // the whole range or none of it: frames the mailbox holds, times that do
+  // not go back, and no expiry due anywhere in it -- the cutoff is monotone in
+  // time and flows born in the range are stamped >= its first time, so the
+  // last packet's cutoff against the floor as the range finds it decides
+  const int64_t n0 = at(0), n1 = at(count - 1);
+  if (n0 < 0 || n0 < c->last_now) return 1;
+  int64_t prev = n0;
+  for (uint32_t i = 0; i < count; i++) {
+    const int64_t ti = at(i);
+    if (b->len[first + i] > kServeFrame || ti < prev) return 1;
+    prev = ti;
+  }
+  if (fw_cutoff(c, n1) > (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)n0)) return 1;
+  VP_TRY(serve_ready(c));
+  ServeBox *bx = c->sbox;
+  for (uint32_t a0 = 0; a0 < count; a0 += kServeBurst) {
+    const uint32_t m = std::min(kServeBurst, count - a0);
+    // the body first (a frame's first 64 bytes are all fw_burst reads), then
+    // the tagged chunk that announces it (ServeBox)
+    for (uint32_t i = 0; i < m; i++) {
+      const uint32_t p = first + a0 + i;
+      if (b->len[p]) memcpy(bx->bframe[i], b->frames[p], std::min<uint32_t>(b->len[p], 64));
+      bx->bmeta[i] = b->len[p] | ((uint32_t)b->in_dev[p] << 16);
+      bx->bnow[i] = at(a0 + i);
+    }
+    const uint32_t req = ++c->srv_req;
+    bx->msg[0][0] = kServeBurstOp | (m << 16);
+    bx->msg[0][1] = 0;
+    bx->msg[0][2] = 0;
+    __atomic_store_n(&bx->msg[0][3], req, __ATOMIC_RELEASE);
+    VP_TRY(serve_wait(c, req, 1));
+    if (bx->amsg[0][0] != kBurstServed) {  // a byte-path frame: nothing of it was done
+      c->srv_stats.declined += 1;
+      return 1;
+    }
+    bool fresh = false;
+    for (uint32_t i = 0; i < m; i++) {
+      const uint32_t p = first + a0 + i, r = bx->bout[i];
+      b->out_dev[p] = (uint16_t)r;
+      fresh |= (r >> 16) & 1u;
+      // (only the MACs change: the frame's first 16-byte chunk comes back)
+      if ((r >> 17) & 1u) memcpy(b->frames[p], bx->bframe[i], std::min<uint32_t>(b->len[p], 16));
+    }
+    if (fresh) t.ts_floor = std::min<uint64_t>(t.ts_floor, (uint64_t)at(a0));
+    c->seq += m;
+    c->last_now = at(a0 + m - 1);
+    c->srv_stats.bursts += 1;
+    c->srv_stats.burst_packets += m;
+    *served += m;
+  }
+  return 0;
 }
 
 // State by flow index: alloc, ts, FlowId bytes (vigfw/flow.h layout, padding

@@ -344,7 +344,8 @@ struct HostMap {
 };
 constexpr int kMaxHostMaps = 16;
 
-// vp_process_one's mailbox (vp_nat.hip nat_serve): page-locked, host-coherent
+// vp_process_one's mailbox (nat_serve, vp_nat.hip; fw_serve, vp_fw.hip; its
+// host side in vp_serve.hip): page-locked, host-coherent
 // memory the host and a persistent one-wave kernel poll. The host writes the
 // request (below); the kernel writes the rewritten frame to `frame`, then
 // sets the answer word.
@@ -391,11 +392,14 @@ constexpr uint32_t kServeBurst = 64;       // frames per burst request
 constexpr uint32_t kServeBurstOp = 0xFFFFu;  // message word 0, low half: a burst
 constexpr uint32_t kBurstServed = 0, kBurstDeclined = 1;  // answer chunk 0, word 0
 static_assert(sizeof(((ServeBox *)nullptr)->bframe) == kServeBurst * kServeFrame, "burst slots");
-// One packet through the persistent kernel (vignat, one GPU, no expiry due):
-// 0 done; 1 not eligible (the caller takes the batch path, the server is
-// stopped); < 0 an error.
+// One packet through the persistent kernel (vignat or vigfw, one GPU, no
+// expiry due): 0 done; 1 not eligible (the caller takes the batch path, the
+// server is stopped); < 0 an error. vigfw sends at most kServeInline bytes of
+// the frame (it reads nothing past byte 78) and takes back the first 12.
 int nat_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, int64_t now,
                     uint16_t *out);
+int fw_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, int64_t now,
+                   uint16_t *out);
 // Packets [first, first + count) of a host batch through the same kernel as
 // burst requests of up to kServeBurst frames (vignat, one GPU, no expiry due
 // anywhere in the range, count within the routing limit): 0 all done; 1
@@ -404,10 +408,30 @@ int nat_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, in
 // (a later request declined: the caller runs the rest through the pipeline).
 int nat_process_burst(vp_ctx *c, const vp_mbuf_batch *b, uint32_t first, uint32_t count,
                       uint32_t *served);
-// Stop the context's persistent kernel, if it runs (every other entry point
-// calls this first: the kernel owns the table while it runs).
+// The same for vigfw (only the first 64 bytes of a frame go, 16 come back).
+int fw_process_burst(vp_ctx *c, const vp_mbuf_batch *b, uint32_t first, uint32_t count,
+                     uint32_t *served);
+// The mailbox's host side, for any served NF (vp_serve.hip). Stop the
+// context's persistent kernel, if it runs (every other entry point calls this
+// first: the kernel owns the table while it runs).
 int serve_stop(vp_ctx *c);
 void serve_free(vp_ctx *c);
+// The mailbox exists and the kernel runs; wait for request `req`'s answer
+// chunks 0 .. need - 1 (the kernel launched again if it left idle before it
+// saw the request). The caller holds c->srv_mu.
+int serve_ready(vp_ctx *c);
+int serve_wait(vp_ctx *c, uint32_t req, uint32_t need);
+bool serve_off();   // VIGPATH_SERVE=0
+bool serve_prof();  // VIGPATH_SERVE_PROF (vignat's stage clock)
+// The largest host batch routed as burst requests: VIGPATH_SERVE_BURST, else
+// the NF's own limit `dflt`.
+uint32_t serve_burst_limit(uint32_t dflt);
+// The NFs' launchers of their resident kernel on c->stream (serve_launch
+// dispatches on c->kind). flags: the kernel's polling parameters -- bits
+// 10-17 the first poll's delay after an answer, bit 18 adapt it, bits 19-23
+// the ticks a late poll adds (nat_serve's comment).
+int nat_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
+int fw_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
 
 }  // namespace vp
 
@@ -489,7 +513,7 @@ struct vp_ctx {
   // during vp_process_mbufs: tail sums of the 64-byte header slots the
   // current device batch holds (vp_nat.hip NatArgs::tail), else null
   const uint32_t *hdr_tail = nullptr;
-  // vp_process_one (vp_nat.hip): the mailbox, whether nat_serve runs on
+  // vp_process_one (vp_serve.hip): the mailbox, whether the NF's server runs on
   // `stream`, the last request number, and its idle exit (wall-clock ticks)
   vp::ServeBox *sbox = nullptr;
   bool srv_on = false;
