@@ -28,6 +28,7 @@
 #include <mutex>
 #include <vector>
 
+#include "vp_serve_dev.h"
 #include "vp_table.h"
 
 namespace vp {
@@ -384,8 +385,8 @@ __global__ void fw_defer_finish(FwArgs a, const uint32_t *list, uint32_t n) {
 // small vp_process_mbufs calls instead go to fw_serve, one wave that stays
 // resident and polls the host-coherent mailbox (ServeBox, vp_internal.h), as
 // nat_serve does for vignat: no launch and no copy call per packet. The host
-// sends requests only while no expiry is due (fw_process_one /
-// fw_process_burst), so the kernel restates fw_main.c:21-80 without the
+// sends requests only while no expiry is due (serve_process_one /
+// serve_process_burst), so the kernel restates fw_main.c:21-80 without the
 // expiry step.
 
 // The FlowId a packet looks up (fw_key) and its hash from the LDS tables.
@@ -401,45 +402,13 @@ __device__ __forceinline__ uint32_t fw_key_hash(const uint32_t *T, bool wan, uin
 
 // flow_manager_allocate_or_refresh_flow (fw_flowmanager.c:38-62) for one LAN
 // FlowId from device `in` at global sequence seq: the flow's index, allocated
-// when new (*fresh = 1; dchain_allocate_new_index: the freed stack first, then
-// the never-used range); kNone with nothing stored when no index is free.
+// when new (serve_lan; int_devices in the key's padding bytes, as
+// fw_miss_finish stores it), or kNone when no index is free
+// (fw_flowmanager.c:47-51).
 __device__ __forceinline__ uint32_t fw_one_lan(const TableDev &t, uint32_t hh,
                                                const uint32_t key[4], uint32_t in, uint64_t seq,
                                                uint32_t *fresh) {
-  uint32_t idx = tbl_probe<0xFFu>(t, hh, key);
-  if (idx != kNone) return idx;
-  Ctl *c = t.ctl;
-  const uint32_t st = c->stack_top, fn = c->fresh_next;
-  if (st) {
-    idx = t.stack[st - 1];
-    c->stack_top = st - 1;
-  } else if (fn < t.cap) {
-    idx = fn;
-    c->fresh_next = fn + 1;
-  } else {
-    return kNone;  // fw_flowmanager.c:47-51
-  }
-  // (int_devices in the key's padding bytes, as fw_miss_finish stores it)
-  const uint32_t k[4] = {key[0], key[1], key[2], key[3] | (in << 8)};
-  bool tomb = false;
-  uint32_t disp = 0;
-  const uint32_t e = tbl_insert(t, hh, k, idx, &tomb, &disp);
-  if (tomb) c->n_tomb -= 1;
-  c->n_live += 1;
-  c->sh_live += 1;
-  c->disp_count += disp;
-  t.slot_of[idx] = e;
-  t.hash_of[idx] = hh;
-  t.birth[idx] = seq;
-  *fresh = 1;
-  return idx;
-}
-
-// The touch of index idx at (now, seq), right behind the lookup.
-__device__ __forceinline__ void fw_stamp(const TableDev &t, uint32_t idx, int64_t now,
-                                         uint64_t seq) {
-  t.ts[idx] = (uint64_t)now;
-  t.tseq[idx] = seq;
+  return serve_lan<0xFFu>(t, hh, key, key[3] | (in << 8), seq, fresh);
 }
 
 // fw_main.c:44-72 for one TCP/UDP packet: the device it goes out on, or kNone
@@ -461,105 +430,32 @@ __device__ __forceinline__ uint32_t fw_one_flow(const FwArgs &a, const uint32_t 
   } else {
     idx = fw_one_lan(a.t, hh, key, in, seq, fresh);
   }
-  if (idx != kNone) fw_stamp(a.t, idx, now, seq);
+  if (idx != kNone) serve_stamp(a.t, idx, now, seq);
   return dst;
 }
 
-// A burst request (ServeBox): n frames as nf_process would take them one after
-// another, lane i = packet i at sequence seq0 + i; the whole wave calls it.
-// No flow leaves during a burst (the host sends one only while no expiry is
-// due anywhere in it), so a lookup that hits is final and only the misses
-// depend on the packets before them: they settle in packet order, one new LAN
-// flow per round (serve_burst, vp_nat.hip, is vignat's form of the same
-// loop). Only the first 64 bytes of a frame are read and only its first 16
-// can change. Returns kBurstServed, or kBurstDeclined -- before any table
-// write -- when a frame has IPv4 options (the byte-addressed path's).
+// A burst request (vp_serve_dev.h) for vigfw: a WAN lane that looks again
+// probes the table. Only the first 64 bytes of a frame are read and only its
+// first 16 can change.
 __device__ __forceinline__ uint32_t fw_burst(const FwArgs &a, const uint32_t *T, ServeBox *box,
                                              uint32_t n, uint64_t seq0, uint32_t lane) {
-  typedef unsigned v4u __attribute__((ext_vector_type(4)));
-  typedef unsigned v2u __attribute__((ext_vector_type(2)));
-  constexpr int kSys = 17;  // sc0 | sc1: system-coherent (bypasses the GPU caches)
-  constexpr uint32_t kBody = kServeBurst * kServeFrame;
   const TableDev &t = a.t;
-  const auto fs = __builtin_amdgcn_make_buffer_rsrc(box->bframe, 0, (int)kBody, 0x00020000);
-  const auto ns = __builtin_amdgcn_make_buffer_rsrc(box->bnow, 0, 8 * kServeBurst, 0x00020000);
-  const auto es = __builtin_amdgcn_make_buffer_rsrc(box->bmeta, 0, 4 * kServeBurst, 0x00020000);
-  const auto os = __builtin_amdgcn_make_buffer_rsrc(box->bout, 0, 4 * kServeBurst, 0x00020000);
-  const bool act = lane < n;
-  // (lanes past the burst read zeros and store nothing: offsets past the resources)
-  const uint32_t slot0 = act ? lane * kServeFrame : kBody;
-  v4u q[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++)
-    q[j] = __builtin_amdgcn_raw_buffer_load_b128(fs, (int)(slot0 + 16 * j), 0, kSys);
-  const uint32_t meta =
-      __builtin_amdgcn_raw_buffer_load_b32(es, act ? (int)(4 * lane) : (int)(4 * kServeBurst), 0, kSys);
-  const v2u nw =
-      __builtin_amdgcn_raw_buffer_load_b64(ns, act ? (int)(8 * lane) : (int)(8 * kServeBurst), 0, kSys);
-  const uint32_t len = min(meta & 0xFFFFu, kServeFrame), in = meta >> 16;
-  const int64_t now = (int64_t)((uint64_t)nw[0] | ((uint64_t)nw[1] << 32));
-  RFrame f;  // the first 64 bytes; bytes past len read as 0
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const uint4 v = chunk_keep(make_uint4(q[j][0], q[j][1], q[j][2], q[j][3]), 0, (int)len - 16 * j);
-    f.w[4 * j] = v.x;
-    f.w[4 * j + 1] = v.y;
-    f.w[4 * j + 2] = v.z;
-    f.w[4 * j + 3] = v.w;
-  }
-  // fw_issue's tests (fw_main.c:26-40); a frame parse_l34 would follow past a
-  // longer IPv4 header is the byte-addressed path's
-  const uint32_t et = f.w[3] & 0xFFFF, ihl = (f.w[3] >> 16) & 0x0F;
-  const uint32_t tl = bswap16((uint16_t)(f.w[4] & 0xFFFF));
-  const uint16_t unread = (uint16_t)(len - 14);
-  const uint32_t proto = f.w[5] >> 24;
-  const bool ip = act && et == 0x0008 && unread >= 20 && unread >= tl;
-  if (__ballot(ip && ihl > 5)) return kBurstDeclined;
-  const bool go =
-      ip && ihl == 5 && ((proto == 6) | (proto == 17)) && (uint32_t)(len - 34) >= 4u;
-  const uint32_t sp = f.w[8] >> 16, dp = f.w[9] & 0xFFFF;
-  const uint32_t sip = f.u32at2(26), dip = f.u32at2(30);
+  const BurstIn b = burst_load(box, n, lane);
+  const BurstHdr h = burst_hdr(b);  // fw_issue's tests (fw_main.c:26-40)
+  if (h.decline) return kBurstDeclined;
+  const uint32_t in = b.in;
   const bool wan = in == a.wan;
-  const bool lanp = go && !wan, wanp = go && wan;
+  const bool lanp = h.go && !wan, wanp = h.go && wan;
   uint32_t key[4];
-  const uint32_t hh = fw_key_hash(T, wan, sp, dp, sip, dip, proto, key);
-  // round 0: every lane looks its flow up in the table as the burst found it
+  const uint32_t hh = fw_key_hash(T, wan, h.sp, h.dp, h.sip, h.dip, h.proto, key);
+  // round 0, then the misses in packet order
   uint32_t idx = kNone, fresh = 0, w3 = 0;
-  if (go) idx = tbl_probe<0xFFu>(t, hh, key, &w3);
-  bool lpend = lanp && idx == kNone, wpend = wanp && idx == kNone;
-  // the misses in packet order: the lowest pending LAN lane m looks again (an
-  // earlier lane of this burst may have inserted its FlowId) and allocates as
-  // a packet of its own would (fw_one_lan: kNone when no index is free, and
-  // nothing is written); a pending WAN lane below m has every flow born
-  // before it in the table and is final, hit or drop. At most one round per
-  // lane.
-  for (uint32_t r = 0; r < kServeBurst; r++) {
-    const uint64_t lp = __ballot(lpend);
-    if (!lp) break;
-    const uint32_t m = (uint32_t)__ffsll((unsigned long long)lp) - 1;
-    if (wpend && lane < m) {
-      idx = tbl_probe<0xFFu>(t, hh, key, &w3);
-      wpend = false;
-    }
-    if (lane == m) {
-      idx = fw_one_lan(t, hh, key, in, seq0 + lane, &fresh);
-      lpend = false;
-    }
-    // (lane m's insert before the later lanes' lookups: one wave, workgroup
-    // scope; an agent-scope release would write the XCD's L2 back)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  }
-  if (wpend) idx = tbl_probe<0xFFu>(t, hh, key, &w3);  // (no LAN miss before them is left)
-  // Stamps: for every index the burst's last packet that touched it must win.
-  // The highest lane holding an index stores both words, the others store
-  // nothing (no order between lanes' stores is relied on).
-  bool last = idx != kNone;
-  for (uint32_t j = 1; j < n; j++) {
-    const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)idx, (int)j);
-    if (j > lane && o == idx) last = false;
-  }
-  if (last) fw_stamp(t, idx, now, seq0 + lane);
+  if (h.go) idx = tbl_probe<0xFFu>(t, hh, key, &w3);
+  burst_settle(
+      lane, lanp && idx == kNone, wanp && idx == kNone,
+      [&] { idx = tbl_probe<0xFFu>(t, hh, key, &w3); },
+      [&] { idx = fw_one_lan(t, hh, key, in, seq0 + lane, &fresh); });
+  if (burst_last(idx, n, lane)) serve_stamp(t, idx, b.now, seq0 + lane);
   // the rewrite: a LAN packet goes out on the WAN device with or without a
   // flow (fw_flowmanager.c:49-53), a WAN packet to its flow's internal device
   uint32_t out = in, rew = 0;
@@ -568,20 +464,11 @@ __device__ __forceinline__ uint32_t fw_burst(const FwArgs &a, const uint32_t *T,
     uint32_t mw[3];
     fw_macs(a, out, mw);
     // back: the frame's first 16 bytes (the MACs are bytes 0-11)
-    __builtin_amdgcn_raw_buffer_store_b128((v4u){mw[0], mw[1], mw[2], f.w[3]}, fs, (int)slot0, 0,
-                                           kSys);
+    __builtin_amdgcn_raw_buffer_store_b128((v4u){mw[0], mw[1], mw[2], b.f.w[3]}, b.fs,
+                                           (int)b.slot0, 0, kSys);
     rew = 1;
   }
-  // the out words, four lanes' in one store
-  const uint32_t res = (out & 0xFFFFu) | (fresh << 16) | (rew << 17);
-  v4u o4;
-#pragma unroll
-  for (int k = 0; k < 4; k++) o4[k] = (uint32_t)__shfl((int)res, (int)((4 * lane + k) & 63));
-  if (4 * lane < n) __builtin_amdgcn_raw_buffer_store_b128(o4, os, (int)(16 * lane), 0, kSys);
-  // (all of it complete before the answer chunk that announces it)
-  __atomic_signal_fence(__ATOMIC_SEQ_CST);
-  __builtin_amdgcn_s_waitcnt(0);
-  __atomic_signal_fence(__ATOMIC_SEQ_CST);
+  burst_out(b, (out & 0xFFFFu) | (fresh << 16) | (rew << 17), n, lane);
   return kBurstServed;
 }
 
@@ -595,9 +482,7 @@ __device__ __forceinline__ uint32_t fw_burst(const FwArgs &a, const uint32_t *T,
 // store instruction. Packets take global sequence numbers seq0, seq0 + 1, ...;
 // a burst request (fw_burst) takes as many as it has frames. The kernel
 // leaves on the leave request or after `idle` wall-clock ticks without a
-// request; the host launches it again (serve_wait). flags as nat_serve's:
-// bits 10-17 the first poll's delay after an answer, bit 18 adapt it, bits
-// 19-23 the ticks a late poll adds.
+// request; the host launches it again (serve_wait). flags: serve_poll's.
 __global__ __launch_bounds__(64) void fw_serve(FwArgs a, ServeBox *box, uint64_t seq0,
                                                uint64_t idle, uint32_t flags) {
   __shared__ uint32_t T[kFwTabWords];
@@ -605,12 +490,7 @@ __global__ __launch_bounds__(64) void fw_serve(FwArgs a, ServeBox *box, uint64_t
   const uint32_t lane = threadIdx.x;
   fw_load_tables(T, a);
   if (a.t.mix == kMixLin) a.t.lin = fw_lin(T);  // (the layout's byte tables: their LDS copy)
-  typedef unsigned v4u __attribute__((ext_vector_type(4)));
-  constexpr int kSys = 17;  // sc0 | sc1: system-coherent (bypasses the GPU caches)
-  const auto ms = __builtin_amdgcn_make_buffer_rsrc(box->msg, 0, 16 * kServeChunks, 0x00020000);
-  const auto as = __builtin_amdgcn_make_buffer_rsrc(box->amsg, 0, 16 * kServeChunks, 0x00020000);
-  // (lanes past the chunks read nothing: an offset past the resource)
-  const int moff = lane < kServeChunks ? (int)(16 * lane) : (int)(16 * kServeChunks);
+  const ServeIo io = serve_io(box, lane);
   uint32_t *fword = reinterpret_cast<uint32_t *>(fr);
   // the last answered request (a relaunched server goes on from the answer
   // word), the next packet's sequence, the last answer's wall clock
@@ -618,8 +498,6 @@ __global__ __launch_bounds__(64) void fw_serve(FwArgs a, ServeBox *box, uint64_t
       &box->ans, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM));
   uint64_t seq = seq0;
   uint64_t t0 = wall_clock64();
-  // one poll's chunks: -1 nothing new (or not yet whole), 0 a request served,
-  // 1 leave
   auto serve = [&](const v4u &c) -> int {
     const uint32_t want = done + 1;
     if (__builtin_amdgcn_readfirstlane(c[3]) != want) return -1;
@@ -629,10 +507,7 @@ __global__ __launch_bounds__(64) void fw_serve(FwArgs a, ServeBox *box, uint64_t
     if ((hi & 0xFFFFu) == kServeBurstOp) {  // chunk 0 alone, the frames in the burst body
       const uint32_t bn = min(max(in, 1u), kServeBurst);
       const uint32_t st = fw_burst(a, T, box, bn, seq, lane);
-      if (lane == 0) {
-        __builtin_amdgcn_raw_buffer_store_b128((v4u){st, bn, 0u, want}, as, 0, 0, kSys);
-        __hip_atomic_store(&box->ans, (uint64_t)want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
+      if (lane == 0) burst_answer(io, box, st, bn, want);
       if (st == kBurstServed) seq += bn;
       t0 = wall_clock64();
       done = want;
@@ -645,25 +520,12 @@ __global__ __launch_bounds__(64) void fw_serve(FwArgs a, ServeBox *box, uint64_t
     const uint32_t got = min(len, kServeInline);    // frame bytes in the chunks
     const uint32_t need = (12 + got + 11) / 12;      // chunks carrying the request
     if (__ballot(lane < need && c[3] != want)) return -1;  // not whole yet: poll again
-    const int64_t now = (int64_t)((uint64_t)__builtin_amdgcn_readfirstlane(c[1]) |
-                                  ((uint64_t)__builtin_amdgcn_readfirstlane(c[2]) << 32));
-    if (lane >= 1 && lane < need) {  // chunk k >= 1: frame bytes 12k - 12 .. 12k - 1
-      fword[3 * lane - 3] = c[0];
-      fword[3 * lane - 2] = c[1];
-      fword[3 * lane - 1] = c[2];
-    }
+    const int64_t now = serve_now(c);
+    serve_chunks_in(fword, c, lane, need);
     wave_lds_sync();
     uint32_t res = 0, m0 = 0, m1 = 0, m2 = 0;
     if (lane == 0) {
-      RFrame f;  // the first 64 bytes; bytes past len read as 0
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const uint4 v = chunk_keep(fr[j], 0, (int)len - 16 * j);
-        f.w[4 * j] = v.x;
-        f.w[4 * j + 1] = v.y;
-        f.w[4 * j + 2] = v.z;
-        f.w[4 * j + 3] = v.w;
-      }
+      const RFrame f = serve_rframe([&](int j) { return fr[j]; }, len);
       const uint32_t et = f.w[3] & 0xFFFF, ihl = (f.w[3] >> 16) & 0x0F;
       uint32_t sp = 0, dp = 0, sip = 0, dip = 0, proto = 0;
       bool ok;
@@ -706,7 +568,7 @@ __global__ __launch_bounds__(64) void fw_serve(FwArgs a, ServeBox *box, uint64_t
     // the answer chunks: the result and frame bytes 0-11, one store
     if (lane < min(need, 2u)) {
       const v4u v = lane == 0 ? (v4u){res, 0u, 0u, want} : (v4u){m0, m1, m2, want};
-      __builtin_amdgcn_raw_buffer_store_b128(v, as, (int)(16 * lane), 0, kSys);
+      __builtin_amdgcn_raw_buffer_store_b128(v, io.as, (int)(16 * lane), 0, kSys);
     }
     // (the answer word: where a relaunched server starts counting; the host
     // reads the answer chunks. No release fence at system scope, which would
@@ -723,33 +585,7 @@ __global__ __launch_bounds__(64) void fw_serve(FwArgs a, ServeBox *box, uint64_t
     wave_lds_sync();  // (lane 0's reads of fr before the next request's writes)
     return 0;
   };
-  // After an answer the next request cannot come before the answer has
-  // crossed to the host and the host's loop has turned round: the first poll
-  // after an answer waits `after` wall-clock ticks so that it reads about when
-  // the request lands, and the delay adapts -- a request the first poll caught
-  // takes a tick off it, one that needed a later poll adds `up` (nat_serve).
-  uint32_t after = (flags >> 10) & 0xFFu;
-  const uint32_t up = (flags >> 19) & 0x1Fu;
-  const bool adapt = (flags >> 18) & 1u;
-  uint32_t polls = 0;  // polls since the last answer
-  for (;;) {
-    const v4u q = __builtin_amdgcn_raw_buffer_load_b128(ms, moff, 0, kSys);
-    const int st = serve(q);
-    if (st == 1) break;
-    polls++;
-    if (st < 0) {
-      if (wall_clock64() - t0 > idle) break;
-      __builtin_amdgcn_s_sleep(1);
-      continue;
-    }
-    if (adapt && polls == 1 && after > 0) after--;
-    if (adapt && polls > 1 && polls < 64) after = min(after + up, 200u);
-    polls = 0;
-    if (after) {
-      const uint64_t w = wall_clock64();
-      while (wall_clock64() - w < after) __builtin_amdgcn_s_sleep(1);
-    }
-  }
+  serve_poll(io, flags, idle, serve, [&] { return t0; });
 }
 
 // =============================================================== host ==
@@ -889,53 +725,6 @@ int fw_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
   return 0;
 }
 
-int fw_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, int64_t now,
-                   uint16_t *out) {
-  std::lock_guard<std::recursive_mutex> sg(c->srv_mu);
-  FlowTable &t = c->ft;
-  // no expiry due at this packet (run_batch's test for a segment of one)
-  const bool ok = !serve_off() && !c->comm && len <= kServeFrame && now >= 0 &&
-                  now >= c->last_now &&
-                  fw_cutoff(c, now) <= (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)now);
-  if (!ok) {
-    VP_TRY(serve_stop(c));
-    return 1;
-  }
-  VP_TRY(serve_ready(c));
-  ServeBox *bx = c->sbox;
-  // the request chunks (ServeBox): payload words first, then each chunk's
-  // tag; chunk 0 last. The frame's first kServeInline bytes are all vigfw
-  // reads (fw_serve), whatever len is.
-  const uint32_t req = ++c->srv_req;
-  const uint32_t got = std::min<uint32_t>(len, kServeInline);
-  uint32_t m[3 * kServeChunks] = {};
-  m[0] = len | ((uint32_t)in_dev << 16);
-  m[1] = (uint32_t)(uint64_t)now;
-  m[2] = (uint32_t)((uint64_t)now >> 32);
-  memcpy(&m[3], frame, got);
-  const uint32_t need = (12 + got + 11) / 12;
-  for (uint32_t k = need; k-- > 0;) {
-    bx->msg[k][0] = m[3 * k];
-    bx->msg[k][1] = m[3 * k + 1];
-    bx->msg[k][2] = m[3 * k + 2];
-    __atomic_store_n(&bx->msg[k][3], req, __ATOMIC_RELEASE);
-  }
-  // the answer: chunk 0, and chunk 1 = frame bytes 0-11 (only the MACs change)
-  const uint32_t nans = std::min(need, 2u);
-  VP_TRY(serve_wait(c, req, nans));
-  const uint32_t res = bx->amsg[0][0];
-  if (nans > 1) {
-    const uint32_t mac[3] = {bx->amsg[1][0], bx->amsg[1][1], bx->amsg[1][2]};
-    memcpy(frame, mac, std::min<uint32_t>(len, 12));
-  }
-  *out = (uint16_t)res;
-  if ((res >> 16) & 1u) t.ts_floor = std::min<uint64_t>(t.ts_floor, (uint64_t)now);
-  c->seq += 1;
-  c->last_now = now;
-  c->srv_stats.packets_one += 1;
-  return 0;
-}
-
 // The largest host batch routed to the server as burst requests: the largest
 // swept n at which the served path measured faster per packet than the batch
 // pipeline on the MI355X (profiles/r08_fw_serve.txt: 0.19 against 0.25 us at
@@ -944,67 +733,14 @@ int fw_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, int
 // vigfw's own sweep. VIGPATH_SERVE_BURST overrides it; 0 routes nothing.
 constexpr uint32_t kFwBurstRoute = 256;
 
-int fw_process_burst(vp_ctx *c, const vp_mbuf_batch *b, uint32_t first, uint32_t count,
-                     uint32_t *served) {
-  *served = 0;
-  std::lock_guard<std::recursive_mutex> sg(c->srv_mu);
-  const uint32_t limit = serve_burst_limit(kFwBurstRoute);
-  if (serve_off() || c->comm || count == 0 || count > limit) return 1;
-  FlowTable &t = c->ft;
-  auto at = [&](uint32_t i) {
-    return b->now ? b->now[first + i] : b->now0 + (int64_t)(first + i) * b->now_step;
-  };
-  // the whole range or none of it: frames the mailbox holds, times that do
-  // not go back, and no expiry due anywhere in it -- the cutoff is monotone in
-  // time and flows born in the range are stamped >= its first time, so the
-  // last packet's cutoff against the floor as the range finds it decides
-  const int64_t n0 = at(0), n1 = at(count - 1);
-  if (n0 < 0 || n0 < c->last_now) return 1;
-  int64_t prev = n0;
-  for (uint32_t i = 0; i < count; i++) {
-    const int64_t ti = at(i);
-    if (b->len[first + i] > kServeFrame || ti < prev) return 1;
-    prev = ti;
-  }
-  if (fw_cutoff(c, n1) > (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)n0)) return 1;
-  VP_TRY(serve_ready(c));
-  ServeBox *bx = c->sbox;
-  for (uint32_t a0 = 0; a0 < count; a0 += kServeBurst) {
-    const uint32_t m = std::min(kServeBurst, count - a0);
-    // the body first (a frame's first 64 bytes are all fw_burst reads), then
-    // the tagged chunk that announces it (ServeBox)
-    for (uint32_t i = 0; i < m; i++) {
-      const uint32_t p = first + a0 + i;
-      if (b->len[p]) memcpy(bx->bframe[i], b->frames[p], std::min<uint32_t>(b->len[p], 64));
-      bx->bmeta[i] = b->len[p] | ((uint32_t)b->in_dev[p] << 16);
-      bx->bnow[i] = at(a0 + i);
-    }
-    const uint32_t req = ++c->srv_req;
-    bx->msg[0][0] = kServeBurstOp | (m << 16);
-    bx->msg[0][1] = 0;
-    bx->msg[0][2] = 0;
-    __atomic_store_n(&bx->msg[0][3], req, __ATOMIC_RELEASE);
-    VP_TRY(serve_wait(c, req, 1));
-    if (bx->amsg[0][0] != kBurstServed) {  // a byte-path frame: nothing of it was done
-      c->srv_stats.declined += 1;
-      return 1;
-    }
-    bool fresh = false;
-    for (uint32_t i = 0; i < m; i++) {
-      const uint32_t p = first + a0 + i, r = bx->bout[i];
-      b->out_dev[p] = (uint16_t)r;
-      fresh |= (r >> 16) & 1u;
-      // (only the MACs change: the frame's first 16-byte chunk comes back)
-      if ((r >> 17) & 1u) memcpy(b->frames[p], bx->bframe[i], std::min<uint32_t>(b->len[p], 16));
-    }
-    if (fresh) t.ts_floor = std::min<uint64_t>(t.ts_floor, (uint64_t)at(a0));
-    c->seq += m;
-    c->last_now = at(a0 + m - 1);
-    c->srv_stats.bursts += 1;
-    c->srv_stats.burst_packets += m;
-    *served += m;
-  }
-  return 0;
+// vigfw through the mailbox (serve_process_one / serve_process_burst,
+// vp_serve.hip): fw_serve reads nothing past a frame's first kServeInline
+// bytes and only the MACs change, so one packet sends at most that much and
+// takes back bytes 0-11; fw_burst reads a frame's first 64 bytes and 16 come
+// back.
+const ServeNf &fw_serve_nf() {
+  static const ServeNf nf = {fw_cutoff, &vp_ctx::ft, false, 64, 16, kFwBurstRoute, false};
+  return nf;
 }
 
 // State by flow index: alloc, ts, FlowId bytes (vigfw/flow.h layout, padding

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <mutex>
 #include <tuple>
@@ -373,15 +374,15 @@ struct ServeBox {
   uint64_t ans;      // device: request number | (out | fresh << 16) << 32 (relaunch state)
   uint64_t prof[10];  // device: wall-clock stamps of the last request (VIGPATH_SERVE_PROF)
   alignas(16) uint8_t frame[kServeFrame];  // longer frames in; every result out
-  // A burst request (nat_process_burst): up to kServeBurst frames, one lane
+  // A burst request (serve_process_burst): up to kServeBurst frames, one lane
   // of the serving wave each. The host writes the body below first, then the
   // tagged chunk 0 alone, whose word 0 is kServeBurstOp | n << 16 (no frame is
   // 0xFFFF bytes long, and n <= kServeBurst keeps it apart from kServeLeave)
   // and whose words 1-2 are unused; the server reads the body only after it
   // has seen the tag (a second PCIe round trip, once per burst). The answer
-  // comes back the same way: the first 64 bytes of every rewritten frame and
-  // bout[] (system-coherent stores, waited for), then answer chunk 0 = {status,
-  // n, 0, request number}.
+  // comes back the same way: the first bytes of every rewritten frame (64 of
+  // vignat's, 16 of vigfw's) and bout[] (system-coherent stores, waited
+  // for), then answer chunk 0 = {status, n, 0, request number}.
   alignas(128) uint8_t bframe[64][kServeFrame];
   int64_t bnow[64];
   uint32_t bmeta[64];  // len | in_dev << 16, as a one-packet request's word 0
@@ -392,25 +393,73 @@ constexpr uint32_t kServeBurst = 64;       // frames per burst request
 constexpr uint32_t kServeBurstOp = 0xFFFFu;  // message word 0, low half: a burst
 constexpr uint32_t kBurstServed = 0, kBurstDeclined = 1;  // answer chunk 0, word 0
 static_assert(sizeof(((ServeBox *)nullptr)->bframe) == kServeBurst * kServeFrame, "burst slots");
-// One packet through the persistent kernel (vignat or vigfw, one GPU, no
-// expiry due): 0 done; 1 not eligible (the caller takes the batch path, the
-// server is stopped); < 0 an error. vigfw sends at most kServeInline bytes of
-// the frame (it reads nothing past byte 78) and takes back the first 12.
-int nat_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, int64_t now,
-                    uint16_t *out);
-int fw_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, int64_t now,
-                   uint16_t *out);
+// The request chunks of a message m (3 words per chunk, `need` chunks) as
+// request `req`: a chunk's payload words, then its tag with release; chunk 0,
+// which the server looks at first, last. A burst's announcement is chunk 0
+// alone, m[0] = kServeBurstOp | n << 16.
+inline void serve_post(ServeBox *bx, const uint32_t *m, uint32_t need, uint32_t req) {
+  for (uint32_t k = need; k-- > 0;) {
+    bx->msg[k][0] = m[3 * k];
+    bx->msg[k][1] = m[3 * k + 1];
+    bx->msg[k][2] = m[3 * k + 2];
+    __atomic_store_n(&bx->msg[k][3], req, __ATOMIC_RELEASE);
+  }
+}
+// A one-packet request's message: word 0, the time, then the frame's first
+// `got` <= kServeInline bytes. Returns the chunks it takes.
+inline uint32_t serve_pack(uint32_t m[3 * kServeChunks], uint32_t word0, int64_t now,
+                           const uint8_t *frame, uint32_t got) {
+  memset(m, 0, 12 * kServeChunks);
+  m[0] = word0;
+  m[1] = (uint32_t)(uint64_t)now;
+  m[2] = (uint32_t)((uint64_t)now >> 32);
+  memcpy(&m[3], frame, got);
+  return (12 + got + 11) / 12;
+}
+// The first `back` <= kServeInline frame bytes of the answer chunks (1 ..).
+inline void serve_unpack(const ServeBox *bx, uint8_t *frame, uint32_t back) {
+  uint32_t m[3 * kServeChunks];
+  for (uint32_t k = 1; k < (12 + back + 11) / 12; k++) {
+    m[3 * k] = bx->amsg[k][0];
+    m[3 * k + 1] = bx->amsg[k][1];
+    m[3 * k + 2] = bx->amsg[k][2];
+  }
+  memcpy(frame, &m[3], back);
+}
+
+// What of a served NF the mailbox's host side needs to know (nat_serve_nf,
+// vp_nat.hip; fw_serve_nf, vp_fw.hip).
+struct ServeNf {
+  // the table whose entries expire and the cutoff for a packet at time t: a
+  // request is sent only while no expiry is due
+  int64_t (*cutoff)(const vp_ctx *c, int64_t t);
+  FlowTable vp_ctx::*table;
+  // one packet: the whole frame goes and comes back, one longer than
+  // kServeInline through `frame`; else its first kServeInline bytes go and
+  // bytes 0-11 (answer chunk 1) come back
+  bool one_whole;
+  uint32_t burst_in, burst_back;  // a burst's frame: the most bytes in, and back
+  uint32_t burst_route;           // the largest host batch routed as burst requests
+  bool prof;                      // VIGPATH_SERVE_PROF's stage clock (nat_serve's)
+};
+const ServeNf &nat_serve_nf();
+const ServeNf &fw_serve_nf();
+inline const ServeNf *serve_nf(int kind) {  // (nullptr: the NF has no resident kernel)
+  return kind == KIND_NAT ? &nat_serve_nf() : kind == KIND_FW ? &fw_serve_nf() : nullptr;
+}
+// One packet through the persistent kernel (one GPU, no expiry due): 0 done;
+// 1 not eligible (the caller takes the batch path, the server is stopped);
+// < 0 an error.
+int serve_process_one(vp_ctx *c, const ServeNf &nf, uint16_t in_dev, uint8_t *frame,
+                      uint16_t len, int64_t now, uint16_t *out);
 // Packets [first, first + count) of a host batch through the same kernel as
-// burst requests of up to kServeBurst frames (vignat, one GPU, no expiry due
-// anywhere in the range, count within the routing limit): 0 all done; 1
-// nothing of it done (not routed, or the kernel declined the first request:
-// the caller runs today's pipeline); < 0 an error. *served = the packets done
-// (a later request declined: the caller runs the rest through the pipeline).
-int nat_process_burst(vp_ctx *c, const vp_mbuf_batch *b, uint32_t first, uint32_t count,
-                      uint32_t *served);
-// The same for vigfw (only the first 64 bytes of a frame go, 16 come back).
-int fw_process_burst(vp_ctx *c, const vp_mbuf_batch *b, uint32_t first, uint32_t count,
-                     uint32_t *served);
+// burst requests of up to kServeBurst frames (one GPU, no expiry due anywhere
+// in the range, count within the routing limit): 0 all done; 1 nothing of it
+// done (not routed, or the kernel declined the first request: the caller runs
+// the batch pipeline); < 0 an error. *served = the packets done (a later
+// request declined: the caller runs the rest through the pipeline).
+int serve_process_burst(vp_ctx *c, const ServeNf &nf, const vp_mbuf_batch *b, uint32_t first,
+                        uint32_t count, uint32_t *served);
 // The mailbox's host side, for any served NF (vp_serve.hip). Stop the
 // context's persistent kernel, if it runs (every other entry point calls this
 // first: the kernel owns the table while it runs).
@@ -429,7 +478,7 @@ uint32_t serve_burst_limit(uint32_t dflt);
 // The NFs' launchers of their resident kernel on c->stream (serve_launch
 // dispatches on c->kind). flags: the kernel's polling parameters -- bits
 // 10-17 the first poll's delay after an answer, bit 18 adapt it, bits 19-23
-// the ticks a late poll adds (nat_serve's comment).
+// the ticks a late poll adds (serve_poll, vp_serve_dev.h).
 int nat_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
 int fw_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
 
@@ -519,7 +568,7 @@ struct vp_ctx {
   bool srv_on = false;
   uint32_t srv_req = 0;
   uint64_t srv_idle = 0, srv_idle_ms = 1;
-  // held by the thread serving (nat_process_one, serve_stop); another
+  // held by the thread serving (serve_process_one, serve_stop); another
   // context's server launch on the same GPU stops this one only if it can
   // take it (serve_launch: resident kernels share the hardware queues)
   std::recursive_mutex srv_mu;

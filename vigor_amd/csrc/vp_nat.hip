@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "vp_comm.h"
+#include "vp_serve_dev.h"
 #include "vp_table.h"
 
 namespace vp {
@@ -2008,50 +2009,16 @@ __global__ void nat_defer_finish(NatArgs a, const uint32_t *list, uint32_t n) {
 // trip per call (≈68 µs); vp_process_one instead hands it to
 // nat_serve, one wave that stays resident and polls a host-coherent mailbox
 // (ServeBox, vp_internal.h): no launch per packet. The host serves through it
-// only while no expiry is due (nat_process_one), so the kernel restates
+// only while no expiry is due (serve_process_one), so the kernel restates
 // nat_main.c:22-109 without the expiry step.
 
 // flow_manager_get_internal / allocate_flow (nat_main.c:68-97) for one LAN
-// key at global sequence seq: its index, allocated when new (*fresh = 1), and
-// stamped; kNone when the table is full (drop).
+// key at global sequence seq: its index, allocated when new (serve_lan,
+// vp_serve_dev.h; the caller stamps it: serve_stamp), or kNone when the table
+// is full (a drop, nat_main.c:87-91).
 __device__ __forceinline__ uint32_t one_lan(const TableDev &t, uint32_t hh, const uint32_t key[4],
-                                            int64_t now, uint64_t seq, uint32_t *fresh) {
-  uint32_t idx = tbl_probe(t, hh, key);
-  if (idx == kNone) {  // dchain_allocate_new_index: the freed stack, then fresh
-    Ctl *c = t.ctl;
-    const uint32_t st = c->stack_top, fn = c->fresh_next;
-    if (st) {
-      idx = t.stack[st - 1];
-      c->stack_top = st - 1;
-    } else if (fn < t.cap) {
-      idx = fn;
-      c->fresh_next = fn + 1;
-    } else {
-      return kNone;  // nat_main.c:87-91
-    }
-    bool tomb = false;
-    uint32_t disp = 0;
-    const uint32_t e = tbl_insert(t, hh, key, idx, &tomb, &disp);
-    if (tomb) c->n_tomb -= 1;
-    c->n_live += 1;
-    c->sh_live += 1;
-    c->disp_count += disp;
-    t.slot_of[idx] = e;
-    t.hash_of[idx] = hh;
-    t.birth[idx] = seq;
-    *fresh = 1;
-  }
-  return idx;  // (the caller stamps it: one_stamp)
-}
-
-// The touch of index idx at (now, seq), right behind the lookup: stamped
-// after the answer instead, the stores' acknowledgement held the wave from
-// its next poll (4.6-4.8 against 4.3-4.4 us per packet,
-// profiles/r06z_serve_stamp.txt).
-__device__ __forceinline__ void one_stamp(const TableDev &t, uint32_t idx, int64_t now,
-                                          uint64_t seq) {
-  t.ts[idx] = (uint64_t)now;
-  t.tseq[idx] = seq;
+                                            uint64_t seq, uint32_t *fresh) {
+  return serve_lan<0xFFFFFFFFu>(t, hh, key, key[3], seq, fresh);
 }
 
 // flow_manager_get_external (nat_main.c:42-67) for external port dp: false
@@ -2082,17 +2049,17 @@ __device__ __forceinline__ uint32_t nat_one(const NatArgs &a, const uint32_t *T,
     uint4 k;
     uint32_t ix;
     if (!one_wan(a, dp, now, seq, &k, &ix)) return in;
-    one_stamp(a.t, ix, now, seq);
+    serve_stamp(a.t, ix, now, seq);
     if ((k.z != sip) | ((k.x >> 16) != sp) | (((k.w >> 16) & 0xFF) != proto)) return in;
     f.w32(h.ip + 16, k.y);
     f.w16(h.l4 + 2, (uint16_t)(k.x & 0xFFFF));
     dst = k.w & 0xFFFF;
   } else {
     const uint32_t key[4] = {sp | (dp << 16), sip, dip, in | (proto << 16)};
-    const uint32_t idx = one_lan(a.t, flowid_hash(T, sp, dp, sip, dip, in, proto), key, now,
-                                 seq, fresh);
+    const uint32_t idx =
+        one_lan(a.t, flowid_hash(T, sp, dp, sip, dip, in, proto), key, seq, fresh);
     if (idx == kNone) return in;
-    one_stamp(a.t, idx, now, seq);
+    serve_stamp(a.t, idx, now, seq);
     f.w32(h.ip + 12, a.ext_ip);
     f.w16(h.l4, (uint16_t)(a.start_port + idx));
     dst = a.wan;
@@ -2125,7 +2092,7 @@ __device__ __forceinline__ uint32_t nat_one_reg(const NatArgs &a, const uint32_t
   if (in == a.wan) {
     uint4 k;
     if (!one_wan(a, dp, now, seq, &k, &ix)) return in;
-    one_stamp(a.t, ix, now, seq);  // (rejuvenated before the anti-spoof check)
+    serve_stamp(a.t, ix, now, seq);  // (rejuvenated before the anti-spoof check)
     if ((k.z != sip) | ((k.x >> 16) != sp) | (((k.w >> 16) & 0xFF) != proto)) return in;
     f.set32at2(30, k.y);        // dst_addr = flow.src_ip
     f.set16(36, k.x & 0xFFFF);  // dst_port = flow.src_port
@@ -2134,10 +2101,10 @@ __device__ __forceinline__ uint32_t nat_one_reg(const NatArgs &a, const uint32_t
     const uint32_t key[4] = {sp | (dp << 16), sip, dip, in | (proto << 16)};
     const uint32_t hh = flowid_hash_batched(T, sp, dp, sip, dip, in, proto);
     if (prof) mk0 = wall_clock64();
-    const uint32_t idx = one_lan(a.t, hh, key, now, seq, fresh);
+    const uint32_t idx = one_lan(a.t, hh, key, seq, fresh);
     if (prof) mk1 = wall_clock64();
     if (idx == kNone) return in;
-    one_stamp(a.t, idx, now, seq);
+    serve_stamp(a.t, idx, now, seq);
     f.set32at2(26, a.ext_ip);
     f.set16(34, (uint16_t)(a.start_port + idx));
     dst = a.wan;
@@ -2150,72 +2117,30 @@ __device__ __forceinline__ uint32_t nat_one_reg(const NatArgs &a, const uint32_t
   return dst;
 }
 
-// A burst request (ServeBox: nf.c's VIGOR_BATCH_SIZE loop, nf.c:178-215): n
-// frames as nf_process would take them one after another, lane i = packet i
-// at sequence seq0 + i; the whole wave calls it. The host sends a burst only
-// while no expiry is due anywhere in it (nat_process_burst), so no flow
-// leaves during the burst: a lookup that hits is final the moment it is made,
-// and only the misses depend on the packets before them. They are settled in
-// packet order by a bounded loop, one new LAN flow per round. Returns
-// kBurstServed, or kBurstDeclined -- before any table write -- when a frame
-// needs the byte-addressed path (nat_one: IP options); the host then runs the
-// burst through the batch pipeline.
+// A burst request (vp_serve_dev.h) for vignat: a WAN lane that looks again
+// reads its port's slot. A frame that needs the byte-addressed path (nat_one:
+// IP options) declines the burst.
 __device__ __forceinline__ uint32_t serve_burst(const NatArgs &a, const uint32_t *T,
                                                 ServeBox *box, uint32_t n, uint64_t seq0,
                                                 uint32_t lane) {
-  typedef unsigned v4u __attribute__((ext_vector_type(4)));
-  typedef unsigned v2u __attribute__((ext_vector_type(2)));
-  constexpr int kSys = 17;  // sc0 | sc1: system-coherent (bypasses the GPU caches)
-  constexpr uint32_t kBody = kServeBurst * kServeFrame;
   const TableDev &t = a.t;
-  const auto fs = __builtin_amdgcn_make_buffer_rsrc(box->bframe, 0, (int)kBody, 0x00020000);
-  const auto ns = __builtin_amdgcn_make_buffer_rsrc(box->bnow, 0, 8 * kServeBurst, 0x00020000);
-  const auto es = __builtin_amdgcn_make_buffer_rsrc(box->bmeta, 0, 4 * kServeBurst, 0x00020000);
-  const auto os = __builtin_amdgcn_make_buffer_rsrc(box->bout, 0, 4 * kServeBurst, 0x00020000);
-  const bool act = lane < n;
-  // (lanes past the burst read zeros and store nothing: offsets past the resources)
-  const uint32_t slot0 = act ? lane * kServeFrame : kBody;
-  v4u q[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++)
-    q[j] = __builtin_amdgcn_raw_buffer_load_b128(fs, (int)(slot0 + 16 * j), 0, kSys);
-  const uint32_t meta =
-      __builtin_amdgcn_raw_buffer_load_b32(es, act ? (int)(4 * lane) : (int)(4 * kServeBurst), 0, kSys);
-  const v2u nw =
-      __builtin_amdgcn_raw_buffer_load_b64(ns, act ? (int)(8 * lane) : (int)(8 * kServeBurst), 0, kSys);
-  const uint32_t len = min(meta & 0xFFFFu, kServeFrame), in = meta >> 16;
-  const int64_t now = (int64_t)((uint64_t)nw[0] | ((uint64_t)nw[1] << 32));
-  RFrame f;  // the first 64 bytes; bytes past len read as 0
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const uint4 v = chunk_keep(make_uint4(q[j][0], q[j][1], q[j][2], q[j][3]), 0, (int)len - 16 * j);
-    f.w[4 * j] = v.x;
-    f.w[4 * j + 1] = v.y;
-    f.w[4 * j + 2] = v.z;
-    f.w[4 * j + 3] = v.w;
-  }
-  // nat_one_reg's tests (nat_main.c:30-38); a frame parse_l34 would follow
-  // past a longer IPv4 header is the byte-addressed path's
-  const uint32_t et = f.w[3] & 0xFFFF, ihl = (f.w[3] >> 16) & 0x0F;
-  const uint32_t tl = bswap16((uint16_t)(f.w[4] & 0xFFFF));
-  const uint16_t unread = (uint16_t)(len - 14);
-  const uint32_t proto = f.w[5] >> 24;
-  const bool ip = act && et == 0x0008 && unread >= 20 && unread >= tl;
-  if (__ballot(ip && ihl > 5)) return kBurstDeclined;
-  const bool go =
-      ip && ihl == 5 && ((proto == 6) | (proto == 17)) && (uint32_t)(len - 34) >= 4u;
+  BurstIn b = burst_load(box, n, lane);
+  const BurstHdr h = burst_hdr(b);  // nat_one_reg's tests (nat_main.c:30-38)
+  if (h.decline) return kBurstDeclined;
+  RFrame &f = b.f;
+  const uint32_t in = b.in;
   // the L4 checksum's bytes past 64, [64, min(14 + total_length, len)), summed
   // straight from the mailbox: each lane its own frame, eight loads in flight
   uint32_t tail = 0;
   {
-    const uint32_t end = go ? min(14 + tl, len) : 0u;
+    const uint32_t end = h.go ? min(14 + h.tl, b.len) : 0u;
     for (uint32_t base = 64; __ballot(base < end); base += 128) {
       v4u x[8];
 #pragma unroll
       for (uint32_t u = 0; u < 8; u++) {
         const uint32_t cc = base + 16 * u;
-        x[u] = __builtin_amdgcn_raw_buffer_load_b128(fs, (int)(cc < end ? slot0 + cc : kBody), 0,
-                                                     kSys);
+        x[u] = __builtin_amdgcn_raw_buffer_load_b128(
+            b.fs, (int)(cc < end ? b.slot0 + cc : kBurstBody), 0, kSys);
       }
 #pragma unroll
       for (uint32_t u = 0; u < 8; u++) {
@@ -2226,53 +2151,26 @@ __device__ __forceinline__ uint32_t serve_burst(const NatArgs &a, const uint32_t
       }
     }
   }
-  const uint32_t sp = f.w[8] >> 16, dp = f.w[9] & 0xFFFF;
-  const uint32_t sip = f.u32at2(26), dip = f.u32at2(30);
-  const bool lanp = go && in != a.wan;
-  const uint32_t key[4] = {sp | (dp << 16), sip, dip, in | (proto << 16)};
-  const uint32_t hh = flowid_hash_batched(T, sp, dp, sip, dip, in, proto);
-  const int wi = (int)dp - (int)a.start_port;
-  const bool wanp = go && in == a.wan && wi >= 0 && wi < (int)t.cap;  // (else: a drop)
+  const bool lanp = h.go && in != a.wan;
+  const uint32_t key[4] = {h.sp | (h.dp << 16), h.sip, h.dip, in | (h.proto << 16)};
+  const uint32_t hh = flowid_hash_batched(T, h.sp, h.dp, h.sip, h.dip, in, h.proto);
+  const int wi = (int)h.dp - (int)a.start_port;
+  const bool wanp = h.go && in == a.wan && wi >= 0 && wi < (int)t.cap;  // (else: a drop)
   const uint32_t widx = wanp ? (uint32_t)wi : 0u;
-  // round 0: every lane looks its flow up in the table as the burst found it
+  // round 0, then the misses in packet order
   uint32_t idx = kNone, fresh = 0;
   if (lanp) idx = tbl_probe(t, hh, key);
   if (wanp && t.slot_of[widx] != kNone) idx = widx;
-  bool lpend = lanp && idx == kNone, wpend = wanp && idx == kNone;
-  // the misses in packet order: the lowest pending LAN lane m looks again (an
-  // earlier lane of this burst may have inserted its key) and allocates as a
-  // packet of its own would (one_lan: kNone when the table is full, a drop);
-  // a pending WAN lane below m has every flow born before it in the table
-  // and is final, hit or drop. At most one round per lane.
-  for (uint32_t r = 0; r < kServeBurst; r++) {
-    const uint64_t lp = __ballot(lpend);
-    if (!lp) break;
-    const uint32_t m = (uint32_t)__ffsll((unsigned long long)lp) - 1;
-    if (wpend && lane < m) {
-      if (t.slot_of[widx] != kNone) idx = widx;
-      wpend = false;
-    }
-    if (lane == m) {
-      idx = one_lan(t, hh, key, now, seq0 + lane, &fresh);
-      lpend = false;
-    }
-    // (lane m's insert before the later lanes' lookups: one wave, workgroup
-    // scope; an agent-scope release would write the XCD's L2 back)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  }
-  if (wpend && t.slot_of[widx] != kNone) idx = widx;  // (no LAN miss before them is left)
+  burst_settle(
+      lane, lanp && idx == kNone, wanp && idx == kNone,
+      [&] {
+        if (t.slot_of[widx] != kNone) idx = widx;
+      },
+      [&] { idx = one_lan(t, hh, key, seq0 + lane, &fresh); });
   // Stamps. idx != kNone: a LAN packet with a flow (a table-full drop stamps
   // nothing) or a WAN packet whose port holds one (stamped before the
-  // anti-spoof check). For every index the burst's last packet that touched
-  // it must win: the highest lane holding an index stores both words, the
-  // others store nothing (no order between lanes' stores is relied on).
-  bool last = idx != kNone;
-  for (uint32_t j = 1; j < n; j++) {
-    const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)idx, (int)j);
-    if (j > lane && o == idx) last = false;
-  }
-  if (last) one_stamp(t, idx, now, seq0 + lane);
+  // anti-spoof check).
+  if (burst_last(idx, n, lane)) serve_stamp(t, idx, b.now, seq0 + lane);
   // the rewrite, each lane its own frame
   uint32_t out = in, rew = 0;
   if (idx != kNone) {
@@ -2283,7 +2181,7 @@ __device__ __forceinline__ uint32_t serve_burst(const NatArgs &a, const uint32_t
       rew = 1;
     } else {
       const uint4 k = tbl_key_of(t, idx);
-      if (!((k.z != sip) | ((k.x >> 16) != sp) | (((k.w >> 16) & 0xFF) != proto))) {
+      if (!((k.z != h.sip) | ((k.x >> 16) != h.sp) | (((k.w >> 16) & 0xFF) != h.proto))) {
         f.set32at2(30, k.y);        // dst_addr = flow.src_ip
         f.set16(36, k.x & 0xFFFF);  // dst_port = flow.src_port
         dst = k.w & 0xFFFF;
@@ -2293,7 +2191,7 @@ __device__ __forceinline__ uint32_t serve_burst(const NatArgs &a, const uint32_t
     if (rew) {
       uint32_t mw[3];
       macs_for(a, dst, mw);
-      fast_checksums(f, proto, tl, tail);
+      fast_checksums(f, h.proto, h.tl, tail);
       f.w[0] = mw[0];
       f.w[1] = mw[1];
       f.w[2] = mw[2];
@@ -2307,37 +2205,29 @@ __device__ __forceinline__ uint32_t serve_burst(const NatArgs &a, const uint32_t
 #pragma unroll
     for (int j = 0; j < 4; j++)
       __builtin_amdgcn_raw_buffer_store_b128(
-          (v4u){f.w[4 * j], f.w[4 * j + 1], f.w[4 * j + 2], f.w[4 * j + 3]}, fs,
-          (int)(slot0 + 16 * j), 0, kSys);
+          (v4u){f.w[4 * j], f.w[4 * j + 1], f.w[4 * j + 2], f.w[4 * j + 3]}, b.fs,
+          (int)(b.slot0 + 16 * j), 0, kSys);
   }
-  const uint32_t res = out | (fresh << 16) | (rew << 17);
-  v4u o4;
-#pragma unroll
-  for (int k = 0; k < 4; k++) o4[k] = (uint32_t)__shfl((int)res, (int)((4 * lane + k) & 63));
-  if (4 * lane < n) __builtin_amdgcn_raw_buffer_store_b128(o4, os, (int)(16 * lane), 0, kSys);
-  // (all of it complete before the answer chunk that announces it)
-  __atomic_signal_fence(__ATOMIC_SEQ_CST);
-  __builtin_amdgcn_s_waitcnt(0);
-  __atomic_signal_fence(__ATOMIC_SEQ_CST);
+  burst_out(b, out | (fresh << 16) | (rew << 17), n, lane);
   return kBurstServed;
 }
 
 // The server: one wave. Every poll reads the request chunks whole (ServeBox,
 // vp_internal.h: one PCIe read brings the doorbell, the time and a frame of up
 // to kServeInline bytes), one poll in flight per wave (VIGPATH_SERVE_WAVES
-// waves poll, staggered; the first to claim a request serves it); longer frames are read from `frame` afterwards. The frame goes into LDS, the
-// wave sums the L4 bytes past byte 64, lane 0 runs the packet, the frame goes
-// back (16-byte system-coherent stores) and the answer word follows once
-// every store has completed. Packets take global sequence numbers seq, seq +
-// 1, ... A burst request (a small vp_process_batch / vp_process_mbufs call,
-// nat_process_burst) brings up to kServeBurst frames in the burst body; the
+// waves poll, staggered; the first to claim a request serves it); longer
+// frames are read from `frame` afterwards. The frame goes into LDS, the wave
+// sums the L4 bytes past byte 64, lane 0 runs the packet, the frame goes back
+// (16-byte system-coherent stores) and the answer word follows once every
+// store has completed. Packets take global sequence numbers seq, seq + 1, ...
+// A burst request (a small vp_process_batch / vp_process_mbufs call,
+// serve_process_burst) brings up to kServeBurst frames in the burst body; the
 // wave that claims it serves it whole, one lane per packet (serve_burst), and
-// it takes as many sequence numbers. It leaves on the leave request or after `idle` wall-clock ticks
-// without a request; a request posted as it leaves finds the stream idle and
-// the host launches it again (nat_process_one). flags: bit 0, the stage
-// clock (VIGPATH_SERVE_PROF); bits 3-9: the waves' stagger in wall-clock
-// ticks; bits 10-17: the first poll's delay after an answer; bit 18: adapt it;
-// bits 19-23: the ticks a late poll adds to it.
+// it takes as many sequence numbers. It leaves on the leave request or after
+// `idle` wall-clock ticks without a request; a request posted as it leaves
+// finds the stream idle and the host launches it again (serve_wait). flags:
+// bit 0, the stage clock (VIGPATH_SERVE_PROF); bits 3-9: the waves' stagger in
+// wall-clock ticks; bits 10-23: serve_poll's.
 __global__ __launch_bounds__(256) void nat_serve(NatArgs a, ServeBox *box, uint64_t seq0,
                                                  uint64_t idle, uint32_t flags) {
   __shared__ uint32_t T[kNatTabWords];
@@ -2356,20 +2246,12 @@ __global__ __launch_bounds__(256) void nat_serve(NatArgs a, ServeBox *box, uint6
   }
   load_nat_tables(T, a);  // (its barrier covers the words above)
   const bool prof = flags & 1u;
-  typedef unsigned v4u __attribute__((ext_vector_type(4)));
-  constexpr int kSys = 17;  // sc0 | sc1: system-coherent (bypasses the GPU caches)
-  const auto ms = __builtin_amdgcn_make_buffer_rsrc(box->msg, 0, 16 * kServeChunks, 0x00020000);
+  const ServeIo io = serve_io(box, lane);
   const auto rs = __builtin_amdgcn_make_buffer_rsrc(box->frame, 0, kServeFrame, 0x00020000);
-  const auto as = __builtin_amdgcn_make_buffer_rsrc(box->amsg, 0, 16 * kServeChunks, 0x00020000);
-  // (lanes past the chunks read nothing: an offset past the resource)
-  const int moff = lane < kServeChunks ? (int)(16 * lane) : (int)(16 * kServeChunks);
-  auto poll = [&]() -> v4u { return __builtin_amdgcn_raw_buffer_load_b128(ms, moff, 0, kSys); };
   auto lds_ld = [](uint32_t *p) {
     return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
   };
   uint32_t *fw = reinterpret_cast<uint32_t *>(fr);
-  // one poll's chunks: -1 nothing new (not yet whole, or another wave's),
-  // 0 a request served, 1 leave
   auto serve = [&](const v4u &c) -> int {
     const uint32_t want = __builtin_amdgcn_readfirstlane(lds_ld(&done_s)) + 1;
     const uint32_t tag0 = __builtin_amdgcn_readfirstlane(c[3]);
@@ -2396,8 +2278,7 @@ __global__ __launch_bounds__(256) void nat_serve(NatArgs a, ServeBox *box, uint6
       const uint32_t bn = min(max(in, 1u), kServeBurst);
       const uint32_t st = serve_burst(a, T, box, bn, seq, lane);
       if (lane == 0) {
-        __builtin_amdgcn_raw_buffer_store_b128((v4u){st, bn, 0u, want}, as, 0, 0, kSys);
-        __hip_atomic_store(&box->ans, (uint64_t)want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        burst_answer(io, box, st, bn, want);
         t0_s = wall_clock64();
         if (st == kBurstServed) seq_s = seq + bn;
       }
@@ -2408,16 +2289,10 @@ __global__ __launch_bounds__(256) void nat_serve(NatArgs a, ServeBox *box, uint6
       wave_lds_sync();
       return 0;
     }
-    const int64_t now =
-        (int64_t)((uint64_t)__builtin_amdgcn_readfirstlane(c[1]) |
-                  ((uint64_t)__builtin_amdgcn_readfirstlane(c[2]) << 32));
+    const int64_t now = serve_now(c);
     const uint32_t nch = (len + 15) / 16;
-    if (inl) {  // chunk k >= 1: frame bytes 12k - 12 .. 12k - 1
-      if (lane >= 1 && lane < need) {
-        fw[3 * lane - 3] = c[0];
-        fw[3 * lane - 2] = c[1];
-        fw[3 * lane - 1] = c[2];
-      }
+    if (inl) {
+      serve_chunks_in(fw, c, lane, need);
     } else {  // the whole frame from `frame` (the host wrote it before the chunks)
       for (uint32_t i = lane; i < nch; i += 64) {
         const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(16 * i), 0, kSys);
@@ -2441,15 +2316,7 @@ __global__ __launch_bounds__(256) void nat_serve(NatArgs a, ServeBox *box, uint6
     uint64_t mk0 = 0, mk1 = 0, mk2 = 0;
     if (lane == 0) {
       uint32_t fresh = 0;
-      RFrame f;
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const uint4 v = chunk_keep(fr[j], 0, (int)len - 16 * j);
-        f.w[4 * j] = v.x;
-        f.w[4 * j + 1] = v.y;
-        f.w[4 * j + 2] = v.z;
-        f.w[4 * j + 3] = v.w;
-      }
+      RFrame f = serve_rframe([&](int j) { return fr[j]; }, len);
       uint32_t out = nat_one_reg(a, T, f, in, len, tail, now, seq, &fresh, prof, mk0, mk1);
       if (prof) mk2 = wall_clock64();
       if (out == kNone) {
@@ -2470,7 +2337,7 @@ __global__ __launch_bounds__(256) void nat_serve(NatArgs a, ServeBox *box, uint6
       if (lane < need) {
         const v4u v = lane == 0 ? (v4u){res, 0u, 0u, want}
                                 : (v4u){fw[3 * lane - 3], fw[3 * lane - 2], fw[3 * lane - 1], want};
-        __builtin_amdgcn_raw_buffer_store_b128(v, as, (int)(16 * lane), 0, kSys);
+        __builtin_amdgcn_raw_buffer_store_b128(v, io.as, (int)(16 * lane), 0, kSys);
       }
     } else {
       for (uint32_t i = lane; i < nch; i += 64) {
@@ -2483,7 +2350,7 @@ __global__ __launch_bounds__(256) void nat_serve(NatArgs a, ServeBox *box, uint6
       __builtin_amdgcn_s_waitcnt(0);
       __atomic_signal_fence(__ATOMIC_SEQ_CST);
       if (lane == 0)
-        __builtin_amdgcn_raw_buffer_store_b128((v4u){res, 0u, 0u, want}, as, 0, 0, kSys);
+        __builtin_amdgcn_raw_buffer_store_b128((v4u){res, 0u, 0u, want}, io.as, 0, 0, kSys);
     }
     if (lane == 0) {
       // (the answer word: where a relaunched server starts counting; the
@@ -2525,41 +2392,9 @@ __global__ __launch_bounds__(256) void nat_serve(NatArgs a, ServeBox *box, uint6
     const uint64_t w = wall_clock64();
     while (wall_clock64() - w < (uint64_t)gap * wv) __builtin_amdgcn_s_sleep(1);
   }
-  // After an answer the next request cannot come before the answer has
-  // crossed to the host and the host's loop has turned round (about half a
-  // round trip plus its own time): a poll issued at once reads the mailbox
-  // too early and the request waits for the poll after it, a whole round
-  // trip later. The first poll after an answer waits `after` wall-clock ticks
-  // (flags bits 10-17; VIGPATH_SERVE_AFTER) so that it reads about when the
-  // request lands.
-  // The delay adapts (flags bit 18): a request the first poll caught takes
-  // a tick off it, one that needed a later poll adds eight -- a late poll
-  // costs a round trip, an early one only its excess -- so it settles just
-  // past where the caller's requests land, whatever the caller's loop.
-  uint32_t after = (flags >> 10) & 0xFFu;
-  const uint32_t up = (flags >> 19) & 0x1Fu;  // ticks added after a late poll
-  const bool adapt = (flags >> 18) & 1u;
-  uint32_t polls = 0;  // polls since the last answer
-  for (;;) {
-    const v4u q = poll();
-    const int st = serve(q);
-    if (st == 1) break;
-    polls++;
-    if (st < 0) {
-      if (wall_clock64() - __hip_atomic_load(&t0_s, __ATOMIC_RELAXED,
-                                              __HIP_MEMORY_SCOPE_WORKGROUP) > idle)
-        break;
-      __builtin_amdgcn_s_sleep(1);
-      continue;
-    }
-    if (adapt && polls == 1 && after > 0) after--;
-    if (adapt && polls > 1 && polls < 64) after = min(after + up, 200u);
-    polls = 0;
-    if (after) {
-      const uint64_t w = wall_clock64();
-      while (wall_clock64() - w < after) __builtin_amdgcn_s_sleep(1);
-    }
-  }
+  serve_poll(io, flags, idle, serve, [&] {
+    return __hip_atomic_load(&t0_s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  });
 }
 
 // =============================================================== host ==
@@ -3371,82 +3206,6 @@ int nat_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
   return 0;
 }
 
-int nat_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, int64_t now,
-                    uint16_t *out) {
-  std::lock_guard<std::recursive_mutex> sg(c->srv_mu);
-  FlowTable &t = c->ft;
-  // no expiry due at this packet (run_batch's test for a segment of one)
-  const bool ok = !serve_off() && !c->comm && len <= kServeFrame && now >= 0 &&
-                  now >= c->last_now &&
-                  nat_cutoff(c, now) <= (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)now);
-  if (!ok) {
-    VP_TRY(serve_stop(c));
-    return 1;
-  }
-  VP_TRY(serve_ready(c));
-  ServeBox *bx = c->sbox;
-  const auto h0 = std::chrono::steady_clock::now();
-  // the request chunks (ServeBox): payload words first, then each chunk's
-  // tag; chunk 0 last; a longer frame whole through `frame` before them
-  const uint32_t req = ++c->srv_req;
-  uint32_t m[3 * kServeChunks] = {};
-  m[0] = len | ((uint32_t)in_dev << 16);
-  m[1] = (uint32_t)(uint64_t)now;
-  m[2] = (uint32_t)((uint64_t)now >> 32);
-  uint32_t need = 1;
-  if (len <= kServeInline) {
-    memcpy(&m[3], frame, len);
-    need = (12 + len + 11) / 12;
-  } else {
-    memcpy(bx->frame, frame, len);
-  }
-  for (uint32_t k = need; k-- > 0;) {
-    bx->msg[k][0] = m[3 * k];
-    bx->msg[k][1] = m[3 * k + 1];
-    bx->msg[k][2] = m[3 * k + 2];
-    __atomic_store_n(&bx->msg[k][3], req, __ATOMIC_RELEASE);
-  }
-  // (need: the chunks the request took, as many as the answer takes)
-  VP_TRY(serve_wait(c, req, need));
-  const uint32_t res = bx->amsg[0][0];
-  if (len <= kServeInline) {
-    uint32_t m2[3 * kServeChunks];
-    for (uint32_t k = 1; k < need; k++) {
-      m2[3 * k] = bx->amsg[k][0];
-      m2[3 * k + 1] = bx->amsg[k][1];
-      m2[3 * k + 2] = bx->amsg[k][2];
-    }
-    memcpy(frame, &m2[3], len);
-  } else {
-    memcpy(frame, bx->frame, len);
-  }
-  const uint64_t ans = (uint64_t)req | ((uint64_t)res << 32);
-  *out = (uint16_t)(ans >> 32);
-  if ((ans >> 48) & 1u) t.ts_floor = std::min<uint64_t>(t.ts_floor, (uint64_t)now);
-  c->seq += 1;
-  c->last_now = now;
-  c->srv_stats.packets_one += 1;
-  if (serve_prof()) {  // (device stamps: wall clock ticks, 100 MHz)
-    const double us_tick = 1e3 / (double)(c->srv_idle / c->srv_idle_ms);
-    c->srv_prof[0] +=
-        std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count();
-    const uint64_t *p = bx->prof;
-    c->srv_prof[1] += us_tick * (double)(p[1] - p[0]);
-    c->srv_prof[2] += us_tick * (double)(p[2] - p[1]);
-    if (p[3] && p[4]) {  // (register-path LAN packets: hash | table | rewrite)
-      c->srv_prof[6] += us_tick * (double)(p[3] - p[2]);
-      c->srv_prof[7] += us_tick * (double)(p[4] - p[3]);
-      c->srv_prof[8] += us_tick * (double)(p[5] - p[4]);
-      c->srv_prof[9] += 1;
-    }
-    c->srv_prof[3] += us_tick * (double)(p[6] - p[2]);
-    c->srv_prof[4] += us_tick * (double)(p[7] - p[6]);
-    c->srv_prof[10] += (double)(p[9] - p[8]);  // (shader cycles over `packet`: MHz)
-    c->srv_prof[5] += 1;
-  }
-  return 0;
-}
-
 // The largest host batch routed to the server as burst requests: the largest
 // n for which the served path measured faster per packet than the batch
 // pipeline on the MI355X (profiles/r07_burst_sweep.txt: 0.24 against 0.30 us
@@ -3455,65 +3214,13 @@ int nat_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, in
 // VIGPATH_SERVE_BURST overrides it; 0 routes nothing.
 constexpr uint32_t kServeBurstRoute = 256;
 
-int nat_process_burst(vp_ctx *c, const vp_mbuf_batch *b, uint32_t first, uint32_t count,
-                      uint32_t *served) {
-  *served = 0;
-  std::lock_guard<std::recursive_mutex> sg(c->srv_mu);
-  const uint32_t limit = serve_burst_limit(kServeBurstRoute);
-  if (serve_off() || c->comm || count == 0 || count > limit) return 1;
-  FlowTable &t = c->ft;
-  auto at = [&](uint32_t i) {
-    return b->now ? b->now[first + i] : b->now0 + (int64_t)(first + i) * b->now_step;
-  };
-  // the whole range or none of it: frames the mailbox holds, times that do
-  // not go back, and no expiry due anywhere in it -- the cutoff is monotone in
-  // time and flows born in the range are stamped >= its first time, so the
-  // last packet's cutoff against the floor as the range finds it decides
-  const int64_t n0 = at(0), n1 = at(count - 1);
-  if (n0 < 0 || n0 < c->last_now) return 1;
-  int64_t prev = n0;
-  for (uint32_t i = 0; i < count; i++) {
-    const int64_t ti = at(i);
-    if (b->len[first + i] > kServeFrame || ti < prev) return 1;
-    prev = ti;
-  }
-  if (nat_cutoff(c, n1) > (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)n0)) return 1;
-  VP_TRY(serve_ready(c));
-  ServeBox *bx = c->sbox;
-  for (uint32_t a0 = 0; a0 < count; a0 += kServeBurst) {
-    const uint32_t m = std::min(kServeBurst, count - a0);
-    // the body first, then the tagged chunk that announces it (ServeBox)
-    for (uint32_t i = 0; i < m; i++) {
-      const uint32_t p = first + a0 + i;
-      if (b->len[p]) memcpy(bx->bframe[i], b->frames[p], b->len[p]);
-      bx->bmeta[i] = b->len[p] | ((uint32_t)b->in_dev[p] << 16);
-      bx->bnow[i] = at(a0 + i);
-    }
-    const uint32_t req = ++c->srv_req;
-    bx->msg[0][0] = kServeBurstOp | (m << 16);
-    bx->msg[0][1] = 0;
-    bx->msg[0][2] = 0;
-    __atomic_store_n(&bx->msg[0][3], req, __ATOMIC_RELEASE);
-    VP_TRY(serve_wait(c, req, 1));
-    if (bx->amsg[0][0] != kBurstServed) {  // a byte-path frame: nothing of it was done
-      c->srv_stats.declined += 1;
-      return 1;
-    }
-    bool fresh = false;
-    for (uint32_t i = 0; i < m; i++) {
-      const uint32_t p = first + a0 + i, r = bx->bout[i];
-      b->out_dev[p] = (uint16_t)r;
-      fresh |= (r >> 16) & 1u;
-      if ((r >> 17) & 1u) memcpy(b->frames[p], bx->bframe[i], std::min<uint32_t>(b->len[p], 64));
-    }
-    if (fresh) t.ts_floor = std::min<uint64_t>(t.ts_floor, (uint64_t)at(a0));
-    c->seq += m;
-    c->last_now = at(a0 + m - 1);
-    c->srv_stats.bursts += 1;
-    c->srv_stats.burst_packets += m;
-    *served += m;
-  }
-  return 0;
+// vignat through the mailbox (serve_process_one / serve_process_burst,
+// vp_serve.hip): the whole frame goes and comes back rewritten, one longer
+// than kServeInline through `frame`; of a burst's frame all bytes go (the L4
+// checksum's) and the first 64 come back. The stage clock is vignat's.
+const ServeNf &nat_serve_nf() {
+  static const ServeNf nf = {nat_cutoff, &vp_ctx::ft, true, kServeFrame, 64, kServeBurstRoute, true};
+  return nf;
 }
 
 void build_flowid_tables(std::vector<uint32_t> &tab) {

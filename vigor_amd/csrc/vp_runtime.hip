@@ -757,11 +757,10 @@ int vp_process_device(vp_ctx *c, const vp_dev_batch *b, void *stream) {
 int vp_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, int64_t now,
                    uint16_t *out_dev) {
   if (!c || !frame || !out_dev) return VP_EINVAL;
-  if (c->kind == KIND_NAT || c->kind == KIND_FW) {
+  if (const ServeNf *nf = serve_nf(c->kind)) {
     // (no hipSetDevice here: a served packet makes no HIP call; the server's
     // launch and stop set the device themselves)
-    const int rc = c->kind == KIND_NAT ? nat_process_one(c, in_dev, frame, len, now, out_dev)
-                                       : fw_process_one(c, in_dev, frame, len, now, out_dev);
+    const int rc = serve_process_one(c, *nf, in_dev, frame, len, now, out_dev);
     if (rc <= 0) return rc;  // (1: not eligible, the batch path below)
     if (hipSetDevice(c->gpu) != hipSuccess) return VP_EIO;
   }

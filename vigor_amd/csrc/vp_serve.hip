@@ -1,11 +1,11 @@
-// vp_process_one's mailbox, host side (ServeBox, vp_internal.h): the parts
-// that serve any context whose NF has a resident kernel -- vignat (nat_serve,
-// vp_nat.hip) and vigfw (fw_serve, vp_fw.hip). Launching the kernel, waiting
-// for an answer, relaunching after an idle exit, stopping it before any other
-// entry point touches the table, and yielding the GPU's hardware queues
-// between contexts. What a request holds and how an answer is read is the
-// NF's own (nat_process_one / nat_process_burst, fw_process_one /
-// fw_process_burst).
+// vp_process_one's mailbox, host side (ServeBox, vp_internal.h), for any
+// context whose NF has a resident kernel -- vignat (nat_serve, vp_nat.hip) and
+// vigfw (fw_serve, vp_fw.hip). Launching the kernel, waiting for an answer,
+// relaunching after an idle exit, stopping it before any other entry point
+// touches the table, yielding the GPU's hardware queues between contexts, and
+// the requests themselves: one packet (serve_process_one) and a small burst
+// (serve_process_burst), the NFs told apart by their ServeNf alone. The
+// device side's shared half is vp_serve_dev.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -214,6 +214,133 @@ int serve_wait(vp_ctx *c, uint32_t req, uint32_t need) {
     VP_HIP(q);
     if (answered()) continue;
     VP_TRY(serve_launch(c));
+  }
+  return 0;
+}
+
+// vignat's stage clock (VIGPATH_SERVE_PROF) for the packet just answered: the
+// host call since h0 and the device's stamps (wall clock ticks, 100 MHz).
+static void serve_prof_add(vp_ctx *c, std::chrono::steady_clock::time_point h0) {
+  const double us_tick = 1e3 / (double)(c->srv_idle / c->srv_idle_ms);
+  c->srv_prof[0] +=
+      std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count();
+  const uint64_t *p = c->sbox->prof;
+  c->srv_prof[1] += us_tick * (double)(p[1] - p[0]);
+  c->srv_prof[2] += us_tick * (double)(p[2] - p[1]);
+  if (p[3] && p[4]) {  // (register-path LAN packets: hash | table | rewrite)
+    c->srv_prof[6] += us_tick * (double)(p[3] - p[2]);
+    c->srv_prof[7] += us_tick * (double)(p[4] - p[3]);
+    c->srv_prof[8] += us_tick * (double)(p[5] - p[4]);
+    c->srv_prof[9] += 1;
+  }
+  c->srv_prof[3] += us_tick * (double)(p[6] - p[2]);
+  c->srv_prof[4] += us_tick * (double)(p[7] - p[6]);
+  c->srv_prof[10] += (double)(p[9] - p[8]);  // (shader cycles over `packet`: MHz)
+  c->srv_prof[5] += 1;
+}
+
+int serve_process_one(vp_ctx *c, const ServeNf &nf, uint16_t in_dev, uint8_t *frame,
+                      uint16_t len, int64_t now, uint16_t *out) {
+  std::lock_guard<std::recursive_mutex> sg(c->srv_mu);
+  FlowTable &t = c->*nf.table;
+  // no expiry due at this packet (run_batch's test for a segment of one)
+  const bool ok = !serve_off() && !c->comm && len <= kServeFrame && now >= 0 &&
+                  now >= c->last_now &&
+                  nf.cutoff(c, now) <= (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)now);
+  if (!ok) {
+    VP_TRY(serve_stop(c));
+    return 1;
+  }
+  VP_TRY(serve_ready(c));
+  ServeBox *bx = c->sbox;
+  const bool prof = nf.prof && serve_prof();
+  const auto h0 = prof ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
+  // the request: a frame longer than the chunks hold goes whole through
+  // `frame` before them and comes back there, or only its first kServeInline
+  // bytes go (nf.one_whole)
+  const uint32_t req = ++c->srv_req;
+  const bool via_frame = nf.one_whole && len > kServeInline;
+  const uint32_t got = via_frame ? 0u : std::min<uint32_t>(len, kServeInline);
+  if (via_frame) memcpy(bx->frame, frame, len);
+  uint32_t m[3 * kServeChunks];
+  const uint32_t need = serve_pack(m, len | ((uint32_t)in_dev << 16), now, frame, got);
+  serve_post(bx, m, need, req);
+  // the answer: chunk 0, and the chunks that bring the frame bytes back -- as
+  // many as the request took, or chunk 1 alone (bytes 0-11)
+  const uint32_t back = nf.one_whole ? got : std::min(got, 12u);
+  VP_TRY(serve_wait(c, req, 1 + (back + 11) / 12));
+  const uint32_t res = bx->amsg[0][0];  // out | fresh << 16
+  if (via_frame)
+    memcpy(frame, bx->frame, len);
+  else
+    serve_unpack(bx, frame, back);
+  *out = (uint16_t)res;
+  if ((res >> 16) & 1u) t.ts_floor = std::min<uint64_t>(t.ts_floor, (uint64_t)now);
+  c->seq += 1;
+  c->last_now = now;
+  c->srv_stats.packets_one += 1;
+  if (prof) serve_prof_add(c, h0);
+  return 0;
+}
+
+int serve_process_burst(vp_ctx *c, const ServeNf &nf, const vp_mbuf_batch *b, uint32_t first,
+                        uint32_t count, uint32_t *served) {
+  *served = 0;
+  std::lock_guard<std::recursive_mutex> sg(c->srv_mu);
+  const uint32_t limit = serve_burst_limit(nf.burst_route);
+  if (serve_off() || c->comm || count == 0 || count > limit) return 1;
+  FlowTable &t = c->*nf.table;
+  auto at = [&](uint32_t i) {
+    return b->now ? b->now[first + i] : b->now0 + (int64_t)(first + i) * b->now_step;
+  };
+  // the whole range or none of it: frames the mailbox holds, times that do
+  // not go back, and no expiry due anywhere in it -- the cutoff is monotone in
+  // time and flows born in the range are stamped >= its first time, so the
+  // last packet's cutoff against the floor as the range finds it decides
+  const int64_t n0 = at(0), n1 = at(count - 1);
+  if (n0 < 0 || n0 < c->last_now) return 1;
+  int64_t prev = n0;
+  for (uint32_t i = 0; i < count; i++) {
+    const int64_t ti = at(i);
+    if (b->len[first + i] > kServeFrame || ti < prev) return 1;
+    prev = ti;
+  }
+  if (nf.cutoff(c, n1) > (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)n0)) return 1;
+  VP_TRY(serve_ready(c));
+  ServeBox *bx = c->sbox;
+  for (uint32_t a0 = 0; a0 < count; a0 += kServeBurst) {
+    const uint32_t m = std::min(kServeBurst, count - a0);
+    // the body first, then the tagged chunk that announces it (ServeBox)
+    for (uint32_t i = 0; i < m; i++) {
+      const uint32_t p = first + a0 + i;
+      if (b->len[p])
+        memcpy(bx->bframe[i], b->frames[p], std::min<uint32_t>(b->len[p], nf.burst_in));
+      bx->bmeta[i] = b->len[p] | ((uint32_t)b->in_dev[p] << 16);
+      bx->bnow[i] = at(a0 + i);
+    }
+    const uint32_t req = ++c->srv_req;
+    const uint32_t op[3] = {kServeBurstOp | (m << 16), 0, 0};
+    serve_post(bx, op, 1, req);
+    VP_TRY(serve_wait(c, req, 1));
+    if (bx->amsg[0][0] != kBurstServed) {  // a byte-path frame: nothing of it was done
+      c->srv_stats.declined += 1;
+      return 1;
+    }
+    bool fresh = false;
+    for (uint32_t i = 0; i < m; i++) {
+      const uint32_t p = first + a0 + i, r = bx->bout[i];
+      b->out_dev[p] = (uint16_t)r;
+      fresh |= (r >> 16) & 1u;
+      // (only rewritten frames come back, and only the bytes a rewrite can change)
+      if ((r >> 17) & 1u)
+        memcpy(b->frames[p], bx->bframe[i], std::min<uint32_t>(b->len[p], nf.burst_back));
+    }
+    if (fresh) t.ts_floor = std::min<uint64_t>(t.ts_floor, (uint64_t)at(a0));
+    c->seq += m;
+    c->last_now = at(a0 + m - 1);
+    c->srv_stats.bursts += 1;
+    c->srv_stats.burst_packets += m;
+    *served += m;
   }
   return 0;
 }
