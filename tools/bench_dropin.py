@@ -8,11 +8,12 @@ and through vp_process_batch in bursts (nf.c:178-215).
 
   tools/bench_dropin.py --nf fw                      # batch 0 / 32 / 1024
   tools/bench_dropin.py --nf fw --sweep 32,64,128    # burst routing limit
+  tools/bench_dropin.py --nf bridge                  # vigbridge: 1,024 stations
 
 --sweep N,...: each burst size twice in this run, VIGPATH_SERVE_BURST forcing
 the resident kernel (a limit above every N) and the batch pipeline (0): the
-routing limit (kServeBurstRoute / kFwBurstRoute) is the largest N at which
-the served path is the faster one per packet.
+routing limit (kServeBurstRoute / kFwBurstRoute / kBridgeBurstRoute) is the
+largest N at which the served path is the faster one per packet.
 
 --tree DIR: another build of the library (a checkout of another commit with
 its own host/ and vigor_amd/), for A/B on one machine in one session.
@@ -33,15 +34,34 @@ sys.path.insert(0, ROOT)
 from vigor_amd import traces as T  # noqa: E402
 
 SLOT = 64
+
+
+def wan_port(n, flows):
+    """vignat, vigfw: every steady packet is a LAN hit and goes out on the WAN
+    port."""
+    return np.ones(n, np.uint16)
+
+
+def bridge_port(n, flows):
+    """T.bridge_trace: frame p goes to station dst_k = (p + flows / 2) mod
+    flows, learned by the warm-up on port dst_k & 1."""
+    p = np.arange(n, dtype=np.int64)
+    return (((p + flows // 2) % flows) & 1).astype(np.uint16)
+
+
+# per NF: its loop binary, trace, arguments, the option that sizes its table to
+# `--flows`, and the out port expected of every steady packet
 NF = {
-    "nat": dict(loop="nf_loop", trace=T.nat_lan_trace,
+    "nat": dict(loop="nf_loop", trace=T.nat_lan_trace, size="--max-flows", steady=wan_port,
                 args=["--expire", "60000000", "--starting-port", "0", "--wan", "1",
                       "--extip", "192.168.4.2", "--eth-dest", "0,90:e2:ba:55:12:20",
                       "--eth-dest", "1,90:e2:ba:55:12:21"]),
-    "fw": dict(loop="nf_loop_fw", trace=T.fw_trace,
+    "fw": dict(loop="nf_loop_fw", trace=T.fw_trace, size="--max-flows", steady=wan_port,
                args=["--expire", "60000000", "--wan", "1",
                      "--eth-dest", "0,90:e2:ba:55:12:20",
                      "--eth-dest", "1,90:e2:ba:55:12:21"]),
+    "bridge": dict(loop="nf_loop_bridge", trace=T.bridge_trace, size="--capacity",
+                   steady=bridge_port, args=["--expire", "60000000"]),
 }
 
 
@@ -50,7 +70,7 @@ def run_loop(tree, nf, tin, tout, flows, batch, env):
     cmd = [os.path.join(tree, "host", NF[nf]["loop"]), tin, tout, "--warm", str(flows)]
     if batch:
         cmd += ["--batch", str(batch)]
-    cmd += ["--"] + NF[nf]["args"] + ["--max-flows", str(flows)]
+    cmd += ["--"] + NF[nf]["args"] + [NF[nf]["size"], str(flows)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300,
                        env=dict(os.environ, **env))
     if r.returncode != 0:
@@ -74,6 +94,7 @@ def main():
     a = ap.parse_args()
     n = a.flows + a.packets
     fr, ln, dv, now = NF[a.nf]["trace"](n, a.flows)
+    steady = NF[a.nf]["steady"](n, a.flows)[a.flows:]
     points = []
     if a.sweep:
         for bt in [int(x) for x in a.sweep.split(",")]:
@@ -92,7 +113,7 @@ def main():
             for _ in range(a.repeat):
                 us.append(run_loop(a.tree, a.nf, tin, tout, a.flows, bt, env))
                 out = np.frombuffer(open(tout, "rb").read(), np.uint16, n, 12)
-                assert (out[a.flows:] == 1).all()  # every steady packet out on the WAN port
+                assert (out[a.flows:] == steady).all()  # every steady packet out where expected
             rec = {"nf": a.nf, "label": a.label, "batch": bt, "path": path,
                    "packets": a.packets, "flows": a.flows,
                    "us_per_packet": [round(x, 3) for x in us],

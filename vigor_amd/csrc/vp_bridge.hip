@@ -34,6 +34,7 @@
 #include <cstring>
 #include <vector>
 
+#include "vp_serve_dev.h"
 #include "vp_table.h"
 
 namespace vp {
@@ -381,11 +382,209 @@ __global__ void bridge_defer_finish(BridgeArgs a) {
   }
 }
 
+// ========================================================= one packet ==
+// nf.c calls nf_process once per packet (nf.c:150-176) or once per small
+// burst (its VIGOR_BATCH_SIZE loop, nf.c:178-215). vp_process_one and small
+// vp_process_mbufs calls go to bridge_serve, one wave that stays resident and
+// polls the host-coherent mailbox (ServeBox, vp_internal.h), as nat_serve and
+// fw_serve do for vignat and vigfw: no launch and no copy call per packet.
+// The host sends requests only while no expiry is due (serve_process_one /
+// serve_process_burst), so the kernel restates bridge_main.c:311-329 without
+// the expiry step. The bridge never rewrites a frame and reads only its 12
+// MAC bytes.
+
+// T holds the CRC tables, then the layout's byte tables (kMixLin).
+constexpr uint32_t kBridgeTabWords = kBridgeTabs * 256 + 1024;
+
+// A frame's MACs from its first three words (eth_words' layout).
+struct Macs {
+  uint32_t d0, d1, s0, s1;
+};
+__device__ __forceinline__ Macs macs_of(uint32_t w0, uint32_t w1, uint32_t w2) {
+  return Macs{w0, w1 & 0xFFFF, (w1 >> 16) | (w2 << 16), w2 >> 16};
+}
+
+// The static table's part of bridge_get_device (bridge_main.c:38-47): the
+// rule keyed {dst, in}, dh = eth_hash(dst); *fwd = its device_to.
+__device__ __forceinline__ bool bridge_static(const BridgeArgs &a, const uint32_t *T, uint32_t dh,
+                                              uint32_t d0, uint32_t d1, uint32_t in,
+                                              int32_t *fwd) {
+  if (!a.n_static) return false;
+  const uint32_t key[4] = {d0, d1 | (in << 16), 0, 0};
+  const uint32_t k = tbl_probe(a.st, static_hash(T, dh, in), key);
+  if (k == kNone) return false;
+  *fwd = a.st_val[k];
+  return true;
+}
+
+// bridge_put_update_entry (bridge_main.c:63-89) for src {s0, s1} (hash sh)
+// from port `in` at global sequence seq, without the stamp: the MAC's index
+// -- a known MAC keeps its port; an unknown one takes an index (serve_lan_by)
+// and stores {s0, s1, in, 0} --, or kNone with nothing written when no index
+// is free (bridge_main.c:73-76).
+__device__ __forceinline__ uint32_t bridge_learn(const TableDev &t, uint32_t sh, uint32_t s0,
+                                                 uint32_t s1, uint32_t in, uint64_t seq,
+                                                 uint32_t *fresh) {
+  const uint32_t key[4] = {s0, s1, in, 0};
+  return serve_lan_by(t, sh, key, 0u, seq, fresh, [&] {
+    uint32_t unused = 0;
+    return mac_probe(t, sh, s0, s1, &unused);
+  });
+}
+
+// A burst request (vp_serve_dev.h) for vigbridge. Every packet both learns
+// its src and looks its dst up, so a lane may be pending on both: lpend = its
+// src is unknown, wpend = its dst is unknown and no static rule decides. In
+// burst_settle the lane learns in its own round (lane == m) and looks its dst
+// up in a later one (lane < the next m, or behind the loop), so its lookup
+// sees the learns of the lanes up to and including itself and of no later
+// lane: a frame addressed to its own new src forwards, as learn precedes
+// lookup in bridge_main.c:316-320. A hit of round 0 is final: nothing expires
+// inside a burst and a known MAC's port never changes. Only the learn stamps
+// (bridge_main.c:66-69, 86), so burst_last runs over the src index. Nothing
+// of a frame comes back and no burst is declined.
+__device__ __forceinline__ uint32_t bridge_burst(const BridgeArgs &a, const uint32_t *T,
+                                                 ServeBox *box, uint32_t n, uint64_t seq0,
+                                                 uint32_t lane) {
+  const TableDev &t = a.t;
+  const BurstIn b = burst_load(box, n, lane);
+  const uint32_t in = b.in;
+  const Macs m = macs_of(b.f.w[0], b.f.w[1], b.f.w[2]);
+  uint32_t sh, dh;
+  eth_hash2(T, m.s0, m.s1, m.d0, m.d1, &sh, &dh);
+  // round 0, then the misses in packet order
+  int32_t st_fwd = 0;
+  const bool st_hit = b.act && bridge_static(a, T, dh, m.d0, m.d1, in, &st_fwd);
+  uint32_t si = kNone, di = kNone, port = 0, fresh = 0;
+  if (b.act) {
+    uint32_t unused = 0;
+    si = mac_probe(t, sh, m.s0, m.s1, &unused);
+    if (!st_hit) di = mac_probe(t, dh, m.d0, m.d1, &port);
+  }
+  burst_settle(
+      lane, b.act && si == kNone, b.act && !st_hit && di == kNone,
+      [&] { di = mac_probe(t, dh, m.d0, m.d1, &port); },
+      [&] { si = bridge_learn(t, sh, m.s0, m.s1, in, seq0 + lane, &fresh); });
+  if (burst_last(si, n, lane)) serve_stamp(t, si, b.now, seq0 + lane);
+  const uint32_t out = st_hit ? resolve(st_fwd, in)
+                       : di != kNone ? (port & 0xFFFFu)
+                                     : (uint32_t)VP_FLOOD_FRAME;
+  burst_out(b, (out & 0xFFFFu) | (fresh << 16), n, lane);
+  return kBurstServed;
+}
+
+// The server: one wave (<<<1, 64>>>). Every poll reads the request chunks
+// whole; a one-packet request is chunk 0 and, for a frame of at least one
+// byte, chunk 1 with frame bytes 0-11 (bytes past len read as 0, the runt
+// convention of DESIGN.md 7), which lane 0 takes from lane 1's registers: no
+// LDS copy of the frame. Lane 0 runs the packet: learn the src, then look the
+// dst up (static rules first; the lookup does not stamp). The answer is chunk
+// 0 alone (out | fresh << 16). Packets take global sequence numbers seq0,
+// seq0 + 1, ...; a burst request (bridge_burst) takes as many as it has
+// frames. The kernel leaves on the leave request or after `idle` wall-clock
+// ticks without a request; the host launches it again (serve_wait). flags:
+// serve_poll's.
+__global__ __launch_bounds__(64) void bridge_serve(BridgeArgs a, ServeBox *box, uint64_t seq0,
+                                                   uint64_t idle, uint32_t flags) {
+  __shared__ uint32_t T[kBridgeTabWords];
+  const uint32_t lane = threadIdx.x;
+  for (uint32_t i = lane; i < kBridgeTabs * 256; i += 64) T[i] = a.crc_tab[i];
+  if (a.t.mix == kMixLin) {  // (the layout's byte tables: their LDS copy)
+    for (uint32_t i = lane; i < 1024; i += 64) T[kBridgeTabs * 256 + i] = a.t.lin[i];
+    a.t.lin = T + kBridgeTabs * 256;
+  }
+  __syncthreads();
+  const ServeIo io = serve_io(box, lane);
+  // the last answered request (a relaunched server goes on from the answer
+  // word), the next packet's sequence, the last answer's wall clock
+  uint32_t done = __builtin_amdgcn_readfirstlane((uint32_t)__hip_atomic_load(
+      &box->ans, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM));
+  uint64_t seq = seq0;
+  uint64_t t0 = wall_clock64();
+  auto serve = [&](const v4u &c) -> int {
+    const uint32_t want = done + 1;
+    if (__builtin_amdgcn_readfirstlane(c[3]) != want) return -1;
+    const uint32_t hi = __builtin_amdgcn_readfirstlane(c[0]);
+    if (hi == kServeLeave) return 1;
+    const uint32_t in = hi >> 16;
+    if ((hi & 0xFFFFu) == kServeBurstOp) {  // chunk 0 alone, the frames in the burst body
+      const uint32_t bn = min(max(in, 1u), kServeBurst);
+      const uint32_t st = bridge_burst(a, T, box, bn, seq, lane);
+      if (lane == 0) burst_answer(io, box, st, bn, want);
+      seq += bn;
+      t0 = wall_clock64();
+      done = want;
+      // (every lane's table writes before the next request reads them)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      return 0;
+    }
+    const uint32_t len = min(hi & 0xFFFFu, kServeFrame);
+    const uint32_t got = min(len, 12u);          // frame bytes in chunk 1
+    const uint32_t need = (12 + got + 11) / 12;  // chunks carrying the request
+    if (__ballot(lane < need && c[3] != want)) return -1;  // not whole yet: poll again
+    const int64_t now = serve_now(c);
+    const uint4 h = chunk_keep(make_uint4((uint32_t)__builtin_amdgcn_readlane((int)c[0], 1),
+                                          (uint32_t)__builtin_amdgcn_readlane((int)c[1], 1),
+                                          (uint32_t)__builtin_amdgcn_readlane((int)c[2], 1), 0u),
+                               0, (int)got);
+    uint32_t res = 0;
+    if (lane == 0) {
+      const Macs m = macs_of(h.x, h.y, h.z);
+      uint32_t sh, dh;
+      eth_hash2(T, m.s0, m.s1, m.d0, m.d1, &sh, &dh);
+      uint32_t fresh = 0;
+      const uint32_t si = bridge_learn(a.t, sh, m.s0, m.s1, in, seq, &fresh);
+      if (si != kNone) serve_stamp(a.t, si, now, seq);
+      int32_t fwd = 0;
+      uint32_t out;
+      if (bridge_static(a, T, dh, m.d0, m.d1, in, &fwd)) {
+        out = resolve(fwd, in);
+      } else {  // (after the learn: a frame to its own new src forwards)
+        uint32_t port = 0;
+        const uint32_t di = mac_probe(a.t, dh, m.d0, m.d1, &port);
+        out = di != kNone ? (port & 0xFFFFu) : (uint32_t)VP_FLOOD_FRAME;
+      }
+      res = (out & 0xFFFFu) | (fresh << 16);
+    }
+    res = __builtin_amdgcn_readfirstlane(res);
+    if (lane == 0) {
+      __builtin_amdgcn_raw_buffer_store_b128((v4u){res, 0u, 0u, want}, io.as, 0, 0, kSys);
+      // (the answer word: where a relaunched server starts counting; the host
+      // reads the answer chunk. No release fence at system scope, which would
+      // write back the whole L2)
+      __hip_atomic_store(&box->ans, (uint64_t)want | ((uint64_t)res << 32), __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    seq += 1;
+    t0 = wall_clock64();
+    done = want;
+    // (lane 0's table writes before the next request's lanes read them)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    return 0;
+  };
+  serve_poll(io, flags, idle, serve, [&] { return t0; });
+}
+
 // =============================================================== host ==
 
 static inline int64_t bridge_cutoff(const vp_ctx *c, int64_t t) {
   const uint32_t e = c->brg.expiration_time * 1000u;  // u32, as vignat
   return (int64_t)((uint64_t)t - e);
+}
+
+// The tables every bridge kernel reads: the dynamic table as it is now, the
+// static table and the CRC tables.
+static void bridge_tables(vp_ctx *c, BridgeArgs *a) {
+  a->t = tbl_dev(c->ft);
+  a->st = TableDev{};
+  a->st.bk = c->st_bk;
+  a->st.bmask = c->st_bmask;
+  a->st.mix = kMixMul;
+  a->st_val = c->st_val;
+  a->n_static = c->n_static;
+  a->crc_tab = c->crc_tab;
 }
 
 static int bridge_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
@@ -402,14 +601,7 @@ static int bridge_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   a.slot = b->slot;
   a.p0 = p0;
   a.p1 = p1;
-  a.t = tbl_dev(t);
-  a.st = TableDev{};
-  a.st.bk = c->st_bk;
-  a.st.bmask = c->st_bmask;
-  a.st.mix = kMixMul;
-  a.st_val = c->st_val;
-  a.n_static = c->n_static;
-  a.crc_tab = c->crc_tab;
+  bridge_tables(c, &a);
   a.miss = w.miss;
   a.defer = w.defer;
 
@@ -481,6 +673,35 @@ static int bridge_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
 int bridge_process_device(vp_ctx *c, const vp_dev_batch *b) {
   ExpiringTable tabs[1] = {{&c->ft, bridge_cutoff}};
   return run_batch(c, b, tabs, 1, bridge_segment);
+}
+
+// ---------------------------------------------------- vp_process_one --
+// vigbridge's launcher of the resident kernel (serve_launch, vp_serve.hip).
+int bridge_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
+  BridgeArgs a{};
+  bridge_tables(c, &a);
+  bridge_serve<<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags);
+  VP_HIP(hipGetLastError());
+  return 0;
+}
+
+// The largest host batch routed to the server as burst requests: the largest
+// swept n at which the served path measured faster per packet than the batch
+// pipeline on the MI355X (profiles/r10_bridge_serve.txt: 0.14 against 0.24 us
+// at 256, 0.14 against 0.18 at 384, 0.139 against 0.137 at 512); larger calls
+// take the pipeline. Above vignat's and vigfw's 256: a served vigbridge burst
+// copies 16 bytes a frame in and none back. VIGPATH_SERVE_BURST overrides it;
+// 0 routes nothing.
+constexpr uint32_t kBridgeBurstRoute = 384;
+
+// vigbridge through the mailbox (serve_process_one / serve_process_burst,
+// vp_serve.hip): bridge_serve reads a frame's 12 MAC bytes and changes none,
+// so one packet sends 12 bytes and takes none back; a burst copies a frame's
+// first 16 bytes in and nothing back. No stage clock.
+const ServeNf &bridge_serve_nf() {
+  static const ServeNf nf = {bridge_cutoff, &vp_ctx::ft, false, 12, 0, 16, 0, kBridgeBurstRoute,
+                             false};
+  return nf;
 }
 
 void build_bridge_tables(std::vector<uint32_t> &tab) {

@@ -739,7 +739,8 @@ constexpr uint32_t kFwBurstRoute = 256;
 // takes back bytes 0-11; fw_burst reads a frame's first 64 bytes and 16 come
 // back.
 const ServeNf &fw_serve_nf() {
-  static const ServeNf nf = {fw_cutoff, &vp_ctx::ft, false, 64, 16, kFwBurstRoute, false};
+  static const ServeNf nf = {fw_cutoff, &vp_ctx::ft, false, kServeInline, 12, 64, 16,
+                             kFwBurstRoute, false};
   return nf;
 }
 

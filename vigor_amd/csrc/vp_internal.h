@@ -345,8 +345,8 @@ struct HostMap {
 };
 constexpr int kMaxHostMaps = 16;
 
-// vp_process_one's mailbox (nat_serve, vp_nat.hip; fw_serve, vp_fw.hip; its
-// host side in vp_serve.hip): page-locked, host-coherent
+// vp_process_one's mailbox (nat_serve, vp_nat.hip; fw_serve, vp_fw.hip;
+// bridge_serve, vp_bridge.hip; its host side in vp_serve.hip): page-locked, host-coherent
 // memory the host and a persistent one-wave kernel poll. The host writes the
 // request (below); the kernel writes the rewritten frame to `frame`, then
 // sets the answer word.
@@ -428,24 +428,32 @@ inline void serve_unpack(const ServeBox *bx, uint8_t *frame, uint32_t back) {
 }
 
 // What of a served NF the mailbox's host side needs to know (nat_serve_nf,
-// vp_nat.hip; fw_serve_nf, vp_fw.hip).
+// vp_nat.hip; fw_serve_nf, vp_fw.hip; bridge_serve_nf, vp_bridge.hip).
 struct ServeNf {
   // the table whose entries expire and the cutoff for a packet at time t: a
   // request is sent only while no expiry is due
   int64_t (*cutoff)(const vp_ctx *c, int64_t t);
   FlowTable vp_ctx::*table;
-  // one packet: the whole frame goes and comes back, one longer than
-  // kServeInline through `frame`; else its first kServeInline bytes go and
-  // bytes 0-11 (answer chunk 1) come back
+  // one packet: a frame longer than kServeInline goes whole through `frame`
+  // and comes back there (vignat: the checksums cover it); else only the
+  // request's chunks carry it
   bool one_whole;
+  // one packet through the chunks: the most frame bytes that go (what the
+  // kernel reads: kServeInline, vigbridge's 12 MAC bytes) and that come back
+  // in the answer chunks (what it can change: all, vigfw's MACs, none)
+  uint32_t one_in, one_back;
   uint32_t burst_in, burst_back;  // a burst's frame: the most bytes in, and back
   uint32_t burst_route;           // the largest host batch routed as burst requests
   bool prof;                      // VIGPATH_SERVE_PROF's stage clock (nat_serve's)
 };
 const ServeNf &nat_serve_nf();
 const ServeNf &fw_serve_nf();
+const ServeNf &bridge_serve_nf();
 inline const ServeNf *serve_nf(int kind) {  // (nullptr: the NF has no resident kernel)
-  return kind == KIND_NAT ? &nat_serve_nf() : kind == KIND_FW ? &fw_serve_nf() : nullptr;
+  return kind == KIND_NAT      ? &nat_serve_nf()
+         : kind == KIND_FW     ? &fw_serve_nf()
+         : kind == KIND_BRIDGE ? &bridge_serve_nf()
+                               : nullptr;
 }
 // One packet through the persistent kernel (one GPU, no expiry due): 0 done;
 // 1 not eligible (the caller takes the batch path, the server is stopped);
@@ -481,6 +489,7 @@ uint32_t serve_burst_limit(uint32_t dflt);
 // the ticks a late poll adds (serve_poll, vp_serve_dev.h).
 int nat_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
 int fw_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
+int bridge_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
 
 }  // namespace vp
 

@@ -3219,7 +3219,8 @@ constexpr uint32_t kServeBurstRoute = 256;
 // than kServeInline through `frame`; of a burst's frame all bytes go (the L4
 // checksum's) and the first 64 come back. The stage clock is vignat's.
 const ServeNf &nat_serve_nf() {
-  static const ServeNf nf = {nat_cutoff, &vp_ctx::ft, true, kServeFrame, 64, kServeBurstRoute, true};
+  static const ServeNf nf = {nat_cutoff, &vp_ctx::ft, true, kServeInline, kServeInline,
+                             kServeFrame, 64, kServeBurstRoute, true};
   return nf;
 }
 

@@ -1,6 +1,6 @@
 // vp_process_one's mailbox, host side (ServeBox, vp_internal.h), for any
-// context whose NF has a resident kernel -- vignat (nat_serve, vp_nat.hip) and
-// vigfw (fw_serve, vp_fw.hip). Launching the kernel, waiting for an answer,
+// context whose NF has a resident kernel -- vignat (nat_serve, vp_nat.hip),
+// vigfw (fw_serve, vp_fw.hip) and vigbridge (bridge_serve, vp_bridge.hip). Launching the kernel, waiting for an answer,
 // relaunching after an idle exit, stopping it before any other entry point
 // touches the table, yielding the GPU's hardware queues between contexts, and
 // the requests themselves: one packet (serve_process_one) and a small burst
@@ -136,6 +136,9 @@ static int serve_launch(vp_ctx *c) {
     case KIND_FW:
       VP_TRY(fw_serve_launch(c, dbox, flags));
       break;
+    case KIND_BRIDGE:
+      VP_TRY(bridge_serve_launch(c, dbox, flags));
+      break;
     default:
       return state_fail("no resident kernel for NF kind %d", c->kind);
   }
@@ -256,18 +259,18 @@ int serve_process_one(vp_ctx *c, const ServeNf &nf, uint16_t in_dev, uint8_t *fr
   const bool prof = nf.prof && serve_prof();
   const auto h0 = prof ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
   // the request: a frame longer than the chunks hold goes whole through
-  // `frame` before them and comes back there, or only its first kServeInline
-  // bytes go (nf.one_whole)
+  // `frame` before them and comes back there (nf.one_whole), or only its
+  // first nf.one_in bytes go
   const uint32_t req = ++c->srv_req;
   const bool via_frame = nf.one_whole && len > kServeInline;
-  const uint32_t got = via_frame ? 0u : std::min<uint32_t>(len, kServeInline);
+  const uint32_t got = via_frame ? 0u : std::min<uint32_t>(len, nf.one_in);
   if (via_frame) memcpy(bx->frame, frame, len);
   uint32_t m[3 * kServeChunks];
   const uint32_t need = serve_pack(m, len | ((uint32_t)in_dev << 16), now, frame, got);
   serve_post(bx, m, need, req);
   // the answer: chunk 0, and the chunks that bring the frame bytes back -- as
-  // many as the request took, or chunk 1 alone (bytes 0-11)
-  const uint32_t back = nf.one_whole ? got : std::min(got, 12u);
+  // many as the request took, chunk 1 alone (bytes 0-11), or none
+  const uint32_t back = std::min(got, nf.one_back);
   VP_TRY(serve_wait(c, req, 1 + (back + 11) / 12));
   const uint32_t res = bx->amsg[0][0];  // out | fresh << 16
   if (via_frame)

@@ -1,5 +1,6 @@
 // vp_process_one's mailbox, device side (ServeBox, vp_internal.h): what the
-// resident kernels nat_serve (vp_nat.hip) and fw_serve (vp_fw.hip) share --
+// resident kernels nat_serve (vp_nat.hip), fw_serve (vp_fw.hip) and
+// bridge_serve (vp_bridge.hip) share --
 // the poll loop, the chunks of a one-packet request, a burst's load, header
 // tests, settle loop, stamp winner and answer words, and the allocate-and-
 // insert of a new LAN flow. What a flow's key is, how a WAN packet finds its
@@ -20,11 +21,16 @@ constexpr int kSys = 17;  // sc0 | sc1: system-coherent (bypasses the GPU caches
 // then the never-used range) with `key` stored, its last word as k3 (vigfw
 // keeps int_devices in the padding bytes); kNone with nothing written when no
 // index is free. The caller stamps the index (serve_stamp).
-template <uint32_t M3>
-__device__ __forceinline__ uint32_t serve_lan(const TableDev &t, uint32_t hh,
-                                              const uint32_t key[4], uint32_t k3, uint64_t seq,
-                                              uint32_t *fresh) {
-  uint32_t idx = tbl_probe<M3>(t, hh, key);
+//
+// serve_lan_by: the same with the lookup as a parameter, for a table whose
+// match is not tbl_probe's (vigbridge: words 0-1 identify the MAC, word 2 is
+// the learned port, vp_bridge.hip mac_probe); probe() returns the key's index
+// or kNone.
+template <class Probe>
+__device__ __forceinline__ uint32_t serve_lan_by(const TableDev &t, uint32_t hh,
+                                                 const uint32_t key[4], uint32_t k3,
+                                                 uint64_t seq, uint32_t *fresh, Probe probe) {
+  uint32_t idx = probe();
   if (idx != kNone) return idx;
   Ctl *c = t.ctl;
   const uint32_t st = c->stack_top, fn = c->fresh_next;
@@ -50,6 +56,12 @@ __device__ __forceinline__ uint32_t serve_lan(const TableDev &t, uint32_t hh,
   t.birth[idx] = seq;
   *fresh = 1;
   return idx;
+}
+template <uint32_t M3>
+__device__ __forceinline__ uint32_t serve_lan(const TableDev &t, uint32_t hh,
+                                              const uint32_t key[4], uint32_t k3, uint64_t seq,
+                                              uint32_t *fresh) {
+  return serve_lan_by(t, hh, key, k3, seq, fresh, [&] { return tbl_probe<M3>(t, hh, key); });
 }
 
 // The touch of index idx at (now, seq), right behind the lookup: stamped
@@ -184,7 +196,11 @@ __device__ __forceinline__ BurstHdr burst_hdr(const BurstIn &b) {
 // inserted its key) and allocates as a packet of its own would (lan_alloc:
 // serve_lan, kNone when no index is free); a pending WAN lane below m has
 // every flow born before it in the table and is final, hit or drop, once it
-// has looked again (wan_again). At most one round per lane.
+// has looked again (wan_again). At most one round per lane. A lane may be
+// pending on both (vigbridge: every packet learns its src and looks its dst
+// up): as lane m it allocates and stays a pending WAN lane, which looks again
+// below the next m or behind the loop -- after its own insert and before any
+// later lane's.
 template <class WanAgain, class LanAlloc>
 __device__ __forceinline__ void burst_settle(uint32_t lane, bool lpend, bool wpend,
                                              WanAgain wan_again, LanAlloc lan_alloc) {
