@@ -16,7 +16,8 @@ import os
 import numpy as np
 
 import orc
-from tracegen import mixed_fw_trace, mixed_nat_trace, mixed_pol_trace
+from tracegen import (edge_lb_trace, mixed_fw_trace, mixed_nat_trace, mixed_pol_trace,
+                      wide_lb_trace)
 from vigor_amd import traces as T
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
@@ -187,6 +188,26 @@ def lb_trace(ref, seed, fexp, bexp):
     return res
 
 
+def lb_shape_trace(ref, shape, seed, fexp, bexp):
+    """viglb over 256-byte slots: wide_lb_trace (payload bytes under the L4
+    sum, odd and padded lengths) or edge_lb_trace (options, short frames,
+    total_length edges; WAN packets and heartbeats alike)."""
+    rng = np.random.default_rng(seed)
+    slot = 256
+    if shape == "wide":
+        fr, ln, dv, now = wide_lb_trace(rng, 3000, 200, 12, slot, max_len=slot)
+    else:
+        fr, ln, dv, now = edge_lb_trace(rng, 3000, 100, 12, slot, long_frames=True)
+    now = T.NOW0 + (now - T.NOW0) * 10  # (2 us: some 200 packets)
+    o = orc.Oracle("lb", lb_cfg(fexp=fexp, bexp=bexp), ref=ref)
+    f = fr.copy()
+    out = o.run(f, ln, dv, now, slot)
+    res = [out, f ^ fr]
+    for x in o.lb_dump(1024, 32):
+        res += [x[0], *_live(x[0], *x[1:])]
+    return res
+
+
 def fw_oracle(ref, max_flows=64, expire_us=60_000_000, n_dev=3, wan=1):
     cfg = orc.fw_cfg(wan=wan, expire_us=expire_us, max_flows=max_flows,
                      device_macs=DEV3_MACS[:n_dev], endpoint_macs=END3_MACS[:n_dev],
@@ -224,11 +245,12 @@ CASES = {
     "crc": (crc, [()]),
     "dchain": (dchain, [(s,) for s in range(6)]),
     "map": (map_, [(s,) for s in range(6)]),
-    "cht": (cht, [(97, 32), (257, 256), (7, 4), (13, 1)]),
+    "cht": (cht, [(97, 32), (257, 256), (7, 4), (13, 1), (521, 512)]),
     "nat": (nat_trace, [(0, 64, 60_000_000, 40), (1, 64, 1, 100),
                         (2, 16, 60_000_000, 40), (3, 256, 5, 300)]),
     "bridge": (bridge_trace, [(0, 64, 300_000_000), (1, 16, 2), (2, 1024, 10)]),
     "lb": (lb_trace, [(0, 60_000_000, 3_600_000_000), (1, 3, 50), (2, 20, 2)]),
+    "lb_shape": (lb_shape_trace, [("wide", 10, 2, 3_600_000), ("edge", 11, 60_000_000, 2)]),
     "fw": (fw_trace, [(0, 64, 60_000_000, 40), (1, 64, 1, 100),
                       (2, 16, 60_000_000, 40), (3, 256, 5, 300)]),
     "pol": (pol_trace, [(0, 64, 40, 3000, 500), (1, 16, 60, 1000, 2000),

@@ -4,13 +4,17 @@ flow and backend state).
 Every test calls the product through the C-ABI (libvigpath.so via
 vigor_amd); the oracle (oracle/liborc.so) is only the checker.
 """
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
 import orc
 import vigor_amd
 from gpuh import check_batches, run_gpu
-from tracegen import mixed_lb_trace
+from tracegen import edge_lb_trace, mixed_lb_trace, wide_lb_trace
 from vigor_amd import traces as T
 
 pytestmark = pytest.mark.gpu
@@ -144,3 +148,85 @@ def test_stale_frees_keep_shard_count():
         assert st["shard_live"] == st["live"], (c, st)
     check_state(lb, o)
     assert lb.table_stats(0)["rebuilds"] <= 4, lb.table_stats(0)
+
+
+@pytest.mark.parametrize("slot,max_len", [(80, 80), (128, 128), (256, 256), (1536, 1518),
+                                          (2048, 1518)])
+def test_wide_slots(slot, max_len):
+    """Frames of 60..1518 bytes in wide slots (lb_classify, set_checksums'
+    raw_sum over real payload): TCP and UDP, odd lengths, frames padded past
+    total_length, heartbeats mixed in, malformed frames, flows that expire
+    and return; several batches, one cut at packet 1."""
+    rng = np.random.default_rng(slot)
+    fr, ln, dv, now = wide_lb_trace(rng, 3000, 200, 12, slot, max_len=max_len)
+    now = T.NOW0 + (now - T.NOW0) * 5
+    lb, o = make_pair(flow_cap=256, fexp=1)  # (1 us: some 200 packets of the trace)
+    check_batches(lb, o, fr, ln, dv, now, slot, [1, 700, 2100])
+    assert (o.lb_dump(256, 32)[0][0] == 1).sum() < 200  # (some flows are gone)
+    check_state(lb, o)
+
+
+@pytest.mark.parametrize("slot,long_frames", [(64, False), (128, False), (256, True)])
+def test_header_edge_cases(slot, long_frames):
+    """edge_lb_trace: IPv4 options (a TCP checksum as far out as bytes 90-91),
+    IHL < 5, total_length below 20 and past the frame, frames shorter than
+    their headers or than 14 bytes, on WAN packets and heartbeats. In 64-byte
+    slots they take the tile kernel's byte path (LbPend.kind 1), in wide slots
+    parse_l34."""
+    rng = np.random.default_rng(100 + slot)
+    fr, ln, dv, now = edge_lb_trace(rng, 3000, 100, 12, slot, long_frames=long_frames)
+    now = T.NOW0 + (now - T.NOW0) * 10
+    lb, o = make_pair(flow_cap=256, bexp=1)  # (1 us: some 100 packets of the trace)
+    check_batches(lb, o, fr, ln, dv, now, slot, [1, 900])
+    if slot == 64:
+        assert lb.last_kernel().startswith("lb_classify64"), lb.last_kernel()
+    check_state(lb, o)
+
+
+def beyond_the_lds_stage(want_kernel):
+    """bcap 512 (above kLbLdsBackends: the tile kernel stages no backend in
+    LDS), CHT height 521: 400 heartbeats, 2000 flows twice (the second batch
+    all hits: lb_flow_found -> lb_rewrite_fast reads be_rec from global
+    memory), then the backends expire, the flows go stale, and heartbeats
+    and traffic come again."""
+    nb, nfl, bexp_us = 400, 2000, 1000
+    lb, o = make_pair(flow_cap=4096, bcap=512, height=521, bexp=bexp_us)
+    hb = T.lb_heartbeats(nb)
+    tr = T.lb_traffic(nfl, nfl)
+    t1 = T.NOW0 + 5 * bexp_us * 1000  # (every backend has expired)
+    at = lambda t: (t + np.arange(nfl, dtype=np.int64),)  # noqa: E731
+    segs = [hb, tr, tr[:3] + at(T.NOW0 + 10_000),
+            tr[:3] + at(t1),                       # no backend alive: dropped, erased
+            T.lb_heartbeats(nb // 2, t0=t1 + 5_000),
+            tr[:3] + at(t1 + 10_000), tr[:3] + at(t1 + 20_000)]
+    for k, (fr, ln, dv, now) in enumerate(segs):
+        exp = fr.copy()
+        exp_out = o.run(exp, ln, dv, now, 64)
+        got, out = run_gpu(lb, fr, ln, dv, now, 64)
+        np.testing.assert_array_equal(out, exp_out, "out ports, segment %d" % k)
+        np.testing.assert_array_equal(got, exp, "frames, segment %d" % k)
+        assert lb.last_kernel() == want_kernel, lb.last_kernel()
+        if k == 2:  # the all-hit batch: forwarded, and to backends past 255
+            assert (exp_out != 2).all()
+            (fa, _, _, fb), _ = o.lb_dump(4096, 512)
+            assert ((fa == 1) & (fb >= 256)).sum() >= 100
+        if k == 3:
+            assert (exp_out == 2).all()
+    check_state(lb, o)
+
+
+def test_backends_beyond_the_lds_stage():
+    beyond_the_lds_stage("lb_classify64")
+
+
+def test_backends_beyond_the_lds_stage_16_waves():
+    """The same through lb_classify64w (VIGPATH_LB_WAVES=16, read once per
+    process: a fresh child)."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, VIGPATH_LB_WAVES="16")
+    env["PYTHONPATH"] = os.pathsep.join([root, os.path.join(root, "tests")] +
+                                        [p for p in [env.get("PYTHONPATH")] if p])
+    code = "import test_lb_gpu as M; M.beyond_the_lds_stage('lb_classify64w'); print('CHILD OK')"
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0 and "CHILD OK" in r.stdout, (r.stdout[-1000:], r.stderr[-2000:])

@@ -9,8 +9,8 @@ bytes past each length zero: the mbuf path reads them as 0)."""
 import numpy as np
 import pytest
 import orc
-from tracegen import (edge_nat_trace, mixed_bridge_trace, mixed_fw_trace,
-                      mixed_lb_trace, mixed_pol_trace, wide_nat_trace)
+from tracegen import (edge_lb_trace, edge_nat_trace, mixed_bridge_trace, mixed_fw_trace,
+                      mixed_lb_trace, mixed_pol_trace, wide_lb_trace, wide_nat_trace)
 from vigor_amd import traces as T
 
 import test_nat_gpu as NG
@@ -156,6 +156,49 @@ def test_nat_pool_not_registered():
     pool, bufs, ptrs = to_pool(fr, ln, SLOT, rng)
     out = run_mbufs(nat, pool, ptrs, ln, dv, now, register=False)
     compare(pool, bufs, ln, exp, exp_out, out, SLOT)
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_lb_long_frames(mode, monkeypatch):
+    """viglb's whole-frame slots with frames of 60-1518 bytes (mbuf_gather_full
+    sizes the slot to the chunk's longest frame): payload under the L4 sum,
+    odd and padded lengths, about 5 % of the frames at a data offset that is
+    no multiple of 16, edge_lb_trace frames (options, short frames) mixed in,
+    and TCP frames under IHL 15, whose checksum at bytes 90-91 is the farthest
+    byte the write-back (128 bytes) has to carry."""
+    import test_lb_gpu as LG
+    monkeypatch.setenv("VIGPATH_HOST_CHUNK", "700")
+    monkeypatch.setenv("VIGPATH_MBUF_MODE", mode)
+    rng = np.random.default_rng(46)
+    n = 3000
+    fr, ln, dv, now = wide_lb_trace(rng, n, 200, 12, SLOT)
+    ef, el, ed, _ = edge_lb_trace(rng, n, 200, 12, SLOT, long_frames=True)
+    F, EF = fr.reshape(n, SLOT), ef.reshape(n, SLOT)
+    mix = rng.random(n) < 0.1
+    F[mix], ln[mix], dv[mix] = EF[mix], el[mix], ed[mix]
+    # 40 option bytes under plain WAN TCP frames: the L4 header moves to 74
+    deep = np.nonzero(~mix & (dv == 2) & (F[:, 12] == 8) & (F[:, 14] == 0x45) & (F[:, 23] == 6) &
+                      (ln >= 160) & (F[:, 16] < 0xFF))[0][::4]
+    for i in deep:
+        F[i, 74:] = F[i, 34:SLOT - 40].copy()
+        F[i, 34:74] = rng.integers(0, 256, 40, dtype=np.uint8)
+        F[i, 14] = 0x4F
+    zero_past_len(fr, ln, SLOT)
+    shift = np.zeros(n, np.int64)
+    shift[rng.random(n) < 0.05] = 3
+    lb, o = LG.make_pair(flow_cap=256, fexp=2)
+    exp = fr.copy()
+    exp_out = o.run(exp, ln, dv, now, SLOT)
+    E = exp.reshape(n, SLOT)
+    far = [i for i in deep if exp_out[i] != 2 and (E[i, 90:92] != F[i, 90:92]).any()]
+    assert len(far) >= 20, len(far)  # (rewritten past byte 64)
+    pool = T.MbufPool(int(n * 1.3) + 1)
+    bufs = rng.permutation(pool.n)[:n]
+    pool.put(bufs, fr, SLOT, ln, shift)
+    out = run_mbufs(lb, pool, pool.ptrs(bufs, shift), ln, dv, now)
+    compare(pool, bufs, ln, exp, exp_out, out, SLOT, shift)
+    assert (exp_out[dv == 2] != 2).sum() > 2000  # (forwarded WAN packets)
+    LG.check_state(lb, o)
 
 
 def _other(kind):

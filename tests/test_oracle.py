@@ -146,7 +146,7 @@ def test_map_matches_reference(seed):
     OC.check("map", seed)
 
 
-@pytest.mark.parametrize("height,cap", [(97, 32), (257, 256), (7, 4), (13, 1)])
+@pytest.mark.parametrize("height,cap", [(97, 32), (257, 256), (7, 4), (13, 1), (521, 512)])
 def test_cht_matches_reference(height, cap):
     OC.check("cht", height, cap)
 
@@ -172,6 +172,19 @@ def test_bridge_trace_matches_reference(seed, cap, expire_us):
                                             (1, 3, 50), (2, 20, 2)])
 def test_lb_trace_matches_reference(seed, fexp, bexp):
     OC.check("lb", seed, fexp, bexp)
+
+
+@pytest.mark.parametrize("shape,seed,fexp,bexp", [("wide", 10, 2, 3_600_000),
+                                                  ("edge", 11, 60_000_000, 2)])
+def test_lb_wide_and_edge_traces_match_reference(shape, seed, fexp, bexp):
+    """viglb in 256-byte slots (wide_lb_trace: flows expire and return;
+    edge_lb_trace: backends expire and are learned again, from heartbeats
+    with options too): the restatement's lb logic on the shapes the GPU is
+    compared with it on."""
+    out, rewritten = OC.check("lb_shape", shape, seed, fexp, bexp)[:2]
+    assert rewritten.reshape(-1, 256).any(axis=1).sum() > 300  # (forwarded frames)
+    if shape == "edge":  # frames with IPv4 options among them
+        assert (rewritten.reshape(-1, 256)[:, 38:].any(axis=1)).sum() > 20
 
 
 # ---------------------------------------------------------------- vigfw --

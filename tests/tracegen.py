@@ -295,3 +295,314 @@ def wide_nat_trace(rng, n, n_flows, slot, max_len=1518, wan_frac=0.25,
     frames[big, 16] = 0xFF  # total_length past the packet: dropped
     now = T.NOW0 + np.cumsum(rng.integers(0, 3, n))
     return frames.reshape(-1), lens, in_dev, now.astype(np.int64)
+
+
+def _lb_src_macs(rng, frames, be):
+    """Source MACs as mixed_lb_trace sets them: 02:be:<backend>:<random>."""
+    n = frames.shape[0]
+    frames[:, 6:8] = [0x02, 0xBE]
+    frames[:, 8] = (be >> 8) & 0xFF
+    frames[:, 9] = be & 0xFF
+    frames[:, 10:12] = rng.integers(0, 256, (n, 2), dtype=np.uint8)
+
+
+def wide_lb_trace(rng, n, n_flows, n_backends, slot, max_len=1518, hb_frac=0.05,
+                  bad_frac=0.03, pad_frac=0.1, wan=2, quiet=None):
+    """viglb's counterpart of wide_nat_trace: WAN traffic over n_flows (TCP
+    and UDP) with heartbeats from n_backends addresses on ports 0/1 mixed in
+    (none inside the packet window `quiet`), frame lengths uniform in [60,
+    min(slot, max_len)] (odd ones included), random payload bytes with the UDP
+    length field consistent, some frames padded past total_length, a few
+    malformed frames (not IPv4, IHL 6, total_length past the frame). Monotone
+    time with ties."""
+    top = min(slot, max_len)
+    fl = rng.integers(0, n_flows, n)
+    sip = T.ip4(11, 1, 0, 0) + fl
+    dip = T.ip4(10, 9, 8, 7) + (fl % 3)
+    sp = 2000 + fl % 11
+    dp = np.full(n, 443)
+    proto = np.where(fl % 3 == 0, 6, 17)
+    hb = rng.random(n) < hb_frac
+    if quiet is not None:
+        hb[quiet[0]:quiet[1]] = False
+    be = rng.integers(0, n_backends, n)
+    sip = np.where(hb, T.ip4(192, 168, 0, 0) + be, sip)
+    lens = rng.integers(60, top + 1, n).astype(np.uint16)
+    frames = rng.integers(0, 256, (n, slot), dtype=np.uint8)
+    for p_ in (6, 17):
+        m = proto == p_
+        f, _ = T.udp_frames(sip[m], dip[m], sp[m], dp[m], slot=slot, proto=p_)
+        frames[m, :38] = f.reshape(-1, slot)[:, :38]
+    tl = lens.astype(np.int64) - 14
+    pad = rng.random(n) < pad_frac  # total_length short of the frame
+    tl[pad] = np.maximum(20, tl[pad] - rng.integers(1, 40, int(pad.sum())))
+    frames[:, 16] = (tl >> 8).astype(np.uint8)
+    frames[:, 17] = (tl & 0xFF).astype(np.uint8)
+    udp = proto == 17
+    ul = tl[udp] - 20
+    frames[udp, 38] = (ul >> 8).astype(np.uint8)
+    frames[udp, 39] = (ul & 0xFF).astype(np.uint8)
+    _lb_src_macs(rng, frames, be)
+    in_dev = np.where(hb, be & 1, wan).astype(np.uint16)
+    bad = rng.random(n)
+    frames[bad < bad_frac / 3, 12] = 0x86
+    frames[(bad >= bad_frac / 3) & (bad < 2 * bad_frac / 3), 14] = 0x46
+    big = (bad >= 2 * bad_frac / 3) & (bad < bad_frac)
+    frames[big, 16] = 0xFF  # total_length past the packet: dropped
+    now = T.NOW0 + np.cumsum(rng.integers(0, 3, n))
+    return frames.reshape(-1), lens, in_dev, now.astype(np.int64)
+
+
+def edge_lb_trace(rng, n, n_flows, n_backends, slot, long_frames=False,
+                  hb_frac=0.15, wan=2):
+    """viglb's counterpart of edge_nat_trace (nf-util.h:116-162): IHL 0-15
+    with dirty option bytes, total_length below 20, equal to the frame and
+    beyond it, lengths 0-63 (below 14 too), protocols 6, 17 and 1, a non-IPv4
+    ethertype; WAN packets and heartbeats alike (lb_main.c learns a backend
+    from any heartbeat whose headers parse). Monotone time with ties."""
+    fl = rng.integers(0, n_flows, n)
+    be = rng.integers(0, n_backends, n)
+    hb = rng.random(n) < hb_frac
+    frames = np.zeros((n, slot), np.uint8)
+    lens = np.zeros(n, np.uint16)
+    maxlen = min(slot, 1514 if long_frames else slot)
+    for i in range(n):
+        ihl = 5 if rng.random() < 0.6 else int(rng.integers(0, 16))
+        proto = int(rng.choice([6, 17, 17, 1]))
+        flen = int(rng.integers(14, maxlen + 1)) if rng.random() < 0.7 else \
+            int(rng.integers(0, 64))
+        f = frames[i]
+        f[:slot] = rng.integers(0, 256, slot, dtype=np.uint8)  # dirty bytes
+        f[12:14] = (8, 0) if rng.random() < 0.95 else (0x86, 0xDD)
+        f[14] = 0x40 | ihl
+        tl = max(0, flen - 14) if rng.random() < 0.7 else \
+            int(rng.integers(0, 2 * maxlen))
+        f[16:18] = (tl >> 8, tl & 0xFF)
+        f[23] = proto
+        if hb[i]:
+            b = int(be[i])
+            f[26:30] = (192, 168, (b >> 8) & 0xFF, b & 0xFF)
+        else:
+            k = int(fl[i])
+            f[26:30] = (11, 2, (k >> 8) & 0xFF, k & 0xFF)
+        f[30:34] = (10, 9, 8, 7 + int(fl[i]) % 3)
+        l4 = 14 + 4 * max(ihl, 5)
+        if l4 + 4 <= slot:
+            f[l4:l4 + 4] = (7, 208 + int(fl[i]) % 11, 0, 80)
+        lens[i] = flen
+    _lb_src_macs(rng, frames, be)
+    in_dev = np.where(hb, be & 1, wan).astype(np.uint16)
+    now = T.NOW0 + np.cumsum(rng.integers(0, 3, n))
+    return frames.reshape(-1), lens, in_dev, now.astype(np.int64)
+
+
+# ------------------------------------------------- checksum value edges --
+# The values at which nf_set_rte_ipv4_udptcp_checksum's arithmetic branches
+# (DPDK 20.08 rte_ip.h): a frame's label is an index into EDGES, -1 for none.
+# Sums and stored values are the host-order (little-endian) 16-bit words the
+# code adds and stores: "stored 0x0001" is the bytes 01 00.
+EDGES = ("l4_zero",   # L4 sum 0xFFFF: stored 0xFFFF by the zero rule
+         "l4_0001",   # L4 sum 0xFFFE: stored 0x0001
+         "l4_fffe",   # L4 sum 0x10000: stored 0xFFFE
+         "ip_zero",   # IP header sum 0xFFFF: stored 0x0000
+         "ip_0001",   # IP header sum 0xFFFE: stored 0x0001
+         "ip_fffe",   # IP header sum 0x10000 (the second fold): stored 0xFFFE
+         "fold2")     # 32-bit raw L4 sum whose first fold carries
+
+
+def _l4_cksum_at(f, l4):
+    return l4 + (16 if f[23] == 6 else 6)
+
+
+def _be16_at(f, o):
+    return (int(f[o]) << 8) | int(f[o + 1])
+
+
+def _le16_at(f, o):
+    return int(f[o]) | (int(f[o + 1]) << 8)
+
+
+def cksum_edge_frames(fresh, frames, lens, in_dev, now, slot, labels, at):
+    """The trace with its labelled frames patched so that their *rewritten*
+    forms land on the labelled checksum edge. fresh() returns a new oracle of
+    the NF; at[i] is the offset of frame i's spare payload word (even, past
+    the L4 header, inside total_length). Two passes: the oracle runs over the
+    trace with the two spare 16-bit fields (IPv4 identification, the payload
+    word) zero; what it stores as the L4 / IP checksum of a rewritten frame,
+    put into the spare field of the original, makes the sum over the rewritten
+    frame 0xFFFF exactly (that value +/- 1: the neighbours). Only the spare
+    fields change, so flow keys and the order of first sightings, hence
+    allocation order, NAT ports and CHT choices, repeat in the next run.
+    fold2 frames carry 0xFF payload bytes, the word chosen so that the low
+    half of the 32-bit raw L4 sum is 0xFFFF. IHL 5 or 6 (zero option word)."""
+    n = lens.shape[0]
+    F = frames.reshape(n, slot).copy()
+    lab = np.asarray(labels)
+    idx = np.nonzero(lab >= 0)[0]
+    for i in idx:
+        f = F[i]
+        l4 = 14 + 4 * (int(f[14]) & 15)
+        assert at[i] % 2 == 0 and l4 + 20 <= at[i] and \
+            at[i] + 2 <= 14 + _be16_at(f, 16) <= lens[i]
+        f[18:20] = 0
+        if EDGES[lab[i]] == "fold2":
+            f[l4 + (20 if f[23] == 6 else 8):14 + _be16_at(f, 16)] = 0xFF
+        f[at[i]:at[i] + 2] = 0
+    out1 = F.reshape(-1).copy()
+    fresh().run(out1, lens, in_dev, now, slot)
+    R = out1.reshape(n, slot)
+    for i in idx:
+        f, r = F[i], R[i]
+        l4 = 14 + 4 * (int(f[14]) & 15)
+        edge = EDGES[lab[i]]
+        if edge == "fold2":  # LE words, as __rte_raw_cksum adds them
+            b = r[l4:l4 + _be16_at(r, 16) - 20].astype(np.int64)
+            if b.size & 1:
+                b = np.append(b, 0)
+            s = int((b[0::2] | (b[1::2] << 8)).sum())
+            c = _l4_cksum_at(r, l4)
+            s -= _le16_at(r, c)  # (summed with the field zero)
+            w = 0xFFFF - (s & 0xFFFF)
+            f[at[i]:at[i] + 2] = (w & 0xFF, w >> 8)
+            continue
+        o, spare = (_l4_cksum_at(r, l4), at[i]) if edge[:2] == "l4" else (24, 18)
+        # (host-order words, as DPDK sums and stores them: the neighbour above
+        # the IP edge is then the sum at which fold16's first fold carries)
+        c = _le16_at(r, o)
+        d = {"zero": 0, "0001": -1, "fffe": 1}[edge[3:]]
+        w = (c + d) % 0xFFFF if c + d not in (0, 0xFFFF) else c + d  # ones' complement
+        f[spare:spare + 2] = (w & 0xFF, w >> 8)
+    return F.reshape(-1)
+
+
+def _assign_edges(rng, eligible, proto):
+    """One label per eligible frame, the counts kept level; the zero rule gets
+    a share for UDP and one for TCP."""
+    kinds = [(0, 17), (0, 6)] + [(e, None) for e in range(1, len(EDGES))]
+    cnt = [0] * len(kinds)
+    lab = np.full(proto.shape[0], -1, np.int64)
+    for i in rng.permutation(np.nonzero(eligible)[0]):
+        ok = [k for k, (_, p) in enumerate(kinds) if p is None or p == proto[i]]
+        k = min(ok, key=lambda j: cnt[j])
+        cnt[k] += 1
+        lab[i] = kinds[k][0]
+    return lab
+
+
+def _spare_word_at(rng, lens, tl, l4, past64):
+    """Byte 56 (l4 + 20 under options) serves the shortest frame, TCP or UDP;
+    `past64`: where the frame is long enough, a word past byte 64 instead (so
+    the edge arrives through the tail sum), for about half the frames or, with
+    past64 = 1.0, for all."""
+    at = l4 + (22 if l4 == 34 else 20)
+    end = 14 + tl
+    if past64 and end >= 68 and rng.random() < past64:
+        at = 64 + 2 * int(rng.integers(0, (end - 64) // 2))
+    return at
+
+
+def nat_cksum_trace(rng, n, n_flows, slot, max_len=60, min_len=60, wan_frac=0.0,
+                    bad_tiles=0.0, ihl6_frac=0.0, pad_frac=0.1, past64=0.5,
+                    only_ihl6=False):
+    """vignat traffic for cksum_edge_frames: LAN packets over n_flows (TCP and
+    UDP alike, random payload, lengths uniform in [min_len, min(slot,
+    max_len)], some padded past total_length), WAN replies of flows whose LAN
+    side came first (the external port is the flow's rank among first
+    sightings: no expiry, the table not full) or of unknown ports, one
+    malformed frame in a fraction `bad_tiles` of the 64-packet tiles, a
+    fraction of frames with IHL 6 (a zero option word: the byte-addressed
+    path). Returns the trace, the labels (every frame that will be forwarded
+    has one; only_ihl6: only those with options) and the spare words'
+    offsets."""
+    top = min(slot, max_len)
+    fl = rng.integers(0, n_flows, n)
+    sip = T.ip4(10, 3, 0, 0) + fl
+    dip = T.ip4(9, 9, 0, 1) + (fl % 5) * 256
+    sp = 4000 + fl % 23
+    dp = 443 + fl % 2
+    proto = np.where(fl % 2 == 0, 6, 17)
+    lens = rng.integers(min_len, top + 1, n).astype(np.uint16)
+    frames = rng.integers(0, 256, (n, slot), dtype=np.uint8)
+    for p_ in (6, 17):
+        m = proto == p_
+        f, _ = T.udp_frames(sip[m], dip[m], sp[m], dp[m], slot=slot, proto=p_)
+        frames[m, :38] = f.reshape(-1, slot)[:, :38]
+    ihl6 = rng.random(n) < ihl6_frac
+    lens[ihl6] = np.minimum(np.maximum(lens[ihl6], 64), slot - 4 if slot > 64 else 60)
+    tl = lens.astype(np.int64) - 14
+    pad = (rng.random(n) < pad_frac) & (tl > 46)
+    tl[pad] = np.maximum(46, tl[pad] - rng.integers(1, 40, int(pad.sum())))
+    frames[:, 16] = (tl >> 8).astype(np.uint8)
+    frames[:, 17] = (tl & 0xFF).astype(np.uint8)
+    in_dev = np.zeros(n, np.uint16)
+    wan = (rng.random(n) < wan_frac) & ~ihl6
+    in_dev[wan] = 1
+    bad = np.zeros(n, bool)
+    for t in np.nonzero(rng.random((n + 63) // 64) < bad_tiles)[0]:
+        bad[min(n - 1, int(t) * 64 + int(rng.integers(0, 64)))] = True
+    rank, eligible = {}, np.zeros(n, bool)
+    for i in range(n):
+        k = int(fl[i])
+        f = frames[i]
+        if bad[i]:
+            if rng.random() < 0.5:
+                f[12] = 0x86  # not IPv4
+            else:
+                f[23] = 1  # ICMP
+        elif wan[i]:  # the reply: addresses and ports swapped, dst port raw LE
+            f[26:30], f[30:34] = f[30:34].copy(), (192, 168, 4, 2)
+            f[34:36] = f[36:38].copy()
+            idx = rank.get(k, n_flows + int(rng.integers(0, 50)))
+            f[36:38] = (idx & 0xFF, idx >> 8)
+            eligible[i] = k in rank
+        else:
+            rank.setdefault(k, len(rank))
+            eligible[i] = True
+        if ihl6[i]:
+            f[38:] = f[34:slot - 4].copy()
+            f[34:38] = 0
+            f[14] = 0x46
+    l4 = np.where(ihl6, 38, 34)
+    udp = frames[:, 23] == 17
+    for i in np.nonzero(udp)[0]:
+        ul = int(tl[i]) - 20 - (4 if ihl6[i] else 0)
+        frames[i, l4[i] + 4:l4[i] + 6] = (ul >> 8, ul & 0xFF)
+    if only_ihl6:
+        eligible &= ihl6
+    labels = _assign_edges(rng, eligible, frames[:, 23])
+    at = np.array([_spare_word_at(rng, int(lens[i]), int(tl[i]), int(l4[i]),
+                                  0 if ihl6[i] else past64) for i in range(n)])
+    now = T.NOW0 + np.cumsum(rng.integers(0, 3, n))
+    return (frames.reshape(-1), lens, in_dev, now.astype(np.int64)), labels, at
+
+
+def lb_cksum_batch(rng, n, slot, max_len=60, pad_frac=0.1, past64=0.5, wan=2):
+    """n WAN frames of n distinct viglb flows (TCP and UDP alike, random
+    payload, lengths uniform in [60, min(slot, max_len)]) for
+    cksum_edge_frames, every one labelled: fed once they are first sightings,
+    fed again they are hits (or, their backends gone, stale flows). Returns
+    (frames, lens, in_dev), labels and the spare words' offsets."""
+    top = min(slot, max_len)
+    k = np.arange(n)
+    proto = np.where(k % 2 == 0, 6, 17)
+    lens = rng.integers(60, top + 1, n).astype(np.uint16)
+    frames = rng.integers(0, 256, (n, slot), dtype=np.uint8)
+    for p_ in (6, 17):
+        m = proto == p_
+        f, _ = T.udp_frames(T.ip4(11, 3, 0, 0) + k[m], np.full(int(m.sum()), T.ip4(10, 9, 8, 7)),
+                            2000 + k[m] % 11, np.full(int(m.sum()), 80), slot=slot, proto=p_)
+        frames[m, :38] = f.reshape(-1, slot)[:, :38]
+    tl = lens.astype(np.int64) - 14
+    pad = (rng.random(n) < pad_frac) & (tl > 46)
+    tl[pad] = np.maximum(46, tl[pad] - rng.integers(1, 40, int(pad.sum())))
+    frames[:, 16] = (tl >> 8).astype(np.uint8)
+    frames[:, 17] = (tl & 0xFF).astype(np.uint8)
+    udp = proto == 17
+    ul = tl[udp] - 20
+    frames[udp, 38] = (ul >> 8).astype(np.uint8)
+    frames[udp, 39] = (ul & 0xFF).astype(np.uint8)
+    _lb_src_macs(rng, frames, k)
+    labels = _assign_edges(rng, np.ones(n, bool), proto)
+    at = np.array([_spare_word_at(rng, int(lens[i]), int(tl[i]), 34, past64)
+                   for i in range(n)])
+    return (frames.reshape(-1), lens, np.full(n, wan, np.uint16)), labels, at
