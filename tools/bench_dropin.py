@@ -9,10 +9,12 @@ and through vp_process_batch in bursts (nf.c:178-215).
   tools/bench_dropin.py --nf fw                      # batch 0 / 32 / 1024
   tools/bench_dropin.py --nf fw --sweep 32,64,128    # burst routing limit
   tools/bench_dropin.py --nf bridge                  # vigbridge: 1,024 stations
+  tools/bench_dropin.py --nf pol                     # vigpol: 1,024 policed addresses
 
 --sweep N,...: each burst size twice in this run, VIGPATH_SERVE_BURST forcing
 the resident kernel (a limit above every N) and the batch pipeline (0): the
-routing limit (kServeBurstRoute / kFwBurstRoute / kBridgeBurstRoute) is the
+routing limit (kServeBurstRoute / kFwBurstRoute / kBridgeBurstRoute /
+kPolBurstRoute) is the
 largest N at which the served path is the faster one per packet.
 
 --tree DIR: another build of the library (a checkout of another commit with
@@ -49,6 +51,12 @@ def bridge_port(n, flows):
     return (((p + flows // 2) % flows) & 1).astype(np.uint16)
 
 
+def lan_port(n, flows):
+    """vigpol: every steady packet arrives on the WAN device, finds its
+    address's bucket full enough and goes out on the LAN device."""
+    return np.ones(n, np.uint16)
+
+
 # per NF: its loop binary, trace, arguments, the option that sizes its table to
 # `--flows`, and the out port expected of every steady packet
 NF = {
@@ -62,6 +70,12 @@ NF = {
                      "--eth-dest", "1,90:e2:ba:55:12:21"]),
     "bridge": dict(loop="nf_loop_bridge", trace=T.bridge_trace, size="--capacity",
                    steady=bridge_port, args=["--expire", "60000000"]),
+    # 1 B/ns into buckets of 100 MB: entries live 0.1 s of trace time (the
+    # trace advances 1 ns a packet, so no expiry is due in a run of up to 1e8
+    # packets) and no bucket of 60-byte packets runs dry
+    "pol": dict(loop="nf_loop_pol", trace=T.pol_trace, size="--capacity", steady=lan_port,
+                args=["--lan", "1", "--wan", "0", "--rate", "1000000000",
+                      "--burst", "100000000"]),
 }
 
 

@@ -346,7 +346,8 @@ struct HostMap {
 constexpr int kMaxHostMaps = 16;
 
 // vp_process_one's mailbox (nat_serve, vp_nat.hip; fw_serve, vp_fw.hip;
-// bridge_serve, vp_bridge.hip; its host side in vp_serve.hip): page-locked, host-coherent
+// bridge_serve, vp_bridge.hip; pol_serve, vp_pol.hip; its host side in
+// vp_serve.hip): page-locked, host-coherent
 // memory the host and a persistent one-wave kernel poll. The host writes the
 // request (below); the kernel writes the rewritten frame to `frame`, then
 // sets the answer word.
@@ -428,7 +429,8 @@ inline void serve_unpack(const ServeBox *bx, uint8_t *frame, uint32_t back) {
 }
 
 // What of a served NF the mailbox's host side needs to know (nat_serve_nf,
-// vp_nat.hip; fw_serve_nf, vp_fw.hip; bridge_serve_nf, vp_bridge.hip).
+// vp_nat.hip; fw_serve_nf, vp_fw.hip; bridge_serve_nf, vp_bridge.hip;
+// pol_serve_nf, vp_pol.hip).
 struct ServeNf {
   // the table whose entries expire and the cutoff for a packet at time t: a
   // request is sent only while no expiry is due
@@ -439,7 +441,8 @@ struct ServeNf {
   // request's chunks carry it
   bool one_whole;
   // one packet through the chunks: the most frame bytes that go (what the
-  // kernel reads: kServeInline, vigbridge's 12 MAC bytes) and that come back
+  // kernel reads: kServeInline, vigbridge's 12 MAC bytes, vigpol's 34 up to
+  // the policed address) and that come back
   // in the answer chunks (what it can change: all, vigfw's MACs, none)
   uint32_t one_in, one_back;
   uint32_t burst_in, burst_back;  // a burst's frame: the most bytes in, and back
@@ -449,10 +452,12 @@ struct ServeNf {
 const ServeNf &nat_serve_nf();
 const ServeNf &fw_serve_nf();
 const ServeNf &bridge_serve_nf();
+const ServeNf &pol_serve_nf();
 inline const ServeNf *serve_nf(int kind) {  // (nullptr: the NF has no resident kernel)
   return kind == KIND_NAT      ? &nat_serve_nf()
          : kind == KIND_FW     ? &fw_serve_nf()
          : kind == KIND_BRIDGE ? &bridge_serve_nf()
+         : kind == KIND_POL    ? &pol_serve_nf()
                                : nullptr;
 }
 // One packet through the persistent kernel (one GPU, no expiry due): 0 done;
@@ -490,6 +495,7 @@ uint32_t serve_burst_limit(uint32_t dflt);
 int nat_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
 int fw_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
 int bridge_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
+int pol_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
 
 }  // namespace vp
 

@@ -870,7 +870,7 @@ int vp_process_mbufs(vp_ctx *c, const vp_mbuf_batch *b) {
   vp_mbuf_batch rest;
   const ServeNf *nf = serve_nf(c->kind);
   if (nf && b->n) {
-    // a small vignat, vigfw or vigbridge burst goes to the resident kernel, which stays
+    // a small vignat, vigfw, vigbridge or vigpol burst goes to the resident kernel, which stays
     // (no hipSetDevice: a served burst makes no HIP call, as vp_process_one)
     uint32_t done = 0;
     const int rc = serve_process_burst(c, *nf, b, 0, b->n, &done);

@@ -35,6 +35,7 @@
 
 #include <vector>
 
+#include "vp_serve_dev.h"
 #include "vp_table.h"
 
 namespace vp {
@@ -442,6 +443,274 @@ __global__ __launch_bounds__(256) void pol_last_ipv4(const uint8_t *frames,
   if (threadIdx.x == 0) *out = found;
 }
 
+// ========================================================= one packet ==
+// nf.c calls nf_process once per packet (nf.c:150-176) or once per small
+// burst (its VIGOR_BATCH_SIZE loop, nf.c:178-215). vp_process_one and small
+// vp_process_mbufs calls go to pol_serve, one wave that stays resident and
+// polls the host-coherent mailbox (ServeBox, vp_internal.h), as nat_serve,
+// fw_serve and bridge_serve do for their NFs: no launch and no copy call per
+// packet. The host sends requests only while no expiry is due
+// (serve_process_one / serve_process_burst), so the kernel restates
+// policer_main.c:111-145 and 34-103 without policer_expire_entries. The
+// policer never rewrites a frame and reads only its first 34 bytes (the
+// policed address is bytes 30-33); IPv4 options do not matter to it (it never
+// parses L4), so nothing is declined.
+
+// T holds the CRC tables, then the layout's byte tables (kMixLin).
+constexpr uint32_t kPolTabWords = kPolTabs * 256 + 1024;
+
+// What pol_serve needs of the configuration and the state (the batch
+// pipeline's PolArgs stays with the pipeline).
+struct PolServeArgs {
+  TableDev t;
+  const uint32_t *crc_tab;
+  uint64_t burst, rate, thr;  // thr = burst * 1e9 / rate (u64, as the reference)
+  uint64_t *bsize;            // dyn_vals by index: bucket_size,
+  int64_t *btime;             //                    bucket_time
+  // lan | wan << 16: one word, its halves taken by shifts (a choice between
+  // two neighbouring members compiles to an indexed load from a copy of the
+  // struct in scratch memory)
+  uint32_t ports;
+  __device__ uint32_t lan() const { return ports & 0xFFFFu; }
+  __device__ uint32_t wan() const { return ports >> 16; }
+};
+
+// nf_then_get_rte_ipv4_header (nf-util.h:122-151) on frame words 3 and 4
+// (bytes 12-19, zero past len), as pol_ipv4_w states it.
+__device__ __forceinline__ bool pol_ipv4_r(uint32_t w3, uint32_t w4, uint32_t total) {
+  const uint16_t unread = (uint16_t)(total - 14);
+  const uint32_t ihl = (w3 >> 16) & 0x0F;
+  const uint16_t tl = bswap16((uint16_t)(w4 & 0xFFFF));
+  return ((w3 & 0xFFFF) == 0x0008) & (unread >= 20) & (ihl >= 5) & (unread >= tl);
+}
+
+// policer_check_tb's arithmetic on a known address (policer_main.c:39-72),
+// as pol_replay's: a packet of len bytes at time tu against the bucket (size,
+// last seen at btu). Forwarded?
+__device__ __forceinline__ bool pol_take(const PolServeArgs &a, uint64_t &size, uint64_t btu,
+                                         uint64_t len, uint64_t tu) {
+  const uint64_t diff = tu - btu;
+  if (diff < a.thr) {
+    size += diff * a.rate / kNsPerS;
+    if (size > a.burst) size = a.burst;
+  } else {
+    size = a.burst;
+  }
+  const bool fwd = size > len;
+  if (fwd) size -= len;
+  return fwd;
+}
+
+// The out port of a packet that is not policed: not IPv4 -> in (dropped
+// before the expiry, policer_main.c:118-121), LAN -> WAN, another device ->
+// in (policer_main.c:125-144).
+__device__ __forceinline__ uint32_t pol_pass(const PolServeArgs &a, bool v4, uint32_t in) {
+  return v4 && in == a.lan() ? a.wan() : in;
+}
+
+// A burst request (vp_serve_dev.h) for vigpol. Round 0 and burst_settle give
+// every policed lane (WAN, IPv4) its address's index, or kNone: a miss no
+// larger than the burst allocates in packet order (lpend; the same new address
+// on a later lane is then a plain hit), a larger one is a hit only of what a
+// lane before it allocated (wpend) and is dropped with nothing written
+// otherwise, as is every packet that finds no index free.
+//
+// Unlike the other served NFs' hits, vigpol's are not independent: the token
+// bucket is a serial recurrence per address (refill, clamp, conditional
+// take), so the lanes of one index must pass through it in packet order. The
+// lanes holding an index form a chain (own: its lowest lane, nxt: the next
+// higher one); the owner carries (size, btu) in registers and walks its chain
+// one member per round, every owner at once, fetching the member's length,
+// time and fresh bit by ds_bpermute: as many rounds as the longest chain, one
+// for a burst of distinct addresses. A member that allocated the index in
+// this burst is the chain's first and starts the bucket at burst - len
+// (policer_main.c:91-100). The owner keeps its members' forwarded bits in a
+// 64-bit mask each member reads afterwards, and stores the bucket once; the
+// chain's last lane stamps (every policed packet rejuvenates,
+// policer_main.c:38).
+__device__ __forceinline__ uint32_t pol_burst(const PolServeArgs &a, const uint32_t *T,
+                                              ServeBox *box, uint32_t n, uint64_t seq0,
+                                              uint32_t lane) {
+  const TableDev &t = a.t;
+  const BurstIn b = burst_load(box, n, lane);
+  const bool v4 = pol_ipv4_r(b.f.w[3], b.f.w[4], b.len);
+  const bool police = b.act && v4 && b.in == a.wan();
+  const uint32_t dst = b.f.u32at2(30);
+  const uint32_t hh = pol_hash(T, dst);
+  const uint32_t key[4] = {dst, 0, 0, 0};
+  // round 0, then the misses in packet order
+  uint32_t idx = kNone, fresh = 0;
+  if (police) idx = tbl_probe(t, hh, key);
+  const bool miss = police && idx == kNone;
+  burst_settle(
+      lane, miss && b.len <= a.burst, miss && b.len > a.burst,
+      [&] { idx = tbl_probe(t, hh, key); },
+      [&] { idx = serve_lan<0xFFFFFFFFu>(t, hh, key, 0u, seq0 + lane, &fresh); });
+  // the chains (descending, so the lowest lane on either side is what stays)
+  uint32_t own = lane, nxt = kServeBurst;
+  for (uint32_t j = n; j-- > 0;) {
+    const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)idx, (int)j);
+    if (o == idx && j > lane) nxt = j;
+    if (o == idx && j < lane) own = j;
+  }
+  const bool policed = idx != kNone;
+  const bool first = policed && own == lane;
+  if (policed && nxt == kServeBurst) serve_stamp(t, idx, b.now, seq0 + lane);
+  // the ordered replay
+  uint64_t size = 0, btu = 0, took = 0;
+  if (first) {
+    size = a.bsize[idx];
+    btu = (uint64_t)a.btime[idx];
+  }
+  const uint32_t now_lo = (uint32_t)(uint64_t)b.now, now_hi = (uint32_t)((uint64_t)b.now >> 32);
+  uint32_t cur = first ? lane : kServeBurst;  // the owner's member of this round
+  while (__ballot(cur < kServeBurst)) {
+    const int src = (int)(cur & (kServeBurst - 1));
+    const uint64_t len = (uint32_t)__shfl((int)b.len, src);
+    const uint64_t tu = (uint64_t)(uint32_t)__shfl((int)now_lo, src) |
+                        ((uint64_t)(uint32_t)__shfl((int)now_hi, src) << 32);
+    const uint32_t born = (uint32_t)__shfl((int)fresh, src);
+    const uint32_t next = (uint32_t)__shfl((int)nxt, src);
+    if (cur < kServeBurst) {
+      bool fwd = true;
+      if (born)
+        size = a.burst - len;  // new flow: forwarded (policer_main.c:91-103)
+      else
+        fwd = pol_take(a, size, btu, len, tu);
+      btu = tu;
+      took |= (uint64_t)fwd << cur;
+      cur = next;
+    }
+  }
+  if (first) {
+    a.bsize[idx] = size;
+    a.btime[idx] = (int64_t)btu;
+  }
+  const uint64_t fwds = (uint64_t)(uint32_t)__shfl((int)(uint32_t)took, (int)own) |
+                        ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(took >> 32), (int)own) << 32);
+  const uint32_t out = !police              ? pol_pass(a, v4, b.in)
+                       : (fwds >> lane) & 1 ? a.lan()
+                                            : a.wan();
+  burst_out(b, (out & 0xFFFFu) | (fresh << 16), n, lane);
+  return kBurstServed;
+}
+
+// The server: one wave (<<<1, 64>>>). Every poll reads the request chunks
+// whole; a one-packet request is chunk 0 (len | in << 16, the time) and the
+// chunks that carry the frame's first 34 bytes at most (bytes past len read
+// as 0, the runt convention of DESIGN.md 7): words 3-4 (ethertype, ihl,
+// total length) in chunk 2 and 7-8 (the policed address) in chunk 3, which
+// lane 0 takes from lanes 2 and 3's registers: no LDS copy of the frame. Lane
+// 0 runs the packet; the answer is chunk 0 alone (out | fresh << 16). Packets
+// take global sequence numbers seq0, seq0 + 1, ...; a burst request
+// (pol_burst) takes as many as it has frames. The kernel leaves on the leave
+// request or after `idle` wall-clock ticks without a request; the host
+// launches it again (serve_wait). flags: serve_poll's.
+__global__ __launch_bounds__(64) void pol_serve(PolServeArgs a, ServeBox *box, uint64_t seq0,
+                                                uint64_t idle, uint32_t flags) {
+  __shared__ uint32_t T[kPolTabWords];
+  const uint32_t lane = threadIdx.x;
+  for (uint32_t i = lane; i < kPolTabs * 256; i += 64) T[i] = a.crc_tab[i];
+  if (a.t.mix == kMixLin) {  // (the layout's byte tables: their LDS copy)
+    for (uint32_t i = lane; i < 1024; i += 64) T[kPolTabs * 256 + i] = a.t.lin[i];
+    a.t.lin = T + kPolTabs * 256;
+  }
+  __syncthreads();
+  const ServeIo io = serve_io(box, lane);
+  // the last answered request (a relaunched server goes on from the answer
+  // word), the next packet's sequence, the last answer's wall clock
+  uint32_t done = __builtin_amdgcn_readfirstlane((uint32_t)__hip_atomic_load(
+      &box->ans, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM));
+  uint64_t seq = seq0;
+  uint64_t t0 = wall_clock64();
+  auto serve = [&](const v4u &c) -> int {
+    const uint32_t want = done + 1;
+    if (__builtin_amdgcn_readfirstlane(c[3]) != want) return -1;
+    const uint32_t hi = __builtin_amdgcn_readfirstlane(c[0]);
+    if (hi == kServeLeave) return 1;
+    const uint32_t in = hi >> 16;
+    if ((hi & 0xFFFFu) == kServeBurstOp) {  // chunk 0 alone, the frames in the burst body
+      const uint32_t bn = min(max(in, 1u), kServeBurst);
+      const uint32_t st = pol_burst(a, T, box, bn, seq, lane);
+      if (lane == 0) burst_answer(io, box, st, bn, want);
+      seq += bn;
+      t0 = wall_clock64();
+      done = want;
+      // (every lane's table writes before the next request reads them)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      return 0;
+    }
+    const uint32_t len = min(hi & 0xFFFFu, kServeFrame);
+    const uint32_t got = min(len, 34u);          // frame bytes in chunks 1-3
+    const uint32_t need = (12 + got + 11) / 12;  // chunks carrying the request
+    if (__ballot(lane < need && c[3] != want)) return -1;  // not whole yet: poll again
+    // chunk 0's time (message bytes 4-11). Not serve_now: readfirstlane
+    // returns an int, and serve_now widens the low word as one, so a time
+    // whose bit 31 is set comes out with the high word all ones; the bucket
+    // arithmetic and the cutoff boundary (a stamp one lifetime on, past 2^32
+    // ns) need the time exact.
+    const int64_t now =
+        (int64_t)((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(c[1]) |
+                  ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(c[2]) << 32));
+    // (a chunk past `need` is an earlier request's: masked to nothing)
+    const uint32_t w3 = (uint32_t)__builtin_amdgcn_readlane((int)c[0], 2) &
+                        bytes_mask(0, (int)got - 12);
+    const uint32_t w4 = (uint32_t)__builtin_amdgcn_readlane((int)c[1], 2) &
+                        bytes_mask(0, (int)got - 16);
+    const uint32_t w7 = (uint32_t)__builtin_amdgcn_readlane((int)c[1], 3) &
+                        bytes_mask(0, (int)got - 28);
+    const uint32_t w8 = (uint32_t)__builtin_amdgcn_readlane((int)c[2], 3) &
+                        bytes_mask(0, (int)got - 32);
+    uint32_t res = 0;
+    if (lane == 0) {
+      const bool v4 = pol_ipv4_r(w3, w4, len);
+      uint32_t out = pol_pass(a, v4, in), fresh = 0;
+      if (v4 && in == a.wan()) {
+        const uint32_t dst = (w7 >> 16) | (w8 << 16);  // bytes 30-33
+        const uint32_t hh = pol_hash(T, dst);
+        const uint32_t key[4] = {dst, 0, 0, 0};
+        uint32_t idx = tbl_probe(a.t, hh, key);
+        bool fwd = false;
+        if (idx != kNone) {
+          serve_stamp(a.t, idx, now, seq);
+          uint64_t size = a.bsize[idx];
+          fwd = pol_take(a, size, (uint64_t)a.btime[idx], len, (uint64_t)now);
+          a.bsize[idx] = size;
+          a.btime[idx] = now;
+        } else if (len <= a.burst) {  // (a larger one: dropped, policer_main.c:77-80)
+          idx = serve_lan<0xFFFFFFFFu>(a.t, hh, key, 0u, seq, &fresh);
+          if (idx != kNone) {  // (kNone: no index free, dropped, policer_main.c:84-87)
+            serve_stamp(a.t, idx, now, seq);
+            a.bsize[idx] = a.burst - len;
+            a.btime[idx] = now;
+            fwd = true;
+          }
+        }
+        out = fwd ? a.lan() : a.wan();
+      }
+      res = (out & 0xFFFFu) | (fresh << 16);
+    }
+    res = __builtin_amdgcn_readfirstlane(res);
+    if (lane == 0) {
+      __builtin_amdgcn_raw_buffer_store_b128((v4u){res, 0u, 0u, want}, io.as, 0, 0, kSys);
+      // (the answer word: where a relaunched server starts counting; the host
+      // reads the answer chunk. No release fence at system scope, which would
+      // write back the whole L2)
+      __hip_atomic_store(&box->ans, (uint64_t)want | ((uint64_t)res << 32), __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    seq += 1;
+    t0 = wall_clock64();
+    done = want;
+    // (lane 0's table writes before the next request's lanes read them)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    return 0;
+  };
+  serve_poll(io, flags, idle, serve, [&] { return t0; });
+}
+
 // =============================================================== host ==
 
 // policer_expire_entries (policer_main.c:21-32): exp_time and the cutoff in
@@ -632,6 +901,44 @@ int pol_process_device(vp_ctx *c, const vp_dev_batch *b) {
   }
   ExpiringTable tabs[1] = {{&c->ft, pol_cutoff}};
   return run_batch(c, b, tabs, 1, pol_segment, exp_end);
+}
+
+// ---------------------------------------------------- vp_process_one --
+// vigpol's launcher of the resident kernel (serve_launch, vp_serve.hip).
+int pol_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
+  PolServeArgs a{};
+  a.t = tbl_dev(c->ft);
+  a.crc_tab = c->crc_tab;
+  a.burst = c->pol.burst;
+  a.rate = c->pol.rate;
+  a.thr = c->pol.burst * kNsPerS / c->pol.rate;
+  a.bsize = c->pol_size;
+  a.btime = c->pol_time;
+  a.ports = (uint32_t)c->pol.lan_device | ((uint32_t)c->pol.wan_device << 16);
+  pol_serve<<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags);
+  VP_HIP(hipGetLastError());
+  return 0;
+}
+
+// The largest host batch routed to the server as burst requests: the largest
+// swept n at which the served path measured faster per packet than the batch
+// pipeline on the MI355X (profiles/r11_pol_serve.txt: 0.17 against 0.33-0.38
+// us at 256, 0.17 against 0.27-0.29 at 384, 0.167-0.176 against 0.201-0.210
+// at 512, the largest size swept); larger calls take the pipeline. Above the
+// other servers' 256 and 384: vigpol's pipeline pays a control read-back and
+// two radix sorts per call on top of its launches, and a served burst of
+// distinct addresses replays its buckets in one round. VIGPATH_SERVE_BURST
+// overrides it; 0 routes nothing.
+constexpr uint32_t kPolBurstRoute = 512;
+
+// vigpol through the mailbox (serve_process_one / serve_process_burst,
+// vp_serve.hip): pol_serve reads a frame's first 34 bytes and changes none,
+// so one packet sends 34 bytes and takes none back; a burst copies a frame's
+// first 48 bytes in (burst_load reads 64 of the slot; what lies past byte 34
+// is never looked at) and nothing back. No stage clock.
+const ServeNf &pol_serve_nf() {
+  static const ServeNf nf = {pol_cutoff, &vp_ctx::ft, false, 34, 0, 48, 0, kPolBurstRoute, false};
+  return nf;
 }
 
 // State by index: alloc, ts, dyn_keys (u32 address), dyn_vals.

@@ -1,6 +1,7 @@
 // vp_process_one's mailbox, host side (ServeBox, vp_internal.h), for any
 // context whose NF has a resident kernel -- vignat (nat_serve, vp_nat.hip),
-// vigfw (fw_serve, vp_fw.hip) and vigbridge (bridge_serve, vp_bridge.hip). Launching the kernel, waiting for an answer,
+// vigfw (fw_serve, vp_fw.hip), vigbridge (bridge_serve, vp_bridge.hip) and
+// vigpol (pol_serve, vp_pol.hip). Launching the kernel, waiting for an answer,
 // relaunching after an idle exit, stopping it before any other entry point
 // touches the table, yielding the GPU's hardware queues between contexts, and
 // the requests themselves: one packet (serve_process_one) and a small burst
@@ -138,6 +139,9 @@ static int serve_launch(vp_ctx *c) {
       break;
     case KIND_BRIDGE:
       VP_TRY(bridge_serve_launch(c, dbox, flags));
+      break;
+    case KIND_POL:
+      VP_TRY(pol_serve_launch(c, dbox, flags));
       break;
     default:
       return state_fail("no resident kernel for NF kind %d", c->kind);

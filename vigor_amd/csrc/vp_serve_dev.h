@@ -1,6 +1,6 @@
 // vp_process_one's mailbox, device side (ServeBox, vp_internal.h): what the
-// resident kernels nat_serve (vp_nat.hip), fw_serve (vp_fw.hip) and
-// bridge_serve (vp_bridge.hip) share --
+// resident kernels nat_serve (vp_nat.hip), fw_serve (vp_fw.hip),
+// bridge_serve (vp_bridge.hip) and pol_serve (vp_pol.hip) share --
 // the poll loop, the chunks of a one-packet request, a burst's load, header
 // tests, settle loop, stamp winner and answer words, and the allocate-and-
 // insert of a new LAN flow. What a flow's key is, how a WAN packet finds its

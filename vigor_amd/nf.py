@@ -277,9 +277,9 @@ class NfBase:
         return step
 
     def process(self, device: int, buffer: bytearray, now: int) -> int:
-        """nf_process for one packet (nf.h:13): vp_process_one (vignat, vigfw
-        and vigbridge on one GPU: the persistent kernel's mailbox, no launch
-        per packet; the other NFs: a one-packet batch)."""
+        """nf_process for one packet (nf.h:13): vp_process_one (vignat, vigfw,
+        vigbridge and vigpol on one GPU: the persistent kernel's mailbox, no
+        launch per packet; viglb: a one-packet batch)."""
         a = (C.c_uint8 * len(buffer)).from_buffer(buffer)
         out = C.c_uint16(device)
         self._ck(self.L.vp_process_one(self.h, device, C.cast(a, C.c_void_p), len(buffer),
@@ -288,7 +288,7 @@ class NfBase:
 
     def serve_stats(self) -> dict:
         """vp_serve_stats_get: what the resident kernel served so far (vignat,
-        vigfw and vigbridge; all zeros for the other NFs) -- packets_one
+        vigfw, vigbridge and vigpol; all zeros for viglb) -- packets_one
         (vp_process_one), bursts / burst_packets (small vp_process_batch /
         vp_process_mbufs calls), declined, launches. A host-side counter
         read: the kernel stays."""
