@@ -194,18 +194,22 @@ int vp_unregister_host(vp_ctx *ctx, void *base);
  * read as 0 and are never written. Per-packet arrays in page-locked memory
  * are DMA'd in place. Frames and out_dev hold the results when the call
  * returns.
- * vignat, vigfw, vigbridge and vigpol on one GPU serve a call of up to
+ * Every NF on one GPU serves a call of up to
  * VIGPATH_SERVE_BURST packets (default 256 for vignat and vigfw, 384 for
- * vigbridge, 512 for vigpol, each from its own measured crossover; 0: none) from
- * vp_process_one's resident kernel instead, as
+ * vigbridge, 512 for vigpol, 128 for viglb, each from its own measured crossover; 0:
+ * none) from vp_process_one's resident kernel instead, as
  * burst requests of up to 64 frames, one lane of a wave per packet, while no
- * flow expiry is due anywhere in the call, every frame is at most 2048 bytes
+ * expiry is due anywhere in the call (viglb: on its flows or its backends), every frame is at most 2048 bytes
  * and the times do not go back: no launch, no copy call, and the kernel stays
  * for the next call (nf.c's VIGOR_BATCH_SIZE loop, nf.c:178-215). A burst
  * holding a frame with IPv4 options is handed back and takes the path above
  * (vp_serve_stats_get counts both); vigbridge, which reads only the MACs,
  * and vigpol, which never parses L4, hand none back. vigpol's packets to one
- * destination address pass through its token bucket in packet order. */
+ * destination address pass through its token bucket in packet order. viglb's
+ * heartbeats from unknown addresses, new flows and flows whose backend died
+ * settle in packet order inside the burst; the one thing its kernel leaves to
+ * the path above is the erasure of a flow whose backend died while no backend
+ * is alive: that request is handed back too. */
 typedef struct vp_mbuf_batch {
   uint32_t n;
   uint8_t *const *frames;
@@ -219,7 +223,7 @@ typedef struct vp_mbuf_batch {
 int vp_process_mbufs(vp_ctx *ctx, const vp_mbuf_batch *batch);
 
 /* The same with a per-packet time array (the batch form of nf_process the
- * nf.h shims call); a small vignat, vigfw, vigbridge or vigpol burst is served by the resident
+ * nf.h shims call); a small burst is served by the NF's resident
  * kernel, which it does not end, exactly as through vp_process_mbufs. */
 int vp_process_batch(vp_ctx *ctx, uint32_t n, const uint16_t *in_dev,
                      uint8_t *const *frames, const uint16_t *len,
@@ -228,9 +232,10 @@ int vp_process_batch(vp_ctx *ctx, uint32_t n, const uint16_t *in_dev,
 /* One packet: nf_process (nf.h:14-15, called once per packet by nf.c:150-176;
  * the nf.h shims' nf_process calls this). The frame is rewritten in place and
  * the output port stored in *out_dev; same results as vp_process_batch with
- * n = 1. vignat, vigfw, vigbridge and vigpol on one GPU serve it from a persistent
+ * n = 1. Every NF on one GPU serves it from a persistent
  * kernel that polls a host-coherent mailbox (no launch per packet) while no
- * expiry is due at `now`; otherwise, and for viglb, it is
+ * expiry is due at `now`; otherwise, and for the one packet viglb's kernel
+ * hands back (the erasure of a flow with no backend alive), it is
  * vp_process_batch with n = 1.
  * The kernel leaves after VIGPATH_SERVE_IDLE_MS (default 20) without a
  * packet, at any other call on the context -- except a vp_process_batch /
@@ -362,15 +367,15 @@ typedef struct vp_table_stats {
 } vp_table_stats;
 int vp_table_stats_get(vp_ctx *ctx, int table, vp_table_stats *out);
 
-/* vignat's, vigfw's, vigbridge's or vigpol's resident kernel (vp_process_one, and
- * vp_process_batch / vp_process_mbufs calls small enough to be served as burst
- * requests) since the context was created. A read of host-side counters: the
- * kernel stays. All zeros for viglb, which has no resident kernel. */
+/* The NF's resident kernel (vp_process_one, and vp_process_batch /
+ * vp_process_mbufs calls small enough to be served as burst requests) since
+ * the context was created. A read of host-side counters: the kernel stays. */
 typedef struct vp_serve_stats {
   uint64_t packets_one;   /* packets served by vp_process_one's kernel */
   uint64_t bursts;        /* burst requests served */
   uint64_t burst_packets; /* packets in them */
-  uint64_t declined;      /* bursts the kernel handed back (byte-path frame) */
+  uint64_t declined;      /* requests the kernel handed back (a burst with a byte-path
+                             frame; viglb: a burst or a packet that erases a flow) */
   uint64_t launches;      /* launches of the resident kernel */
 } vp_serve_stats;
 int vp_serve_stats_get(vp_ctx *ctx, vp_serve_stats *out);

@@ -10,11 +10,12 @@ and through vp_process_batch in bursts (nf.c:178-215).
   tools/bench_dropin.py --nf fw --sweep 32,64,128    # burst routing limit
   tools/bench_dropin.py --nf bridge                  # vigbridge: 1,024 stations
   tools/bench_dropin.py --nf pol                     # vigpol: 1,024 policed addresses
+  tools/bench_dropin.py --nf lb                      # viglb: 256 backends, 1,024 flows
 
 --sweep N,...: each burst size twice in this run, VIGPATH_SERVE_BURST forcing
 the resident kernel (a limit above every N) and the batch pipeline (0): the
 routing limit (kServeBurstRoute / kFwBurstRoute / kBridgeBurstRoute /
-kPolBurstRoute) is the
+kPolBurstRoute / kLbBurstRoute) is the
 largest N at which the served path is the faster one per packet.
 
 --tree DIR: another build of the library (a checkout of another commit with
@@ -57,6 +58,25 @@ def lan_port(n, flows):
     return np.ones(n, np.uint16)
 
 
+LB_BACKENDS = 256
+
+
+def lb_trace(n, flows):
+    """viglb: LB_BACKENDS heartbeats announce the backends first, then WAN
+    traffic over `flows` flows round robin (n packets of it); nothing expires
+    in the run."""
+    hb = T.lb_heartbeats(LB_BACKENDS)
+    tr = T.lb_traffic(n, flows)
+    return tuple(np.concatenate(x) for x in zip(hb, tr))
+
+
+def lb_port(n, flows):
+    """viglb: every steady packet hits its flow and leaves on its backend's
+    device, 0 or 1 (which of the two is the CHT's choice): never on the WAN
+    device, 2."""
+    return None
+
+
 # per NF: its loop binary, trace, arguments, the option that sizes its table to
 # `--flows`, and the out port expected of every steady packet
 NF = {
@@ -76,17 +96,24 @@ NF = {
     "pol": dict(loop="nf_loop_pol", trace=T.pol_trace, size="--capacity", steady=lan_port,
                 args=["--lan", "1", "--wan", "0", "--rate", "1000000000",
                       "--burst", "100000000"]),
+    # `warm`: packets ahead of the flows that the warm-up takes too
+    "lb": dict(loop="nf_loop_lb", trace=lb_trace, size="--flow-capacity", steady=lb_port,
+               warm=LB_BACKENDS, env={"VIGPATH_NB_DEVICES": "3"},  # (WAN = device 2)
+               args=["--backend-capacity", str(LB_BACKENDS), "--cht-height", "257",
+                     "--flow-expiration", "60000000", "--backend-expiration", "60000000",
+                     "--wan", "2"]),
 }
 
 
 def run_loop(tree, nf, tin, tout, flows, batch, env):
     """One nf_loop run: us per timed packet (its out ports are left in tout)."""
-    cmd = [os.path.join(tree, "host", NF[nf]["loop"]), tin, tout, "--warm", str(flows)]
+    cmd = [os.path.join(tree, "host", NF[nf]["loop"]), tin, tout, "--warm",
+           str(flows + NF[nf].get("warm", 0))]
     if batch:
         cmd += ["--batch", str(batch)]
     cmd += ["--"] + NF[nf]["args"] + [NF[nf]["size"], str(flows)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300,
-                       env=dict(os.environ, **env))
+                       env=dict(os.environ, **NF[nf].get("env", {}), **env))
     if r.returncode != 0:
         raise RuntimeError("%s failed (%d): %s" % (cmd[0], r.returncode, r.stderr[-500:]))
     line = [x for x in r.stderr.splitlines() if x.startswith("timed ")][-1]
@@ -108,7 +135,8 @@ def main():
     a = ap.parse_args()
     n = a.flows + a.packets
     fr, ln, dv, now = NF[a.nf]["trace"](n, a.flows)
-    steady = NF[a.nf]["steady"](n, a.flows)[a.flows:]
+    steady = NF[a.nf]["steady"](n, a.flows)
+    n, warm = len(ln), len(ln) - a.packets  # (viglb: the heartbeats ahead of the flows)
     points = []
     if a.sweep:
         for bt in [int(x) for x in a.sweep.split(",")]:
@@ -127,7 +155,9 @@ def main():
             for _ in range(a.repeat):
                 us.append(run_loop(a.tree, a.nf, tin, tout, a.flows, bt, env))
                 out = np.frombuffer(open(tout, "rb").read(), np.uint16, n, 12)
-                assert (out[a.flows:] == steady).all()  # every steady packet out where expected
+                # every steady packet out where expected
+                assert (out[warm:] < 2).all() if steady is None else \
+                    (out[warm:] == steady[a.flows:]).all()
             rec = {"nf": a.nf, "label": a.label, "batch": bt, "path": path,
                    "packets": a.packets, "flows": a.flows,
                    "us_per_packet": [round(x, 3) for x in us],

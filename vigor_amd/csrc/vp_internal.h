@@ -346,8 +346,8 @@ struct HostMap {
 constexpr int kMaxHostMaps = 16;
 
 // vp_process_one's mailbox (nat_serve, vp_nat.hip; fw_serve, vp_fw.hip;
-// bridge_serve, vp_bridge.hip; pol_serve, vp_pol.hip; its host side in
-// vp_serve.hip): page-locked, host-coherent
+// bridge_serve, vp_bridge.hip; pol_serve, vp_pol.hip; lb_serve, vp_lb.hip; its
+// host side in vp_serve.hip): page-locked, host-coherent
 // memory the host and a persistent one-wave kernel poll. The host writes the
 // request (below); the kernel writes the rewritten frame to `frame`, then
 // sets the answer word.
@@ -367,7 +367,8 @@ constexpr uint32_t kServeInline = 12 * kServeChunks - 12;  // 84 frame bytes
 struct ServeBox {
   alignas(128) uint32_t msg[kServeChunks][4];  // host: the tagged request chunks
   // device: the answer the same way -- chunk k = bytes 12k .. 12k + 11 of
-  // (out | fresh << 16, 8 unused bytes, the rewritten frame's first
+  // (out | fresh << 16 | viglb: kOneFresh2, kOneDeclined; 8 unused bytes, the
+  // rewritten frame's first
   // kServeInline bytes) and the request number; one store instruction, no
   // wait between the frame and the answer word (a longer frame goes through
   // `frame` first, then chunk 0 alone)
@@ -387,12 +388,19 @@ struct ServeBox {
   alignas(128) uint8_t bframe[64][kServeFrame];
   int64_t bnow[64];
   uint32_t bmeta[64];  // len | in_dev << 16, as a one-packet request's word 0
-  // out port | fresh << 16 | rewritten << 17 (only rewritten frames are copied back)
+  // out port | fresh << 16 | rewritten << 17 | second table fresh << 18 (only
+  // rewritten frames are copied back)
   alignas(16) uint32_t bout[64];
 };
 constexpr uint32_t kServeBurst = 64;       // frames per burst request
 constexpr uint32_t kServeBurstOp = 0xFFFFu;  // message word 0, low half: a burst
 constexpr uint32_t kBurstServed = 0, kBurstDeclined = 1;  // answer chunk 0, word 0
+// Beside `fresh` (bit 16) in a burst's out word and in a one-packet result:
+// an entry of the NF's second table was allocated (viglb: a backend).
+constexpr uint32_t kOneFresh2 = 1u << 18;
+// A one-packet result: the request was declined with nothing written (viglb's
+// erasure of a flow, vp_lb.hip); the caller takes the batch path.
+constexpr uint32_t kOneDeclined = 1u << 19;
 static_assert(sizeof(((ServeBox *)nullptr)->bframe) == kServeBurst * kServeFrame, "burst slots");
 // The request chunks of a message m (3 words per chunk, `need` chunks) as
 // request `req`: a chunk's payload words, then its tag with release; chunk 0,
@@ -430,7 +438,7 @@ inline void serve_unpack(const ServeBox *bx, uint8_t *frame, uint32_t back) {
 
 // What of a served NF the mailbox's host side needs to know (nat_serve_nf,
 // vp_nat.hip; fw_serve_nf, vp_fw.hip; bridge_serve_nf, vp_bridge.hip;
-// pol_serve_nf, vp_pol.hip).
+// pol_serve_nf, vp_pol.hip; lb_serve_nf, vp_lb.hip).
 struct ServeNf {
   // the table whose entries expire and the cutoff for a packet at time t: a
   // request is sent only while no expiry is due
@@ -448,21 +456,28 @@ struct ServeNf {
   uint32_t burst_in, burst_back;  // a burst's frame: the most bytes in, and back
   uint32_t burst_route;           // the largest host batch routed as burst requests
   bool prof;                      // VIGPATH_SERVE_PROF's stage clock (nat_serve's)
+  // a second expiring table (viglb's backends), null for the others: a
+  // request is sent only while no expiry is due on it either, and kOneFresh2
+  // lowers its floor
+  int64_t (*cutoff2)(const vp_ctx *c, int64_t t) = nullptr;
+  FlowTable vp_ctx::*table2 = nullptr;
 };
 const ServeNf &nat_serve_nf();
 const ServeNf &fw_serve_nf();
 const ServeNf &bridge_serve_nf();
 const ServeNf &pol_serve_nf();
+const ServeNf &lb_serve_nf();
 inline const ServeNf *serve_nf(int kind) {  // (nullptr: the NF has no resident kernel)
   return kind == KIND_NAT      ? &nat_serve_nf()
          : kind == KIND_FW     ? &fw_serve_nf()
          : kind == KIND_BRIDGE ? &bridge_serve_nf()
          : kind == KIND_POL    ? &pol_serve_nf()
+         : kind == KIND_LB     ? &lb_serve_nf()
                                : nullptr;
 }
 // One packet through the persistent kernel (one GPU, no expiry due): 0 done;
-// 1 not eligible (the caller takes the batch path, the server is stopped);
-// < 0 an error.
+// 1 not eligible, or declined by the kernel with nothing written (the caller
+// takes the batch path, the server is stopped); < 0 an error.
 int serve_process_one(vp_ctx *c, const ServeNf &nf, uint16_t in_dev, uint8_t *frame,
                       uint16_t len, int64_t now, uint16_t *out);
 // Packets [first, first + count) of a host batch through the same kernel as
@@ -473,6 +488,9 @@ int serve_process_one(vp_ctx *c, const ServeNf &nf, uint16_t in_dev, uint8_t *fr
 // request declined: the caller runs the rest through the pipeline).
 int serve_process_burst(vp_ctx *c, const ServeNf &nf, const vp_mbuf_batch *b, uint32_t first,
                         uint32_t count, uint32_t *served);
+// A host batch through the batch pipeline, the resident kernel stopped first
+// (vp_mbuf.hip).
+int mbufs_unserved(vp_ctx *c, const vp_mbuf_batch *b);
 // The mailbox's host side, for any served NF (vp_serve.hip). Stop the
 // context's persistent kernel, if it runs (every other entry point calls this
 // first: the kernel owns the table while it runs).
@@ -496,6 +514,7 @@ int nat_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
 int fw_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
 int bridge_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
 int pol_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
+int lb_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
 
 }  // namespace vp
 

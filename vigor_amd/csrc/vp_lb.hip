@@ -47,6 +47,7 @@
 #include <cstring>
 #include <vector>
 
+#include "vp_serve_dev.h"
 #include "vp_table.h"
 
 namespace vp {
@@ -584,6 +585,391 @@ __global__ void lb_hb_finish(LbArgs a, const uint32_t *list, uint32_t n,
   }
 }
 
+// ========================================================= one packet ==
+// nf.c calls nf_process once per packet (nf.c:150-176) or once per small
+// burst (its VIGOR_BATCH_SIZE loop, nf.c:178-215). vp_process_one and small
+// vp_process_mbufs calls go to lb_serve, one wave that stays resident and
+// polls the host-coherent mailbox (ServeBox, vp_internal.h), as nat_serve,
+// fw_serve, bridge_serve and pol_serve do for their NFs: no launch and no
+// copy call per packet. The host sends requests only while no expiry is due
+// on the flow table or on the backend table (serve_process_one /
+// serve_process_burst), so the kernel restates lb_main.c:20-68 and
+// lb_balancer.c:38-143 without lb_expire_flows / lb_expire_backends.
+//
+// One case is left to the batch pipeline: a WAN packet whose flow points at a
+// dead backend while no backend is alive erases the flow and frees its index
+// (lb_stale_free_seq). The host's control mirror and its tombstone check
+// (tbl_check_tombs) do not see what a resident kernel does, so lb_serve never
+// erases: it declines such a request before it has written anything.
+
+// lb_one's answers that are no backend index.
+constexpr uint32_t kLbPass = 0xFFFFFFFEu;     // out = in, the frame as it came
+constexpr uint32_t kLbDecline = 0xFFFFFFFDu;  // the erasure: the batch pipeline's
+
+// lb_main.c:56-65 on a register frame (IHL 5), the L4 bytes past byte 64
+// summed in `tail`: the out port, *rew = 1 when the frame changed.
+__device__ __forceinline__ uint32_t lb_serve_rewrite(const LbArgs &a, RFrame &f, uint4 rec,
+                                                     uint32_t proto, uint32_t tl, uint32_t tail,
+                                                     uint32_t *rew) {
+  const uint32_t nic = rec.z >> 16;
+  if (nic == a.wan) return nic;
+  f.set32at2(30, rec.x);  // dst_addr = backend.ip
+  uint32_t mw[3];
+  backend_macs(a, rec, nic, mw);
+  f.w[0] = mw[0];
+  f.w[1] = mw[1];
+  f.w[2] = mw[2];
+  fast_checksums(f, proto, tl, tail);
+  *rew = 1;
+  return nic;
+}
+
+// A new flow's index for key (sip, dip, sp | dp << 16, proto) that the caller
+// has just looked up in vain, its backend c in word 3 (serve_lan without the
+// second lookup); kNone when no index is free.
+__device__ __forceinline__ uint32_t lb_flow_new(const LbArgs &a, uint32_t h, uint32_t sip,
+                                                uint32_t dip, uint32_t ports, uint32_t proto,
+                                                uint32_t c, uint64_t seq, uint32_t *fresh) {
+  const uint32_t key[4] = {sip, dip, ports, proto};
+  return serve_lan_by(a.ft, h, key, proto | (c << 8), seq, fresh, [] { return kNone; });
+}
+
+// lb_process_heartbit (lb_balancer.c:114-143) for source address sip, source
+// MAC (m0: bytes 6-9, m1: 10-11) on device `in`: the backend's index, allocated
+// and its record written when the address is new (*fresh = 1), kNone when the
+// backend table is full. The caller stamps it.
+__device__ __forceinline__ uint32_t lb_backend_seen(const LbArgs &a, uint32_t hh, uint32_t sip,
+                                                    uint32_t m0, uint32_t m1, uint32_t in,
+                                                    uint64_t seq, uint32_t *fresh) {
+  const uint32_t key[4] = {sip, 0, 0, 0};
+  uint32_t born = 0;
+  const uint32_t bi = serve_lan<0xFFFFFFFFu>(a.bt, hh, key, 0u, seq, &born);
+  if (born) {
+    a.be_rec[bi] = make_uint4(sip, m0, m1 | (in << 16), 0);
+    *fresh = 1;
+  }
+  return bi;
+}
+
+// A stale flow fi (its backend is gone) re-pointed at backend c, as
+// lb_stale_reassign does: free + allocate hands the same index back.
+__device__ __forceinline__ void lb_flow_repoint(const LbArgs &a, uint32_t fi, uint32_t proto,
+                                                uint32_t c) {
+  const uint32_t e = a.ft.slot_of[fi];
+  a.ft.bk[e >> 2].k[e & 3][3] = proto | (c << 8);
+}
+
+// lb_process in packet order for one parsed TCP/UDP packet: the backend whose
+// record rewrites it, kLbPass or kLbDecline. *fresh: bit 0 a flow was
+// allocated, bit 1 a backend. T: the 17 CRC tables.
+__device__ __forceinline__ uint32_t lb_one(const LbArgs &a, const uint32_t *T, uint32_t in,
+                                           uint32_t sip, uint32_t dip, uint32_t sp, uint32_t dp,
+                                           uint32_t proto, uint32_t m0, uint32_t m1, int64_t now,
+                                           uint64_t seq, uint32_t *fresh) {
+  if (in != a.wan) {  // a heartbeat
+    uint32_t born = 0;
+    const uint32_t bi =
+        lb_backend_seen(a, ip_hash(T + kLbFlowTabs * 256, sip), sip, m0, m1, in, seq, &born);
+    if (bi != kNone) serve_stamp(a.bt, bi, now, seq);
+    *fresh |= born << 1;
+    return kLbPass;
+  }
+  const uint32_t h = lbflow_hash(T, sip, dip, sp, dp, proto);
+  uint32_t w3 = 0;
+  const uint32_t fi = flow_probe(a.ft, h, sip, dip, sp | (dp << 16), proto, &w3);
+  if (fi != kNone) {
+    uint32_t bi = w3 >> 8;
+    if (a.bt.slot_of[bi] == kNone) {  // its backend is gone
+      bi = cht_choose(a, h);
+      if (bi == kNone) return kLbDecline;  // (nothing written so far)
+      lb_flow_repoint(a, fi, proto, bi);
+    }
+    serve_stamp(a.ft, fi, now, seq);
+    return bi;
+  }
+  const uint32_t c = cht_choose(a, h);
+  if (c == kNone) return kLbPass;  // no backend alive: nothing written
+  uint32_t born = 0;
+  const uint32_t idx = lb_flow_new(a, h, sip, dip, sp | (dp << 16), proto, c, seq, &born);
+  if (idx != kNone) serve_stamp(a.ft, idx, now, seq);
+  *fresh |= born;
+  return c;  // (also when no index was free, lb_balancer.c:66)
+}
+
+// A burst request (vp_serve_dev.h) for viglb. Round 0: every lane looks
+// itself up in the state as the burst found it. Final there: a WAN hit on a
+// live backend (nothing inside a burst changes that flow's backend or kills
+// it), a heartbeat from a known address, and every frame that is no TCP or UDP
+// packet over IPv4. Pending, all as burst_settle's lpend (the lowest pending
+// lane runs per round, so they settle in packet order):
+//   H  a heartbeat from an unknown address: allocates on the backend table,
+//      and changes what cht_choose finds for every later lane;
+//   M  a WAN miss: its choice depends on every H before it, its index on every
+//      M before it, and a later lane with its key must take its backend;
+//   S  a WAN hit on a dead backend: its choice depends on every H before it.
+// Each looks again before it acts: H may find its address brought by an
+// earlier lane (a plain stamp), M its key stored (a plain hit on the stored
+// backend), S its backend index handed to an earlier H (which the reference
+// then takes for the flow's live backend: a plain hit) or the flow re-pointed
+// by an earlier S. As many rounds as pending lanes; steady traffic has none.
+// The erasure (S with no backend alive) declines the burst: when round 0
+// finds an S lane and the backend table's n_live is 0 at the burst's start.
+// Conservative (an earlier H of the burst might have revived a backend) but
+// exact, since the pipeline then gets the burst whole; with n_live above 0 at
+// the start it stays so, and no S lane can find cht_choose empty later.
+__device__ __forceinline__ uint32_t lb_burst(const LbArgs &a, const uint32_t *T, ServeBox *box,
+                                             uint32_t n, uint64_t seq0, uint32_t lane) {
+  BurstIn b = burst_load(box, n, lane);
+  const BurstHdr h = burst_hdr(b);
+  if (h.decline) return kBurstDeclined;
+  RFrame &f = b.f;
+  const uint32_t in = b.in;
+  // the L4 checksum's bytes past 64, [64, min(14 + total_length, len)), summed
+  // straight from the mailbox (as nat_serve's burst)
+  uint32_t tail = 0;
+  {
+    const uint32_t end = h.go && in == a.wan ? min(14 + h.tl, b.len) : 0u;
+    for (uint32_t base = 64; __ballot(base < end); base += 128) {
+      v4u x[8];
+#pragma unroll
+      for (uint32_t u = 0; u < 8; u++) {
+        const uint32_t cc = base + 16 * u;
+        x[u] = __builtin_amdgcn_raw_buffer_load_b128(
+            b.fs, (int)(cc < end ? b.slot0 + cc : kBurstBody), 0, kSys);
+      }
+#pragma unroll
+      for (uint32_t u = 0; u < 8; u++) {
+        const uint32_t cc = base + 16 * u;
+        tail = sum16x4(
+            chunk_keep(make_uint4(x[u][0], x[u][1], x[u][2], x[u][3]), 0, (int)end - (int)cc),
+            tail);
+      }
+    }
+  }
+  const bool hbp = h.go && in != a.wan, wanp = h.go && in == a.wan;
+  const uint32_t ports = h.sp | (h.dp << 16);
+  const uint32_t hf = lbflow_hash_batched(T, h.sip, h.dip, h.sp, h.dp, h.proto);
+  const uint32_t hi = ip_hash(T + kLbFlowTabs * 256, h.sip);
+  const uint32_t m0 = f.u32at2(6), m1 = f.w[2] >> 16;  // a heartbeat's source MAC
+  // round 0. fi: the flow to stamp, bi: the backend to stamp, be: the backend
+  // whose record rewrites the frame
+  uint32_t fi = kNone, bi = kNone, be = kNone, w3 = 0, fresh = 0;
+  auto flow_look = [&] {  // a flow whose backend is alive: final
+    fi = flow_probe(a.ft, hf, h.sip, h.dip, ports, h.proto, &w3);
+    if (fi != kNone && a.bt.slot_of[w3 >> 8] != kNone) be = w3 >> 8;
+  };
+  if (hbp) {
+    const uint32_t key[4] = {h.sip, 0, 0, 0};
+    bi = tbl_probe(a.bt, hi, key);
+  }
+  if (wanp) flow_look();
+  const bool stale = wanp && fi != kNone && be == kNone;
+  if (a.bt.ctl->n_live == 0 && __ballot(stale)) return kBurstDeclined;
+  burst_settle(
+      lane, hbp ? bi == kNone : wanp && be == kNone, false, [] {},
+      [&] {
+        if (hbp) {
+          uint32_t born = 0;
+          bi = lb_backend_seen(a, hi, h.sip, m0, m1, in, seq0 + lane, &born);
+          fresh |= born << 1;
+          return;
+        }
+        flow_look();
+        if (be != kNone) return;  // stored, re-pointed or revived by an earlier lane
+        const uint32_t c = cht_choose(a, hf);
+        if (c == kNone) {  // a miss with no backend alive: nothing written
+          fi = kNone;
+          return;
+        }
+        if (fi != kNone) {
+          lb_flow_repoint(a, fi, h.proto, c);
+        } else {
+          uint32_t born = 0;
+          fi = lb_flow_new(a, hf, h.sip, h.dip, ports, h.proto, c, seq0 + lane, &born);
+          fresh |= born;
+        }
+        be = c;
+      });
+  // Stamps, once over the flow indices and once over the backend indices: a
+  // packet that went to a backend stamps its flow if it has one (a miss that
+  // found no index free has none), a heartbeat its backend.
+  if (be == kNone) fi = kNone;
+  if (burst_last(fi, n, lane)) serve_stamp(a.ft, fi, b.now, seq0 + lane);
+  if (burst_last(bi, n, lane)) serve_stamp(a.bt, bi, b.now, seq0 + lane);
+  // the rewrite, each lane its own frame; back go a rewritten frame's first 64
+  // bytes (a rewrite touches nothing past byte 51)
+  uint32_t out = in, rew = 0;
+  if (be != kNone) out = lb_serve_rewrite(a, f, a.be_rec[be], h.proto, h.tl, tail, &rew);
+  if (rew) {
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+      __builtin_amdgcn_raw_buffer_store_b128(
+          (v4u){f.w[4 * j], f.w[4 * j + 1], f.w[4 * j + 2], f.w[4 * j + 3]}, b.fs,
+          (int)(b.slot0 + 16 * j), 0, kSys);
+  }
+  burst_out(b, (out & 0xFFFFu) | ((fresh & 1u) << 16) | (rew << 17) | ((fresh >> 1) << 18), n,
+            lane);
+  return kBurstServed;
+}
+
+// The server: one wave (<<<1, 64>>>). Every poll reads the request chunks
+// whole; a one-packet request brings a frame of up to kServeInline bytes in
+// them, a longer one whole through `frame`. The frame goes into LDS, the wave
+// sums the L4 bytes past byte 64, lane 0 runs the packet (in registers when
+// IHL = 5, byte-addressed over the LDS copy otherwise), the frame goes back
+// and the answer follows: out | flow allocated << 16 | backend allocated << 18,
+// or kOneDeclined with nothing written (the erasure). Packets take global
+// sequence numbers seq0, seq0 + 1, ...; a burst request (lb_burst) takes as
+// many as it has frames, a declined request none. The kernel leaves on the
+// leave request or after `idle` wall-clock ticks without a request; the host
+// launches it again (serve_wait). flags: serve_poll's.
+__global__ __launch_bounds__(64) void lb_serve(LbArgs a, ServeBox *box, uint64_t seq0,
+                                               uint64_t idle, uint32_t flags) {
+  __shared__ uint32_t T[kLbTabs * 256];
+  __shared__ uint4 fr[kServeFrame / 16];
+  const uint32_t lane = threadIdx.x;
+  lb_load_tables(T, a.crc_tab);
+  const ServeIo io = serve_io(box, lane);
+  const auto rs = __builtin_amdgcn_make_buffer_rsrc(box->frame, 0, kServeFrame, 0x00020000);
+  uint32_t *fw = reinterpret_cast<uint32_t *>(fr);
+  // the last answered request (a relaunched server goes on from the answer
+  // word), the next packet's sequence, the last answer's wall clock
+  uint32_t done = __builtin_amdgcn_readfirstlane((uint32_t)__hip_atomic_load(
+      &box->ans, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM));
+  uint64_t seq = seq0;
+  uint64_t t0 = wall_clock64();
+  auto serve = [&](const v4u &c) -> int {
+    const uint32_t want = done + 1;
+    if (__builtin_amdgcn_readfirstlane(c[3]) != want) return -1;
+    const uint32_t hi = __builtin_amdgcn_readfirstlane(c[0]);
+    if (hi == kServeLeave) return 1;
+    const uint32_t in = hi >> 16;
+    if ((hi & 0xFFFFu) == kServeBurstOp) {  // chunk 0 alone, the frames in the burst body
+      const uint32_t bn = min(max(in, 1u), kServeBurst);
+      const uint32_t st = lb_burst(a, T, box, bn, seq, lane);
+      if (lane == 0) burst_answer(io, box, st, bn, want);
+      if (st == kBurstServed) seq += bn;
+      t0 = wall_clock64();
+      done = want;
+      // (every lane's table writes before the next request reads them)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      return 0;
+    }
+    const uint32_t len = min(hi & 0xFFFFu, kServeFrame);
+    const bool inl = len <= kServeInline;
+    const uint32_t need = inl ? (12 + len + 11) / 12 : 1u;  // chunks carrying it
+    if (__ballot(lane < need && c[3] != want)) return -1;  // not whole yet: poll again
+    // chunk 0's time (message bytes 4-11), its words widened unsigned (as
+    // pol_serve: serve_now sign-extends a low word whose bit 31 is set)
+    const int64_t now =
+        (int64_t)((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(c[1]) |
+                  ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(c[2]) << 32));
+    const uint32_t nch = (len + 15) / 16;
+    if (inl) {
+      serve_chunks_in(fw, c, lane, need);
+    } else {  // the whole frame from `frame` (the host wrote it before the chunks)
+      for (uint32_t i = lane; i < nch; i += 64) {
+        const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(16 * i), 0, kSys);
+        fr[i] = make_uint4(v[0], v[1], v[2], v[3]);
+      }
+    }
+    wave_lds_sync();
+    // the L4 checksum's bytes past 64: [64, min(14 + total_length, len))
+    uint32_t tail = 0;
+    if (len > 64) {
+      const uint8_t *fb = reinterpret_cast<const uint8_t *>(fr);
+      const uint32_t tl = ((uint32_t)fb[16] << 8) | fb[17];
+      const uint32_t end = min(14 + tl, len);
+      for (uint32_t cc = 64 + 16 * lane; cc < end; cc += 1024)
+        tail = sum16x4(chunk_keep(fr[cc / 16], 0, (int)end - (int)cc), tail);
+      for (int o = 32; o > 0; o >>= 1) tail += __shfl_xor(tail, o);
+    }
+    uint32_t res = 0;
+    if (lane == 0) {
+      uint32_t fresh = 0, out = in, be = kLbPass;
+      RFrame f = serve_rframe([&](int j) { return fr[j]; }, len);
+      const uint32_t et = f.w[3] & 0xFFFF, ihl = (f.w[3] >> 16) & 0x0F;
+      if (et == 0x0008 && ihl == 5) {  // in registers (lb_main.c:27-38's tests)
+        const uint32_t tl = bswap16((uint16_t)(f.w[4] & 0xFFFF));
+        const uint16_t unread = (uint16_t)(len - 14);
+        const uint32_t proto = f.w[5] >> 24;
+        if ((unread >= 20) & (unread >= tl) & ((proto == 6) | (proto == 17)) &
+            ((uint32_t)(len - 34) >= 4u)) {
+          be = lb_one(a, T, in, f.u32at2(26), f.u32at2(30), f.w[8] >> 16, f.w[9] & 0xFFFF, proto,
+                      f.u32at2(6), f.w[2] >> 16, now, seq, &fresh);
+          if (be < kLbDecline) {
+            uint32_t rew = 0;
+            out = lb_serve_rewrite(a, f, a.be_rec[be], proto, tl, tail, &rew);
+            if (rew) {
+#pragma unroll
+              for (int j = 0; j < 4; j++)
+                fr[j] = make_uint4(f.w[4 * j], f.w[4 * j + 1], f.w[4 * j + 2], f.w[4 * j + 3]);
+            }
+          }
+        }
+      } else {  // byte-addressed over the LDS copy (IPv4 options)
+        const GFrame g{reinterpret_cast<uint8_t *>(fr), len};
+        const L34 l = parse_l34(g, len);
+        if (l.ok) {
+          be = lb_one(a, T, in, g.r32(l.ip + 12), g.r32(l.ip + 16), g.r16(l.l4), g.r16(l.l4 + 2),
+                      g.r8(l.ip + 9), g.r32(6), g.r16(10), now, seq, &fresh);
+          if (be < kLbDecline) {
+            const uint4 rec = a.be_rec[be];
+            out = rec.z >> 16;
+            if (out != a.wan) {
+              g.w32(l.ip + 16, rec.x);
+              uint32_t mw[3];
+              backend_macs(a, rec, out, mw);
+              set_macs(g, mw);
+              set_checksums(g, l.ip, l.l4);  // (the whole frame is in g)
+            }
+          }
+        }
+      }
+      res = (out & 0xFFFFu) | ((fresh & 1u) << 16) | ((fresh >> 1) << 18) |
+            (be == kLbDecline ? kOneDeclined : 0u);
+    }
+    wave_lds_sync();
+    res = __builtin_amdgcn_readfirstlane(res);
+    if (inl) {  // the answer chunks: the result and the frame in one store
+      if (lane < need) {
+        const v4u v = lane == 0 ? (v4u){res, 0u, 0u, want}
+                                : (v4u){fw[3 * lane - 3], fw[3 * lane - 2], fw[3 * lane - 1], want};
+        __builtin_amdgcn_raw_buffer_store_b128(v, io.as, (int)(16 * lane), 0, kSys);
+      }
+    } else {
+      for (uint32_t i = lane; i < nch; i += 64) {
+        const uint4 v = fr[i];
+        __builtin_amdgcn_raw_buffer_store_b128((v4u){v.x, v.y, v.z, v.w}, rs, (int)(16 * i), 0,
+                                               kSys);
+      }
+      // (the frame complete before the answer chunk that announces it)
+      __atomic_signal_fence(__ATOMIC_SEQ_CST);
+      __builtin_amdgcn_s_waitcnt(0);
+      __atomic_signal_fence(__ATOMIC_SEQ_CST);
+      if (lane == 0)
+        __builtin_amdgcn_raw_buffer_store_b128((v4u){res, 0u, 0u, want}, io.as, 0, 0, kSys);
+    }
+    if (lane == 0) {
+      // (the answer word: where a relaunched server starts counting; the host
+      // reads the answer chunks. No release fence at system scope, which would
+      // write back the whole L2)
+      __hip_atomic_store(&box->ans, (uint64_t)want | ((uint64_t)res << 32), __ATOMIC_RELAXED,
+                         __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    if (!(res & kOneDeclined)) seq += 1;
+    t0 = wall_clock64();
+    done = want;
+    // (lane 0's table writes before the next request's lanes read them)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    wave_lds_sync();
+    return 0;
+  };
+  serve_poll(io, flags, idle, serve, [&] { return t0; });
+}
+
 // =============================================================== host ==
 
 static inline int64_t lb_flow_cutoff(const vp_ctx *c, int64_t t) {
@@ -864,6 +1250,52 @@ static int lb_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
 int lb_process_device(vp_ctx *c, const vp_dev_batch *b) {
   ExpiringTable tabs[2] = {{&c->ft, lb_flow_cutoff}, {&c->ft2, lb_backend_cutoff}};
   return run_batch(c, b, tabs, 2, lb_segment);
+}
+
+// ---------------------------------------------------- vp_process_one --
+// viglb's launcher of the resident kernel (serve_launch, vp_serve.hip): of
+// LbArgs what lb_serve reads -- both tables, the backend records, the CHT, the
+// CRC tables and the devices' MACs; the batch's fields stay empty.
+int lb_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
+  LbArgs a{};
+  a.ft = tbl_dev(c->ft);
+  a.bt = tbl_dev(c->ft2);
+  a.be_rec = c->be_rec;
+  a.cht = c->cht;
+  a.height = c->lb.cht_height;
+  a.bcap = c->lb.backend_capacity;
+  a.crc_tab = c->crc_tab;
+  a.dmacw = c->dmacw;
+  a.wan = c->lb.wan_device;
+  a.n_dev = c->lb.n_devices;
+  lb_serve<<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags);
+  VP_HIP(hipGetLastError());
+  return 0;
+}
+
+// The largest host batch routed to the server as burst requests: the largest
+// swept n at which the served path measured faster per packet than the batch
+// pipeline on the MI355X (profiles/r12_lb_serve.txt: 0.30 against 1.07-1.10
+// us at 64, 0.296-0.299 against 0.553-0.560 at 128; at 256 the pipeline wins,
+// 0.284-0.289 against 0.296-0.298, and by more at 384 and 512); larger calls
+// take the pipeline. Below the other servers' 256 to 512: a served viglb frame
+// crosses whole and 64 bytes of it come back, which costs 0.30 us per packet
+// whatever the burst, and steady traffic costs viglb's pipeline no sort.
+// VIGPATH_SERVE_BURST overrides it; 0 routes nothing.
+constexpr uint32_t kLbBurstRoute = 128;
+
+// viglb through the mailbox (serve_process_one / serve_process_burst,
+// vp_serve.hip). The transfer sizes are vignat's: a rewrite changes bytes 0-11
+// and 24-25, 30-33, 40-41 or 50-51, and the L4 checksum is recomputed over
+// [34, 14 + total_length), so the whole frame goes, one longer than
+// kServeInline through `frame`, and a burst's frame comes back in its first 64
+// bytes. Two expiring tables: requests go only while no expiry is due on the
+// flows or on the backends. No stage clock.
+const ServeNf &lb_serve_nf() {
+  static const ServeNf nf = {lb_flow_cutoff, &vp_ctx::ft,   true,          kServeInline,
+                             kServeInline,   kServeFrame,   64,            kLbBurstRoute,
+                             false,          lb_backend_cutoff, &vp_ctx::ft2};
+  return nf;
 }
 
 void build_lb_tables(std::vector<uint32_t> &tab) {

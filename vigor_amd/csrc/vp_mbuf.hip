@@ -787,6 +787,19 @@ static int mbuf_host_pipeline(vp_ctx *c, const vp_mbuf_batch *b, const MbufPlan 
   return 0;
 }
 
+// A host batch through the batch pipeline, the resident kernel stopped first
+// (vp_process_mbufs past the routing; vp_process_one for a packet the server
+// did not take, which a burst request of one would only be refused again).
+int mbufs_unserved(vp_ctx *c, const vp_mbuf_batch *b) {
+  if (hipSetDevice(c->gpu) != hipSuccess) return VP_EIO;
+  VP_TRY(serve_stop(c));
+  if (b->n == 0 && !c->comm) return 0;
+  const MbufPlan pl = mbuf_plan(c);
+  if (pl.header && !c->comm && mbuf_mode_host()) return mbuf_host_pipeline(c, b, pl);
+  if (c->hmaps.empty()) return staged_range(c, b, 0, b->n);
+  return mbuf_pipeline(c, b);
+}
+
 }  // namespace vp
 
 using namespace vp;
@@ -870,7 +883,7 @@ int vp_process_mbufs(vp_ctx *c, const vp_mbuf_batch *b) {
   vp_mbuf_batch rest;
   const ServeNf *nf = serve_nf(c->kind);
   if (nf && b->n) {
-    // a small vignat, vigfw, vigbridge or vigpol burst goes to the resident kernel, which stays
+    // a small burst goes to the NF's resident kernel, which stays
     // (no hipSetDevice: a served burst makes no HIP call, as vp_process_one)
     uint32_t done = 0;
     const int rc = serve_process_burst(c, *nf, b, 0, b->n, &done);
@@ -886,13 +899,7 @@ int vp_process_mbufs(vp_ctx *c, const vp_mbuf_batch *b) {
       b = &rest;
     }
   }
-  if (hipSetDevice(c->gpu) != hipSuccess) return VP_EIO;
-  VP_TRY(serve_stop(c));
-  if (b->n == 0 && !c->comm) return 0;
-  const MbufPlan pl = mbuf_plan(c);
-  if (pl.header && !c->comm && mbuf_mode_host()) return mbuf_host_pipeline(c, b, pl);
-  if (c->hmaps.empty()) return staged_range(c, b, 0, b->n);
-  return mbuf_pipeline(c, b);
+  return mbufs_unserved(c, b);
 }
 
 int vp_process_batch(vp_ctx *c, uint32_t n, const uint16_t *in_dev, uint8_t *const *frames,

@@ -761,8 +761,18 @@ int vp_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, int
     // (no hipSetDevice here: a served packet makes no HIP call; the server's
     // launch and stop set the device themselves)
     const int rc = serve_process_one(c, *nf, in_dev, frame, len, now, out_dev);
-    if (rc <= 0) return rc;  // (1: not eligible, the batch path below)
-    if (hipSetDevice(c->gpu) != hipSuccess) return VP_EIO;
+    if (rc <= 0) return rc;
+    // 1: not eligible or declined, and the server is stopped. Straight to the
+    // batch pipeline: a burst request of one would meet the same refusal
+    uint8_t *one[1] = {frame};
+    vp_mbuf_batch b{};
+    b.n = 1;
+    b.frames = one;
+    b.len = &len;
+    b.in_dev = &in_dev;
+    b.now = &now;
+    b.out_dev = out_dev;
+    return mbufs_unserved(c, &b);
   }
   uint8_t *frames[1] = {frame};
   return vp_process_batch(c, 1, &in_dev, frames, &len, &now, out_dev);

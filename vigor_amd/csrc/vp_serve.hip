@@ -1,7 +1,8 @@
 // vp_process_one's mailbox, host side (ServeBox, vp_internal.h), for any
 // context whose NF has a resident kernel -- vignat (nat_serve, vp_nat.hip),
-// vigfw (fw_serve, vp_fw.hip), vigbridge (bridge_serve, vp_bridge.hip) and
-// vigpol (pol_serve, vp_pol.hip). Launching the kernel, waiting for an answer,
+// vigfw (fw_serve, vp_fw.hip), vigbridge (bridge_serve, vp_bridge.hip),
+// vigpol (pol_serve, vp_pol.hip) and viglb (lb_serve, vp_lb.hip, the one with
+// two expiring tables). Launching the kernel, waiting for an answer,
 // relaunching after an idle exit, stopping it before any other entry point
 // touches the table, yielding the GPU's hardware queues between contexts, and
 // the requests themselves: one packet (serve_process_one) and a small burst
@@ -143,6 +144,9 @@ static int serve_launch(vp_ctx *c) {
     case KIND_POL:
       VP_TRY(pol_serve_launch(c, dbox, flags));
       break;
+    case KIND_LB:
+      VP_TRY(lb_serve_launch(c, dbox, flags));
+      break;
     default:
       return state_fail("no resident kernel for NF kind %d", c->kind);
   }
@@ -250,10 +254,14 @@ int serve_process_one(vp_ctx *c, const ServeNf &nf, uint16_t in_dev, uint8_t *fr
                       uint16_t len, int64_t now, uint16_t *out) {
   std::lock_guard<std::recursive_mutex> sg(c->srv_mu);
   FlowTable &t = c->*nf.table;
-  // no expiry due at this packet (run_batch's test for a segment of one)
+  FlowTable *t2 = nf.table2 ? &(c->*nf.table2) : nullptr;
+  // no expiry due at this packet on either table (run_batch's test for a
+  // segment of one, each table against its own floor)
   const bool ok = !serve_off() && !c->comm && len <= kServeFrame && now >= 0 &&
                   now >= c->last_now &&
-                  nf.cutoff(c, now) <= (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)now);
+                  nf.cutoff(c, now) <= (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)now) &&
+                  (!t2 || nf.cutoff2(c, now) <=
+                              (int64_t)std::min<uint64_t>(t2->ts_floor, (uint64_t)now));
   if (!ok) {
     VP_TRY(serve_stop(c));
     return 1;
@@ -276,13 +284,19 @@ int serve_process_one(vp_ctx *c, const ServeNf &nf, uint16_t in_dev, uint8_t *fr
   // many as the request took, chunk 1 alone (bytes 0-11), or none
   const uint32_t back = std::min(got, nf.one_back);
   VP_TRY(serve_wait(c, req, 1 + (back + 11) / 12));
-  const uint32_t res = bx->amsg[0][0];  // out | fresh << 16
+  const uint32_t res = bx->amsg[0][0];  // out | fresh << 16 | kOneFresh2 | kOneDeclined
+  if (res & kOneDeclined) {  // nothing of it was done: the batch path, as an ineligible one
+    c->srv_stats.declined += 1;
+    VP_TRY(serve_stop(c));
+    return 1;
+  }
   if (via_frame)
     memcpy(frame, bx->frame, len);
   else
     serve_unpack(bx, frame, back);
   *out = (uint16_t)res;
   if ((res >> 16) & 1u) t.ts_floor = std::min<uint64_t>(t.ts_floor, (uint64_t)now);
+  if (t2 && (res & kOneFresh2)) t2->ts_floor = std::min<uint64_t>(t2->ts_floor, (uint64_t)now);
   c->seq += 1;
   c->last_now = now;
   c->srv_stats.packets_one += 1;
@@ -313,6 +327,8 @@ int serve_process_burst(vp_ctx *c, const ServeNf &nf, const vp_mbuf_batch *b, ui
     prev = ti;
   }
   if (nf.cutoff(c, n1) > (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)n0)) return 1;
+  FlowTable *t2 = nf.table2 ? &(c->*nf.table2) : nullptr;  // (the same, on its own floor)
+  if (t2 && nf.cutoff2(c, n1) > (int64_t)std::min<uint64_t>(t2->ts_floor, (uint64_t)n0)) return 1;
   VP_TRY(serve_ready(c));
   ServeBox *bx = c->sbox;
   for (uint32_t a0 = 0; a0 < count; a0 += kServeBurst) {
@@ -333,16 +349,18 @@ int serve_process_burst(vp_ctx *c, const ServeNf &nf, const vp_mbuf_batch *b, ui
       c->srv_stats.declined += 1;
       return 1;
     }
-    bool fresh = false;
+    bool fresh = false, fresh2 = false;
     for (uint32_t i = 0; i < m; i++) {
       const uint32_t p = first + a0 + i, r = bx->bout[i];
       b->out_dev[p] = (uint16_t)r;
       fresh |= (r >> 16) & 1u;
+      fresh2 |= (r & kOneFresh2) != 0;
       // (only rewritten frames come back, and only the bytes a rewrite can change)
       if ((r >> 17) & 1u)
         memcpy(b->frames[p], bx->bframe[i], std::min<uint32_t>(b->len[p], nf.burst_back));
     }
     if (fresh) t.ts_floor = std::min<uint64_t>(t.ts_floor, (uint64_t)at(a0));
+    if (t2 && fresh2) t2->ts_floor = std::min<uint64_t>(t2->ts_floor, (uint64_t)at(a0));
     c->seq += m;
     c->last_now = at(a0 + m - 1);
     c->srv_stats.bursts += 1;

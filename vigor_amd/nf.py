@@ -277,9 +277,10 @@ class NfBase:
         return step
 
     def process(self, device: int, buffer: bytearray, now: int) -> int:
-        """nf_process for one packet (nf.h:13): vp_process_one (vignat, vigfw,
-        vigbridge and vigpol on one GPU: the persistent kernel's mailbox, no
-        launch per packet; viglb: a one-packet batch)."""
+        """nf_process for one packet (nf.h:13): vp_process_one (on one GPU the
+        NF's persistent kernel's mailbox, no launch per packet; a one-packet
+        batch where an expiry is due, and for the packet viglb's kernel hands
+        back: the erasure of a flow while no backend is alive)."""
         a = (C.c_uint8 * len(buffer)).from_buffer(buffer)
         out = C.c_uint16(device)
         self._ck(self.L.vp_process_one(self.h, device, C.cast(a, C.c_void_p), len(buffer),
@@ -287,11 +288,11 @@ class NfBase:
         return int(out.value)
 
     def serve_stats(self) -> dict:
-        """vp_serve_stats_get: what the resident kernel served so far (vignat,
-        vigfw, vigbridge and vigpol; all zeros for viglb) -- packets_one
-        (vp_process_one), bursts / burst_packets (small vp_process_batch /
-        vp_process_mbufs calls), declined, launches. A host-side counter
-        read: the kernel stays."""
+        """vp_serve_stats_get: what the NF's resident kernel served so far --
+        packets_one (vp_process_one), bursts / burst_packets (small
+        vp_process_batch / vp_process_mbufs calls), declined (requests handed
+        back to the pipeline: a burst with IPv4 options, viglb's erasure of a
+        flow), launches. A host-side counter read: the kernel stays."""
         st = ServeStatsC()
         self._ck(self.L.vp_serve_stats_get(self.h, C.byref(st)), "vp_serve_stats_get")
         return {k: int(getattr(st, k)) for k, _ in ServeStatsC._fields_}
