@@ -201,7 +201,14 @@ int vp_unregister_host(vp_ctx *ctx, void *base);
  * burst requests of up to 64 frames, one lane of a wave per packet, while no
  * expiry is due anywhere in the call (viglb: on its flows or its backends), every frame is at most 2048 bytes
  * and the times do not go back: no launch, no copy call, and the kernel stays
- * for the next call (nf.c's VIGOR_BATCH_SIZE loop, nf.c:178-215). A burst
+ * for the next call (nf.c's VIGOR_BATCH_SIZE loop, nf.c:178-215). vignat and
+ * vigfw hand over only the first call at which an expiry is due: from the
+ * next one on their kernel expires the entries itself before each request
+ * (vp_serve_expiry_stats_get), and a burst inside which an expiry falls due
+ * is served up to that packet and the rest posted as the next request.
+ * VIGPATH_SERVE_EXPIRE=0 turns that off (every due expiry takes the path
+ * above); VIGPATH_SERVE_JOURNAL sets the journal's size in records per table
+ * index (default 8, at least 2). A burst
  * holding a frame with IPv4 options is handed back and takes the path above
  * (vp_serve_stats_get counts both); vigbridge, which reads only the MACs,
  * and vigpol, which never parses L4, hand none back. vigpol's packets to one
@@ -236,7 +243,10 @@ int vp_process_batch(vp_ctx *ctx, uint32_t n, const uint16_t *in_dev,
  * kernel that polls a host-coherent mailbox (no launch per packet) while no
  * expiry is due at `now`; otherwise, and for the one packet viglb's kernel
  * hands back (the erasure of a flow with no backend alive), it is
- * vp_process_batch with n = 1.
+ * vp_process_batch with n = 1. vignat and vigfw take that path only for the
+ * first packet at which an expiry is due: afterwards the kernel expires the
+ * entries itself, before the packet, and stays (vp_serve_expiry_stats_get;
+ * VIGPATH_SERVE_EXPIRE=0: off).
  * The kernel leaves after VIGPATH_SERVE_IDLE_MS (default 20) without a
  * packet, at any other call on the context -- except a vp_process_batch /
  * vp_process_mbufs call small enough to be served by it as a burst -- and at
@@ -379,6 +389,23 @@ typedef struct vp_serve_stats {
   uint64_t launches;      /* launches of the resident kernel */
 } vp_serve_stats;
 int vp_serve_stats_get(vp_ctx *ctx, vp_serve_stats *out);
+
+/* Expiry inside the resident kernel (vignat and vigfw; all zero for the other
+ * NFs), since the context was created. The first request at which an expiry
+ * is due takes the batch pipeline (`handed`); the next launch builds a touch
+ * journal from the table (`seeds`) and from then on the kernel expires entries
+ * itself, in the reference's LRU order, before every request. A pipeline call
+ * that processes packets (a large batch, a declined burst) drops the journal:
+ * the next due expiry is handed over once more and seeds it again. A read of
+ * host-side counters: the kernel stays. */
+typedef struct vp_serve_expiry_stats {
+  uint64_t seeds;    /* journal builds from the table (first and re-seeds) */
+  uint64_t expired;  /* entries the resident kernel expired */
+  uint64_t walks;    /* requests at which it expired at least one */
+  uint64_t handed;   /* requests that took the pipeline because an expiry was due */
+  uint64_t splits;   /* burst requests served in part (rest re-posted) */
+} vp_serve_expiry_stats;
+int vp_serve_expiry_stats_get(vp_ctx *ctx, vp_serve_expiry_stats *out);
 
 /* Why the calling thread's last failing vp_* call failed: the HIP error and
  * the call site for VP_EIO / VP_ENOMEM, the broken invariant for VP_ESTATE

@@ -11,6 +11,15 @@ and through vp_process_batch in bursts (nf.c:178-215).
   tools/bench_dropin.py --nf bridge                  # vigbridge: 1,024 stations
   tools/bench_dropin.py --nf pol                     # vigpol: 1,024 policed addresses
   tools/bench_dropin.py --nf lb                      # viglb: 256 backends, 1,024 flows
+  tools/bench_dropin.py --nf nat --churn --batches 0,32   # flows expiring all along
+
+--churn (vignat, vigfw): every 16th timed packet opens a never-seen flow and
+the others hit the `--flows` most recent flows round robin, so the oldest flow
+goes idle each time; the clock advances 1 us a packet and `--expire` is four
+round-robin turns (4 x flows us), so in steady state about one flow expires
+every 16 packets while no flow that is still hit does. The table holds 2 x
+flows. VIGPATH_SERVE_EXPIRE=0 in the environment gives the path that hands
+every due expiry to the batch pipeline.
 
 --sweep N,...: each burst size twice in this run, VIGPATH_SERVE_BURST forcing
 the resident kernel (a limit above every N) and the batch pipeline (0): the
@@ -56,6 +65,20 @@ def lan_port(n, flows):
     """vigpol: every steady packet arrives on the WAN device, finds its
     address's bucket full enough and goes out on the LAN device."""
     return np.ones(n, np.uint16)
+
+
+def churn_trace(n, flows):
+    """--churn: `flows` flows opened by the warm-up, then packet p of the
+    timed part opens flow flows + p / 16 when p is a multiple of 16 and else
+    hits one of the `flows` newest flows, round robin; 1 us a packet."""
+    p = np.arange(n - flows, dtype=np.int64)
+    newest = flows - 1 + (p // 16 + 1)  # (the newest flow once packet p has been seen)
+    hit = newest - flows + 1 + (p - p // 16) % flows
+    fl = np.concatenate([np.arange(flows, dtype=np.int64), np.where(p % 16 == 0, newest, hit)])
+    z = np.zeros_like(fl)
+    frames, lens = T.udp_frames(T.ip4(10, 0, 0, 0) + (fl >> 16), z, fl & 0xFFFF, z, slot=SLOT)
+    now = T.NOW0 + 1000 * np.arange(n, dtype=np.int64)
+    return frames, lens, np.zeros(n, np.uint16), now
 
 
 LB_BACKENDS = 256
@@ -105,13 +128,17 @@ NF = {
 }
 
 
-def run_loop(tree, nf, tin, tout, flows, batch, env):
+def run_loop(tree, nf, tin, tout, flows, batch, env, churn=False):
     """One nf_loop run: us per timed packet (its out ports are left in tout)."""
     cmd = [os.path.join(tree, "host", NF[nf]["loop"]), tin, tout, "--warm",
            str(flows + NF[nf].get("warm", 0))]
     if batch:
         cmd += ["--batch", str(batch)]
-    cmd += ["--"] + NF[nf]["args"] + [NF[nf]["size"], str(flows)]
+    args, size = list(NF[nf]["args"]), flows
+    if churn:  # four round-robin turns of 1 us packets; room for the idle flows
+        args[args.index("--expire") + 1] = str(4 * flows)
+        size = 2 * flows
+    cmd += ["--"] + args + [NF[nf]["size"], str(size)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300,
                        env=dict(os.environ, **NF[nf].get("env", {}), **env))
     if r.returncode != 0:
@@ -129,12 +156,16 @@ def main():
     ap.add_argument("--batches", default="0,32,1024")
     ap.add_argument("--sweep", default="", help="burst sizes, each served and through the pipeline")
     ap.add_argument("--repeat", type=int, default=3, help="runs per point (all reported)")
+    ap.add_argument("--churn", action="store_true",
+                    help="vignat, vigfw: a flow expires about every 16 packets")
     ap.add_argument("--tree", default=ROOT)
     ap.add_argument("--label", default="")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     n = a.flows + a.packets
-    fr, ln, dv, now = NF[a.nf]["trace"](n, a.flows)
+    if a.churn and a.nf not in ("nat", "fw"):
+        ap.error("--churn: vignat and vigfw only")
+    fr, ln, dv, now = (churn_trace if a.churn else NF[a.nf]["trace"])(n, a.flows)
     steady = NF[a.nf]["steady"](n, a.flows)
     n, warm = len(ln), len(ln) - a.packets  # (viglb: the heartbeats ahead of the flows)
     points = []
@@ -153,12 +184,12 @@ def main():
         for bt, path, env in points:
             us = []
             for _ in range(a.repeat):
-                us.append(run_loop(a.tree, a.nf, tin, tout, a.flows, bt, env))
+                us.append(run_loop(a.tree, a.nf, tin, tout, a.flows, bt, env, a.churn))
                 out = np.frombuffer(open(tout, "rb").read(), np.uint16, n, 12)
                 # every steady packet out where expected
                 assert (out[warm:] < 2).all() if steady is None else \
                     (out[warm:] == steady[a.flows:]).all()
-            rec = {"nf": a.nf, "label": a.label, "batch": bt, "path": path,
+            rec = {"nf": a.nf, "label": a.label, "batch": bt, "path": path, "churn": a.churn,
                    "packets": a.packets, "flows": a.flows,
                    "us_per_packet": [round(x, 3) for x in us],
                    "us_per_packet_min": round(min(us), 3)}

@@ -46,6 +46,13 @@ class ServeStatsC(C.Structure):
                 ("launches", C.c_uint64)]
 
 
+class ServeExpiryStatsC(C.Structure):
+    """vp_serve_expiry_stats (include/vigpath.h)."""
+    _fields_ = [("seeds", C.c_uint64), ("expired", C.c_uint64),
+                ("walks", C.c_uint64), ("handed", C.c_uint64),
+                ("splits", C.c_uint64)]
+
+
 MacTable = (C.c_uint8 * 6) * MAX_DEV
 
 
@@ -134,7 +141,8 @@ EXPORTS = ["vp_nat_create", "vp_bridge_create", "vp_lb_create", "vp_fw_create",
            "vp_kernel_timing", "vp_last_kernel_ms", "vp_version", "vp_table_stats_get",
            "vp_last_error", "vp_register_host", "vp_unregister_host", "vp_process_mbufs",
            "vp_last_stage_ms", "vp_stage_ms", "vp_comm_abort", "vp_probe_slots",
-           "vp_probe_slots_w", "vp_process_one", "vp_last_kernel", "vp_serve_stats_get"]
+           "vp_probe_slots_w", "vp_process_one", "vp_last_kernel", "vp_serve_stats_get",
+           "vp_serve_expiry_stats_get"]
 
 _libs = {}
 
@@ -233,6 +241,8 @@ def lib(path: str | None = None):
     L.vp_table_stats_get.restype = C.c_int
     L.vp_serve_stats_get.argtypes = [C.c_void_p, C.POINTER(ServeStatsC)]
     L.vp_serve_stats_get.restype = C.c_int
+    L.vp_serve_expiry_stats_get.argtypes = [C.c_void_p, C.POINTER(ServeExpiryStatsC)]
+    L.vp_serve_expiry_stats_get.restype = C.c_int
     L.vp_last_error.argtypes = []
     L.vp_last_error.restype = C.c_char_p
     _libs[path] = L

@@ -384,10 +384,11 @@ __global__ void fw_defer_finish(FwArgs a, const uint32_t *list, uint32_t n) {
 // each call costs a launch sequence and a host round trip; vp_process_one and
 // small vp_process_mbufs calls instead go to fw_serve, one wave that stays
 // resident and polls the host-coherent mailbox (ServeBox, vp_internal.h), as
-// nat_serve does for vignat: no launch and no copy call per packet. The host
-// sends requests only while no expiry is due (serve_process_one /
-// serve_process_burst), so the kernel restates fw_main.c:21-80 without the
-// expiry step.
+// nat_serve does for vignat: no launch and no copy call per packet. Until the
+// context meets a due expiry the host sends requests only while none is due
+// (serve_process_one / serve_process_burst) and the kernel restates
+// fw_main.c:21-80 without the expiry step; from then on it runs that step
+// too, from the touch journal (serve_expire, vp_serve_dev.h).
 
 // The FlowId a packet looks up (fw_key) and its hash from the LDS tables.
 __device__ __forceinline__ uint32_t fw_key_hash(const uint32_t *T, bool wan, uint32_t sp,
@@ -417,7 +418,7 @@ __device__ __forceinline__ uint32_t fw_one_lan(const TableDev &t, uint32_t hh,
 __device__ __forceinline__ uint32_t fw_one_flow(const FwArgs &a, const uint32_t *T, uint32_t in,
                                                 uint32_t sp, uint32_t dp, uint32_t sip,
                                                 uint32_t dip, uint32_t proto, int64_t now,
-                                                uint64_t seq, uint32_t *fresh) {
+                                                uint64_t seq, uint32_t *fresh, uint32_t *tix) {
   const bool wan = in == a.wan;
   uint32_t key[4];
   const uint32_t hh = fw_key_hash(T, wan, sp, dp, sip, dip, proto, key);
@@ -431,18 +432,29 @@ __device__ __forceinline__ uint32_t fw_one_flow(const FwArgs &a, const uint32_t 
     idx = fw_one_lan(a.t, hh, key, in, seq, fresh);
   }
   if (idx != kNone) serve_stamp(a.t, idx, now, seq);
+  *tix = idx;  // (the index the packet touched, for the journal)
   return dst;
 }
 
 // A burst request (vp_serve_dev.h) for vigfw: a WAN lane that looks again
 // probes the table. Only the first 64 bytes of a frame are read and only its
-// first 16 can change.
+// first 16 can change. With the journal on (J) the expiries due at the first
+// packet run first and *k <= n packets are served (burst_split).
+template <bool J>
 __device__ __forceinline__ uint32_t fw_burst(const FwArgs &a, const uint32_t *T, ServeBox *box,
-                                             uint32_t n, uint64_t seq0, uint32_t lane) {
+                                             uint32_t n, uint64_t seq0, uint32_t lane,
+                                             const JournalDev &j, JournalSt &js, uint32_t *k) {
   const TableDev &t = a.t;
   const BurstIn b = burst_load(box, n, lane);
-  const BurstHdr h = burst_hdr(b);  // fw_issue's tests (fw_main.c:26-40)
+  BurstHdr h = burst_hdr(b);  // fw_issue's tests (fw_main.c:26-40)
   if (h.decline) return kBurstDeclined;
+  int64_t now0 = 0;
+  if (J) {
+    n = burst_split(t, j, js, b, n, lane, &now0);
+    if (!n) return kBurstFull;
+    h.go = h.go && lane < n;
+  }
+  *k = n;
   const uint32_t in = b.in;
   const bool wan = in == a.wan;
   const bool lanp = h.go && !wan, wanp = h.go && wan;
@@ -455,7 +467,9 @@ __device__ __forceinline__ uint32_t fw_burst(const FwArgs &a, const uint32_t *T,
       lane, lanp && idx == kNone, wanp && idx == kNone,
       [&] { idx = tbl_probe<0xFFu>(t, hh, key, &w3); },
       [&] { idx = fw_one_lan(t, hh, key, in, seq0 + lane, &fresh); });
-  if (burst_last(idx, n, lane)) serve_stamp(t, idx, b.now, seq0 + lane);
+  const bool won = burst_last(idx, n, lane);
+  if (won) serve_stamp(t, idx, b.now, seq0 + lane);
+  if (J) journal_touch_burst(j, js, won, idx, seq0 + lane, now0, lane);
   // the rewrite: a LAN packet goes out on the WAN device with or without a
   // flow (fw_flowmanager.c:49-53), a WAN packet to its flow's internal device
   uint32_t out = in, rew = 0;
@@ -483,8 +497,11 @@ __device__ __forceinline__ uint32_t fw_burst(const FwArgs &a, const uint32_t *T,
 // a burst request (fw_burst) takes as many as it has frames. The kernel
 // leaves on the leave request or after `idle` wall-clock ticks without a
 // request; the host launches it again (serve_wait). flags: serve_poll's.
+// J: the kernel expires from the touch journal j (vp_serve_dev.h); a context
+// whose journal is off runs the instance without any of it.
+template <bool J>
 __global__ __launch_bounds__(64) void fw_serve(FwArgs a, ServeBox *box, uint64_t seq0,
-                                               uint64_t idle, uint32_t flags) {
+                                               uint64_t idle, uint32_t flags, JournalDev j) {
   __shared__ uint32_t T[kFwTabWords];
   __shared__ uint4 fr[(kServeInline + 15) / 16];
   const uint32_t lane = threadIdx.x;
@@ -498,17 +515,22 @@ __global__ __launch_bounds__(64) void fw_serve(FwArgs a, ServeBox *box, uint64_t
       &box->ans, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM));
   uint64_t seq = seq0;
   uint64_t t0 = wall_clock64();
+  // the touch journal's control words
+  JournalSt js = journal_load(J ? j : JournalDev{});
   auto serve = [&](const v4u &c) -> int {
     const uint32_t want = done + 1;
     if (__builtin_amdgcn_readfirstlane(c[3]) != want) return -1;
     const uint32_t hi = __builtin_amdgcn_readfirstlane(c[0]);
     if (hi == kServeLeave) return 1;
     const uint32_t in = hi >> 16;
+    js.expired = 0, js.flags = 0;
     if ((hi & 0xFFFFu) == kServeBurstOp) {  // chunk 0 alone, the frames in the burst body
-      const uint32_t bn = min(max(in, 1u), kServeBurst);
-      const uint32_t st = fw_burst(a, T, box, bn, seq, lane);
-      if (lane == 0) burst_answer(io, box, st, bn, want);
-      if (st == kBurstServed) seq += bn;
+      uint32_t bn = min(max(in, 1u), kServeBurst);
+      uint32_t st = fw_burst<J>(a, T, box, bn, seq, lane, j, js, &bn);
+      if (J && st == kBurstServed && js.flags) st |= kBurstTombs;
+      if (J) journal_store(j, js, lane);
+      if (lane == 0) burst_answer(io, box, st, bn, want, js.expired);
+      if ((st & 0xFFu) == kBurstServed) seq += bn;
       t0 = wall_clock64();
       done = want;
       // (every lane's table writes before the next request reads them)
@@ -523,8 +545,11 @@ __global__ __launch_bounds__(64) void fw_serve(FwArgs a, ServeBox *box, uint64_t
     const int64_t now = serve_now(c);
     serve_chunks_in(fword, c, lane, need);
     wave_lds_sync();
-    uint32_t res = 0, m0 = 0, m1 = 0, m2 = 0;
-    if (lane == 0) {
+    uint32_t res = 0, m0 = 0, m1 = 0, m2 = 0, tix = kNone;
+    const bool full = J && !journal_room(j, js, 1);  // (nothing is done: seeded again)
+    if (J && !full) serve_expire(a.t, j, js, journal_cutoff(j, now), lane);
+    if (full) res = kOneFull;
+    if (lane == 0 && !full) {
       const RFrame f = serve_rframe([&](int j) { return fr[j]; }, len);
       const uint32_t et = f.w[3] & 0xFFFF, ihl = (f.w[3] >> 16) & 0x0F;
       uint32_t sp = 0, dp = 0, sip = 0, dip = 0, proto = 0;
@@ -550,7 +575,7 @@ __global__ __launch_bounds__(64) void fw_serve(FwArgs a, ServeBox *box, uint64_t
       }
       uint32_t fresh = 0;
       const uint32_t dst =
-          ok ? fw_one_flow(a, T, in, sp, dp, sip, dip, proto, now, seq, &fresh) : kNone;
+          ok ? fw_one_flow(a, T, in, sp, dp, sip, dip, proto, now, seq, &fresh, &tix) : kNone;
       m0 = f.w[0], m1 = f.w[1], m2 = f.w[2];
       uint32_t out = in;
       if (dst != kNone) {  // fw_main.c:76-77
@@ -559,15 +584,19 @@ __global__ __launch_bounds__(64) void fw_serve(FwArgs a, ServeBox *box, uint64_t
         m0 = mw[0], m1 = mw[1], m2 = mw[2];
         out = dst;
       }
-      res = (out & 0xFFFFu) | (fresh << 16);
+      res = (out & 0xFFFFu) | (fresh << 16) | js.flags;
     }
     res = __builtin_amdgcn_readfirstlane(res);
+    if (J) {
+      journal_touch(j, js, __builtin_amdgcn_readfirstlane(tix), seq, now, lane);
+      journal_store(j, js, lane);
+    }
     m0 = __builtin_amdgcn_readfirstlane(m0);
     m1 = __builtin_amdgcn_readfirstlane(m1);
     m2 = __builtin_amdgcn_readfirstlane(m2);
     // the answer chunks: the result and frame bytes 0-11, one store
     if (lane < min(need, 2u)) {
-      const v4u v = lane == 0 ? (v4u){res, 0u, 0u, want} : (v4u){m0, m1, m2, want};
+      const v4u v = lane == 0 ? (v4u){res, js.expired, 0u, want} : (v4u){m0, m1, m2, want};
       __builtin_amdgcn_raw_buffer_store_b128(v, io.as, (int)(16 * lane), 0, kSys);
     }
     // (the answer word: where a relaunched server starts counting; the host
@@ -576,7 +605,7 @@ __global__ __launch_bounds__(64) void fw_serve(FwArgs a, ServeBox *box, uint64_t
     if (lane == 0)
       __hip_atomic_store(&box->ans, (uint64_t)want | ((uint64_t)res << 32), __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_SYSTEM);
-    seq += 1;
+    if (!full) seq += 1;
     t0 = wall_clock64();
     done = want;
     // (lane 0's table writes before the next request's lanes read them)
@@ -720,7 +749,11 @@ int fw_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
   a.macw = c->macw;
   a.wan = c->fw.wan_device;
   a.n_dev = c->fw.n_devices;
-  fw_serve<<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags);
+  const JournalDev j = serve_journal_dev(c, fw_serve_nf());
+  if (j.ctl)
+    fw_serve<true><<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags, j);
+  else
+    fw_serve<false><<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags, j);
   VP_HIP(hipGetLastError());
   return 0;
 }
@@ -739,8 +772,8 @@ constexpr uint32_t kFwBurstRoute = 256;
 // takes back bytes 0-11; fw_burst reads a frame's first 64 bytes and 16 come
 // back.
 const ServeNf &fw_serve_nf() {
-  static const ServeNf nf = {fw_cutoff, &vp_ctx::ft, false, kServeInline, 12, 64, 16,
-                             kFwBurstRoute, false};
+  static const ServeNf nf = {fw_cutoff, &vp_ctx::ft,    false,   kServeInline, 12, 64, 16,
+                             kFwBurstRoute, false, nullptr, nullptr,      true};
   return nf;
 }
 

@@ -153,6 +153,18 @@ struct CtlPub {
   uint32_t epoch;
 };
 
+// The touch journal's control words, in device memory beside
+// the table and apart from Ctl, whose layout is published: the ring position
+// of the oldest record, the records from there to the head, and the cached
+// floor -- a lower bound of the live stamps (kJournalNone: nothing is live).
+// The resident kernel keeps them in registers and stores them back after
+// every request, so a relaunched kernel goes on from them.
+struct JournalCtl {
+  uint32_t tail, cnt;
+  int64_t floor;
+};
+constexpr int64_t kJournalNone = INT64_MAX;
+
 // One device table (see vp_table.h).
 struct FlowTable {
   Bucket *bk = nullptr;
@@ -200,6 +212,14 @@ struct FlowTable {
   // expiry workspace (sized cap)
   uint64_t *ekey = nullptr, *ekey2 = nullptr;
   uint32_t *eidx = nullptr, *eidx2 = nullptr;
+  // touch journal of the resident kernel (vp_table.h Journal; allocated by the
+  // first tbl_journal_seed): its control words, its ring of jr_n records, and
+  // whether it describes the table (a pipeline call that processes packets
+  // turns it off: run_batch)
+  JournalCtl *jr = nullptr;
+  uint4 *jrec = nullptr;
+  uint32_t jr_n = 0;
+  bool jr_on = false;
   // owner-sharded mode (vp_shard_mode): this rank's buckets
   // hold only the keys it owns; key by index is replicated in kv
   uint4 *kv = nullptr;
@@ -395,6 +415,16 @@ struct ServeBox {
 constexpr uint32_t kServeBurst = 64;       // frames per burst request
 constexpr uint32_t kServeBurstOp = 0xFFFFu;  // message word 0, low half: a burst
 constexpr uint32_t kBurstServed = 0, kBurstDeclined = 1;  // answer chunk 0, word 0
+// With the touch journal on (vignat, vigfw) a burst's answer chunk 0 is
+// {status, k, expired, request number}: k packets were served (the rest is
+// posted again: an expiry falls due at packet k), `expired` entries left
+// before them. kBurstFull: the journal has no room for the request's touches
+// and nothing was done (the host seeds it again); kBurstTombs, or-ed into a
+// served status: the table passed the purge bound (the host runs
+// tbl_check_tombs before the next request). A one-packet result carries the
+// same as kOneFull / kOneTombs, the expired count in answer chunk 0's word 1.
+constexpr uint32_t kBurstFull = 2, kBurstTombs = 0x100;
+constexpr uint32_t kOneFull = 1u << 20, kOneTombs = 1u << 21;
 // Beside `fresh` (bit 16) in a burst's out word and in a one-packet result:
 // an entry of the NF's second table was allocated (viglb: a backend).
 constexpr uint32_t kOneFresh2 = 1u << 18;
@@ -461,6 +491,9 @@ struct ServeNf {
   // lowers its floor
   int64_t (*cutoff2)(const vp_ctx *c, int64_t t) = nullptr;
   FlowTable vp_ctx::*table2 = nullptr;
+  // the resident kernel expires entries itself from a touch journal once the
+  // context has met a due expiry (vignat, vigfw; serve_journal_ok)
+  bool journal = false;
 };
 const ServeNf &nat_serve_nf();
 const ServeNf &fw_serve_nf();
@@ -501,6 +534,9 @@ void serve_free(vp_ctx *c);
 // saw the request). The caller holds c->srv_mu.
 int serve_ready(vp_ctx *c);
 int serve_wait(vp_ctx *c, uint32_t req, uint32_t need);
+// The journal's launch arguments for c's table (off: ctl == null).
+struct JournalDev;
+JournalDev serve_journal_dev(const vp_ctx *c, const ServeNf &nf);
 bool serve_off();   // VIGPATH_SERVE=0
 bool serve_prof();  // VIGPATH_SERVE_PROF (vignat's stage clock)
 // The largest host batch routed as burst requests: VIGPATH_SERVE_BURST, else
@@ -608,4 +644,8 @@ struct vp_ctx {
   std::recursive_mutex srv_mu;
   double srv_prof[11] = {};  // VIGPATH_SERVE_PROF: summed stage times (us), counts
   vp_serve_stats srv_stats{};  // vp_serve_stats_get (counted under srv_mu)
+  // the touch journal (vp_serve.hip): the last fallback was a due expiry, so
+  // the next launch seeds the journal; vp_serve_expiry_stats_get's counters
+  bool jr_want = false;
+  vp_serve_expiry_stats srv_exp{};
 };

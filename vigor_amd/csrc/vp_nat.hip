@@ -2008,9 +2008,11 @@ __global__ void nat_defer_finish(NatArgs a, const uint32_t *list, uint32_t n) {
 // Through the batch path one packet costs a launch sequence and a host round
 // trip per call (≈68 µs); vp_process_one instead hands it to
 // nat_serve, one wave that stays resident and polls a host-coherent mailbox
-// (ServeBox, vp_internal.h): no launch per packet. The host serves through it
-// only while no expiry is due (serve_process_one), so the kernel restates
-// nat_main.c:22-109 without the expiry step.
+// (ServeBox, vp_internal.h): no launch per packet. Until the context meets a
+// due expiry the host serves through it only while none is due
+// (serve_process_one) and the kernel restates nat_main.c:22-109 without the
+// expiry step; from then on it runs that step too, from the touch journal
+// (serve_expire, vp_serve_dev.h).
 
 // flow_manager_get_internal / allocate_flow (nat_main.c:68-97) for one LAN
 // key at global sequence seq: its index, allocated when new (serve_lan,
@@ -2038,7 +2040,8 @@ __device__ __forceinline__ bool one_wan(const NatArgs &a, uint32_t dp, int64_t n
 // length; IP options, odd headers): returns the output port.
 __device__ __forceinline__ uint32_t nat_one(const NatArgs &a, const uint32_t *T,
                                             const GFrame &f, uint32_t in, uint32_t len,
-                                            int64_t now, uint64_t seq, uint32_t *fresh) {
+                                            int64_t now, uint64_t seq, uint32_t *fresh,
+                                            uint32_t *tix) {
   const L34 h = parse_l34(f, len);
   if (!h.ok) return in;  // nat_main.c:30-38
   const uint32_t proto = f.r8(h.ip + 9);
@@ -2050,6 +2053,7 @@ __device__ __forceinline__ uint32_t nat_one(const NatArgs &a, const uint32_t *T,
     uint32_t ix;
     if (!one_wan(a, dp, now, seq, &k, &ix)) return in;
     serve_stamp(a.t, ix, now, seq);
+    *tix = ix;
     if ((k.z != sip) | ((k.x >> 16) != sp) | (((k.w >> 16) & 0xFF) != proto)) return in;
     f.w32(h.ip + 16, k.y);
     f.w16(h.l4 + 2, (uint16_t)(k.x & 0xFFFF));
@@ -2060,6 +2064,7 @@ __device__ __forceinline__ uint32_t nat_one(const NatArgs &a, const uint32_t *T,
         one_lan(a.t, flowid_hash(T, sp, dp, sip, dip, in, proto), key, seq, fresh);
     if (idx == kNone) return in;
     serve_stamp(a.t, idx, now, seq);
+    *tix = idx;
     f.w32(h.ip + 12, a.ext_ip);
     f.w16(h.l4, (uint16_t)(a.start_port + idx));
     dst = a.wan;
@@ -2077,7 +2082,8 @@ __device__ __forceinline__ uint32_t nat_one(const NatArgs &a, const uint32_t *T,
 __device__ __forceinline__ uint32_t nat_one_reg(const NatArgs &a, const uint32_t *T, RFrame &f,
                                                 uint32_t in, uint32_t len, uint32_t tail,
                                                 int64_t now, uint64_t seq, uint32_t *fresh,
-                                                bool prof, uint64_t &mk0, uint64_t &mk1) {
+                                                uint32_t *tix, bool prof, uint64_t &mk0,
+                                                uint64_t &mk1) {
   const uint32_t et = f.w[3] & 0xFFFF, ihl = (f.w[3] >> 16) & 0x0F;
   if (!(et == 0x0008 && ihl == 5)) return kNone;
   const uint32_t tl = bswap16((uint16_t)(f.w[4] & 0xFFFF));
@@ -2093,6 +2099,7 @@ __device__ __forceinline__ uint32_t nat_one_reg(const NatArgs &a, const uint32_t
     uint4 k;
     if (!one_wan(a, dp, now, seq, &k, &ix)) return in;
     serve_stamp(a.t, ix, now, seq);  // (rejuvenated before the anti-spoof check)
+    *tix = ix;  // (the index the packet touched, for the journal)
     if ((k.z != sip) | ((k.x >> 16) != sp) | (((k.w >> 16) & 0xFF) != proto)) return in;
     f.set32at2(30, k.y);        // dst_addr = flow.src_ip
     f.set16(36, k.x & 0xFFFF);  // dst_port = flow.src_port
@@ -2105,6 +2112,7 @@ __device__ __forceinline__ uint32_t nat_one_reg(const NatArgs &a, const uint32_t
     if (prof) mk1 = wall_clock64();
     if (idx == kNone) return in;
     serve_stamp(a.t, idx, now, seq);
+    *tix = idx;
     f.set32at2(26, a.ext_ip);
     f.set16(34, (uint16_t)(a.start_port + idx));
     dst = a.wan;
@@ -2119,14 +2127,24 @@ __device__ __forceinline__ uint32_t nat_one_reg(const NatArgs &a, const uint32_t
 
 // A burst request (vp_serve_dev.h) for vignat: a WAN lane that looks again
 // reads its port's slot. A frame that needs the byte-addressed path (nat_one:
-// IP options) declines the burst.
+// IP options) declines the burst. With the journal on (J) the expiries due at
+// the first packet run first and *k <= n packets are served (burst_split).
+template <bool J>
 __device__ __forceinline__ uint32_t serve_burst(const NatArgs &a, const uint32_t *T,
                                                 ServeBox *box, uint32_t n, uint64_t seq0,
-                                                uint32_t lane) {
+                                                uint32_t lane, const JournalDev &j,
+                                                JournalSt &js, uint32_t *k) {
   const TableDev &t = a.t;
   BurstIn b = burst_load(box, n, lane);
-  const BurstHdr h = burst_hdr(b);  // nat_one_reg's tests (nat_main.c:30-38)
+  BurstHdr h = burst_hdr(b);  // nat_one_reg's tests (nat_main.c:30-38)
   if (h.decline) return kBurstDeclined;
+  int64_t now0 = 0;
+  if (J) {
+    n = burst_split(t, j, js, b, n, lane, &now0);
+    if (!n) return kBurstFull;
+    h.go = h.go && lane < n;
+  }
+  *k = n;
   RFrame &f = b.f;
   const uint32_t in = b.in;
   // the L4 checksum's bytes past 64, [64, min(14 + total_length, len)), summed
@@ -2170,7 +2188,9 @@ __device__ __forceinline__ uint32_t serve_burst(const NatArgs &a, const uint32_t
   // Stamps. idx != kNone: a LAN packet with a flow (a table-full drop stamps
   // nothing) or a WAN packet whose port holds one (stamped before the
   // anti-spoof check).
-  if (burst_last(idx, n, lane)) serve_stamp(t, idx, b.now, seq0 + lane);
+  const bool won = burst_last(idx, n, lane);
+  if (won) serve_stamp(t, idx, b.now, seq0 + lane);
+  if (J) journal_touch_burst(j, js, won, idx, seq0 + lane, now0, lane);
   // the rewrite, each lane its own frame
   uint32_t out = in, rew = 0;
   if (idx != kNone) {
@@ -2228,8 +2248,11 @@ __device__ __forceinline__ uint32_t serve_burst(const NatArgs &a, const uint32_t
 // finds the stream idle and the host launches it again (serve_wait). flags:
 // bit 0, the stage clock (VIGPATH_SERVE_PROF); bits 3-9: the waves' stagger in
 // wall-clock ticks; bits 10-23: serve_poll's.
+// J: the kernel expires from the touch journal j (vp_serve_dev.h; one wave
+// only); a context whose journal is off runs the instance without any of it.
+template <bool J>
 __global__ __launch_bounds__(256) void nat_serve(NatArgs a, ServeBox *box, uint64_t seq0,
-                                                 uint64_t idle, uint32_t flags) {
+                                                 uint64_t idle, uint32_t flags, JournalDev j) {
   __shared__ uint32_t T[kNatTabWords];
   __shared__ uint4 fr[kServeFrame / 16];
   __shared__ uint32_t done_s, claim_s;  // the last answered / claimed request
@@ -2252,6 +2275,8 @@ __global__ __launch_bounds__(256) void nat_serve(NatArgs a, ServeBox *box, uint6
     return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
   };
   uint32_t *fw = reinterpret_cast<uint32_t *>(fr);
+  // the touch journal's control words
+  JournalSt js = journal_load(J ? j : JournalDev{});
   auto serve = [&](const v4u &c) -> int {
     const uint32_t want = __builtin_amdgcn_readfirstlane(lds_ld(&done_s)) + 1;
     const uint32_t tag0 = __builtin_amdgcn_readfirstlane(c[3]);
@@ -2275,12 +2300,15 @@ __global__ __launch_bounds__(256) void nat_serve(NatArgs a, ServeBox *box, uint6
     if (burst) {
       // the wave that claimed the request serves all of it, whatever
       // VIGPATH_SERVE_WAVES is: lane i = packet i (serve_burst)
-      const uint32_t bn = min(max(in, 1u), kServeBurst);
-      const uint32_t st = serve_burst(a, T, box, bn, seq, lane);
+      uint32_t bn = min(max(in, 1u), kServeBurst);
+      js.expired = 0, js.flags = 0;
+      uint32_t st = serve_burst<J>(a, T, box, bn, seq, lane, j, js, &bn);
+      if (J && st == kBurstServed && js.flags) st |= kBurstTombs;
+      if (J) journal_store(j, js, lane);
       if (lane == 0) {
-        burst_answer(io, box, st, bn, want);
+        burst_answer(io, box, st, bn, want, js.expired);
         t0_s = wall_clock64();
-        if (st == kBurstServed) seq_s = seq + bn;
+        if ((st & 0xFFu) == kBurstServed) seq_s = seq + bn;
       }
       // (every lane's table writes before the next request's wave reads them)
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -2312,30 +2340,39 @@ __global__ __launch_bounds__(256) void nat_serve(NatArgs a, ServeBox *box, uint6
     }
     const uint64_t s1 = wall_clock64();
     const uint64_t c1 = prof ? __builtin_amdgcn_s_memtime() : 0;  // (shader clock)
-    uint32_t res = 0;
+    uint32_t res = 0, tix = kNone;
     uint64_t mk0 = 0, mk1 = 0, mk2 = 0;
-    if (lane == 0) {
+    js.expired = 0, js.flags = 0;
+    const bool full = J && !journal_room(j, js, 1);  // (nothing is done: seeded again)
+    if (J && !full) serve_expire(a.t, j, js, journal_cutoff(j, now), lane);
+    if (full) res = kOneFull;
+    if (lane == 0 && !full) {
       uint32_t fresh = 0;
       RFrame f = serve_rframe([&](int j) { return fr[j]; }, len);
-      uint32_t out = nat_one_reg(a, T, f, in, len, tail, now, seq, &fresh, prof, mk0, mk1);
+      uint32_t out =
+          nat_one_reg(a, T, f, in, len, tail, now, seq, &fresh, &tix, prof, mk0, mk1);
       if (prof) mk2 = wall_clock64();
       if (out == kNone) {
         const GFrame g{reinterpret_cast<uint8_t *>(fr), len};
-        out = nat_one(a, T, g, in, len, now, seq, &fresh);
+        out = nat_one(a, T, g, in, len, now, seq, &fresh, &tix);
       } else {
 #pragma unroll
         for (int j = 0; j < 4; j++)
           fr[j] = make_uint4(f.w[4 * j], f.w[4 * j + 1], f.w[4 * j + 2], f.w[4 * j + 3]);
       }
-      res = out | (fresh << 16);
+      res = out | (fresh << 16) | js.flags;
     }
     wave_lds_sync();
     const uint64_t s2 = wall_clock64();
     const uint64_t c2 = prof ? __builtin_amdgcn_s_memtime() : 0;
     res = __builtin_amdgcn_readfirstlane(res);
+    if (J) {
+      journal_touch(j, js, __builtin_amdgcn_readfirstlane(tix), seq, now, lane);
+      journal_store(j, js, lane);
+    }
     if (inl) {  // the answer chunks: the result and the frame in one store
       if (lane < need) {
-        const v4u v = lane == 0 ? (v4u){res, 0u, 0u, want}
+        const v4u v = lane == 0 ? (v4u){res, js.expired, 0u, want}
                                 : (v4u){fw[3 * lane - 3], fw[3 * lane - 2], fw[3 * lane - 1], want};
         __builtin_amdgcn_raw_buffer_store_b128(v, io.as, (int)(16 * lane), 0, kSys);
       }
@@ -2350,7 +2387,8 @@ __global__ __launch_bounds__(256) void nat_serve(NatArgs a, ServeBox *box, uint6
       __builtin_amdgcn_s_waitcnt(0);
       __atomic_signal_fence(__ATOMIC_SEQ_CST);
       if (lane == 0)
-        __builtin_amdgcn_raw_buffer_store_b128((v4u){res, 0u, 0u, want}, io.as, 0, 0, kSys);
+        __builtin_amdgcn_raw_buffer_store_b128((v4u){res, js.expired, 0u, want}, io.as, 0, 0,
+                                               kSys);
     }
     if (lane == 0) {
       // (the answer word: where a relaunched server starts counting; the
@@ -2359,7 +2397,7 @@ __global__ __launch_bounds__(256) void nat_serve(NatArgs a, ServeBox *box, uint6
       const uint64_t ans = (uint64_t)want | ((uint64_t)res << 32);
       __hip_atomic_store(&box->ans, ans, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       t0_s = wall_clock64();
-      seq_s = seq + 1;
+      seq_s = full ? seq : seq + 1;
       if (prof) {
         auto put = [&](int k, uint64_t v) {
           __hip_atomic_store(&box->prof[k], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -3200,8 +3238,14 @@ int nat_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
     const char *e = getenv("VIGPATH_SERVE_GAP");
     return e ? (uint32_t)std::min(127, std::max(0, atoi(e))) : 35u;
   }();
-  nat_serve<<<1, 64 * waves, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle,
-                                             (serve_prof() ? 1u : 0u) | (gap << 3) | flags);
+  // (the journal's control words live in one wave's registers: off with more)
+  JournalDev j = serve_journal_dev(c, nat_serve_nf());
+  if (waves > 1) j = JournalDev{};
+  const uint32_t fl = (serve_prof() ? 1u : 0u) | (gap << 3) | flags;
+  if (j.ctl)
+    nat_serve<true><<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, fl, j);
+  else
+    nat_serve<false><<<1, 64 * waves, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, fl, j);
   VP_HIP(hipGetLastError());
   return 0;
 }
@@ -3219,8 +3263,10 @@ constexpr uint32_t kServeBurstRoute = 256;
 // than kServeInline through `frame`; of a burst's frame all bytes go (the L4
 // checksum's) and the first 64 come back. The stage clock is vignat's.
 const ServeNf &nat_serve_nf() {
-  static const ServeNf nf = {nat_cutoff, &vp_ctx::ft, true, kServeInline, kServeInline,
-                             kServeFrame, 64, kServeBurstRoute, true};
+  static const ServeNf nf = {nat_cutoff,  &vp_ctx::ft, true,
+                             kServeInline, kServeInline, kServeFrame,
+                             64,          kServeBurstRoute, true,
+                             nullptr,     nullptr,     true};
   return nf;
 }
 

@@ -903,6 +903,14 @@ int vp_serve_stats_get(vp_ctx *c, vp_serve_stats *out) {
   return 0;
 }
 
+int vp_serve_expiry_stats_get(vp_ctx *c, vp_serve_expiry_stats *out) {
+  if (!c || !out) return VP_EINVAL;
+  // (host counters only: the resident kernel stays)
+  std::lock_guard<std::recursive_mutex> sg(c->srv_mu);
+  *out = c->srv_exp;
+  return 0;
+}
+
 const char *vp_last_error(void) { return vp::g_last_error; }
 
 int vp_kernel_timing(vp_ctx *c, int on) {

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "vp_internal.h"
+#include "vp_table.h"
 
 namespace vp {
 
@@ -177,6 +178,80 @@ uint32_t serve_burst_limit(uint32_t dflt) {  // VIGPATH_SERVE_BURST
   return v < 0 ? dflt : (uint32_t)v;
 }
 
+// ------------------------------------------------------ the touch journal --
+// Expiry inside the resident kernel (vp_serve_dev.h). The
+// expiry time E of the NF's cutoff, cutoff(t) = t - E in u64 arithmetic
+// (vignat's 32-bit wrap inside it).
+static uint64_t serve_expire_e(const vp_ctx *c, const ServeNf &nf) {
+  return (uint64_t)0 - (uint64_t)nf.cutoff(c, 0);
+}
+
+// Whether c's kernel may expire: the NF has the walk (vignat, vigfw),
+// VIGPATH_SERVE_EXPIRE is not 0, vignat polls with one wave (the journal's
+// control words live in that wave's registers), and E is not negative (a
+// packet would then expire the flow it has just touched).
+static bool serve_journal_ok(const vp_ctx *c, const ServeNf &nf) {
+  static const bool off = [] {
+    const char *e = getenv("VIGPATH_SERVE_EXPIRE");
+    return e && !atoi(e);
+  }();
+  static const bool waves = [] {
+    const char *e = getenv("VIGPATH_SERVE_WAVES");
+    const int v = e ? atoi(e) : 1;
+    return v == 2 || v == 4;
+  }();
+  return nf.journal && !off && !(waves && c->kind == KIND_NAT) &&
+         (int64_t)serve_expire_e(c, nf) >= 0;
+}
+
+JournalDev serve_journal_dev(const vp_ctx *c, const ServeNf &nf) {
+  const FlowTable &t = c->*nf.table;
+  if (!t.jr_on) return JournalDev{};
+  return JournalDev{t.jr, t.jrec, t.jr_n, tbl_purge_bound(t), serve_expire_e(c, nf)};
+}
+
+// A request found an expiry due while the journal was off: it takes the
+// pipeline, and the next launch seeds the journal (serve_ready).
+static void serve_handed(vp_ctx *c, const ServeNf &nf) {
+  if (!nf.journal) return;
+  c->srv_exp.handed += 1;
+  if (serve_journal_ok(c, nf)) c->jr_want = true;
+}
+
+// What a journal request's answer says beside its results: `expired` entries
+// left in its walk; kOneTombs / kBurstTombs (tombs): the table passed the
+// purge bound, so the kernel stops for the pipeline's own check and is
+// launched again by the next request. The journal stays: a rebuild moves
+// entries, not stamps.
+static int serve_expired(vp_ctx *c, FlowTable &t, uint32_t expired, bool tombs) {
+  if (expired) {
+    c->srv_exp.expired += expired;
+    c->srv_exp.walks += 1;
+  }
+  if (!tombs) return 0;
+  VP_TRY(serve_stop(c));
+  VP_HIP(hipSetDevice(c->gpu));
+  return tbl_check_tombs(c, t);
+}
+
+// The ring is full: stop, and the launch that follows seeds it again from the
+// table, on all CUs -- the journal's compaction.
+static int serve_reseed(vp_ctx *c, FlowTable &t) {
+  VP_TRY(serve_stop(c));
+  t.jr_on = false;
+  c->jr_want = true;
+  return serve_ready(c);
+}
+
+// An expiry is due and the journal is off. If the context's last fallback was
+// a due expiry (jr_want: the bounce is behind it), the journal is seeded now
+// and the request served; else this request is the bounce.
+static int serve_seed_now(vp_ctx *c) {
+  if (!c->jr_want) return 0;
+  VP_TRY(serve_stop(c));
+  return serve_ready(c);
+}
+
 // The mailbox exists and the server runs (the caller holds c->srv_mu).
 int serve_ready(vp_ctx *c) {
   if (!c->sbox || !c->srv_on) VP_HIP(hipSetDevice(c->gpu));  // (HIP calls below)
@@ -192,6 +267,17 @@ int serve_ready(vp_ctx *c) {
     c->srv_idle = (uint64_t)std::max(khz, 1) * c->srv_idle_ms;
   }
   if (!c->srv_on) {
+    // the context's last fallback was a due expiry: from this launch on the
+    // kernel expires itself, from a journal of the table as it is now
+    if (c->jr_want) {
+      const ServeNf *nf = serve_nf(c->kind);
+      FlowTable &t = c->*nf->table;
+      c->jr_want = false;
+      if (!t.jr_on) {
+        VP_TRY(tbl_journal_seed(c, t));
+        c->srv_exp.seeds += 1;
+      }
+    }
     // the batch path may leave a timestamp fold running: the server is
     // queued behind it on the same stream
     VP_TRY(serve_launch(c));
@@ -255,36 +341,55 @@ int serve_process_one(vp_ctx *c, const ServeNf &nf, uint16_t in_dev, uint8_t *fr
   std::lock_guard<std::recursive_mutex> sg(c->srv_mu);
   FlowTable &t = c->*nf.table;
   FlowTable *t2 = nf.table2 ? &(c->*nf.table2) : nullptr;
-  // no expiry due at this packet on either table (run_batch's test for a
-  // segment of one, each table against its own floor)
+  // times that do not go back, a frame the mailbox holds
   const bool ok = !serve_off() && !c->comm && len <= kServeFrame && now >= 0 &&
-                  now >= c->last_now &&
-                  nf.cutoff(c, now) <= (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)now) &&
-                  (!t2 || nf.cutoff2(c, now) <=
-                              (int64_t)std::min<uint64_t>(t2->ts_floor, (uint64_t)now));
+                  now >= c->last_now;
   if (!ok) {
     VP_TRY(serve_stop(c));
     return 1;
   }
-  VP_TRY(serve_ready(c));
-  ServeBox *bx = c->sbox;
+  // no expiry due at this packet on either table (run_batch's test for a
+  // segment of one, each table against its own floor) -- or the kernel
+  // expires itself (the journal is on)
+  const bool due = nf.cutoff(c, now) > (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)now) ||
+                   (t2 && nf.cutoff2(c, now) >
+                              (int64_t)std::min<uint64_t>(t2->ts_floor, (uint64_t)now));
+  if (due && !t.jr_on) VP_TRY(serve_seed_now(c));  // (after a bounce: seeded, then served)
+  if (due && !t.jr_on) {
+    serve_handed(c, nf);
+    VP_TRY(serve_stop(c));
+    return 1;
+  }
   const bool prof = nf.prof && serve_prof();
   const auto h0 = prof ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
-  // the request: a frame longer than the chunks hold goes whole through
-  // `frame` before them and comes back there (nf.one_whole), or only its
-  // first nf.one_in bytes go
-  const uint32_t req = ++c->srv_req;
-  const bool via_frame = nf.one_whole && len > kServeInline;
-  const uint32_t got = via_frame ? 0u : std::min<uint32_t>(len, nf.one_in);
-  if (via_frame) memcpy(bx->frame, frame, len);
-  uint32_t m[3 * kServeChunks];
-  const uint32_t need = serve_pack(m, len | ((uint32_t)in_dev << 16), now, frame, got);
-  serve_post(bx, m, need, req);
-  // the answer: chunk 0, and the chunks that bring the frame bytes back -- as
-  // many as the request took, chunk 1 alone (bytes 0-11), or none
-  const uint32_t back = std::min(got, nf.one_back);
-  VP_TRY(serve_wait(c, req, 1 + (back + 11) / 12));
-  const uint32_t res = bx->amsg[0][0];  // out | fresh << 16 | kOneFresh2 | kOneDeclined
+  ServeBox *bx = nullptr;
+  uint32_t res = 0, got = 0, back = 0;
+  bool via_frame = false;
+  for (int attempt = 0;; attempt++) {
+    VP_TRY(serve_ready(c));
+    bx = c->sbox;
+    // the request: a frame longer than the chunks hold goes whole through
+    // `frame` before them and comes back there (nf.one_whole), or only its
+    // first nf.one_in bytes go
+    const uint32_t req = ++c->srv_req;
+    via_frame = nf.one_whole && len > kServeInline;
+    got = via_frame ? 0u : std::min<uint32_t>(len, nf.one_in);
+    if (via_frame) memcpy(bx->frame, frame, len);
+    uint32_t m[3 * kServeChunks];
+    const uint32_t need = serve_pack(m, len | ((uint32_t)in_dev << 16), now, frame, got);
+    serve_post(bx, m, need, req);
+    // the answer: chunk 0, and the chunks that bring the frame bytes back -- as
+    // many as the request took, chunk 1 alone (bytes 0-11), or none
+    back = std::min(got, nf.one_back);
+    VP_TRY(serve_wait(c, req, 1 + (back + 11) / 12));
+    // out | fresh << 16 | kOneFresh2 | kOneDeclined | kOneFull | kOneTombs
+    res = bx->amsg[0][0];
+    if (!(res & kOneFull)) break;
+    // the journal's ring is full and nothing was done: seeded again, then
+    // the same packet once more (it fits: at most cap records of >= 2 cap)
+    if (attempt) return state_fail("journal full right after a seed");
+    VP_TRY(serve_reseed(c, t));
+  }
   if (res & kOneDeclined) {  // nothing of it was done: the batch path, as an ineligible one
     c->srv_stats.declined += 1;
     VP_TRY(serve_stop(c));
@@ -301,6 +406,7 @@ int serve_process_one(vp_ctx *c, const ServeNf &nf, uint16_t in_dev, uint8_t *fr
   c->last_now = now;
   c->srv_stats.packets_one += 1;
   if (prof) serve_prof_add(c, h0);
+  if (t.jr_on) VP_TRY(serve_expired(c, t, bx->amsg[0][1], (res & kOneTombs) != 0));
   return 0;
 }
 
@@ -326,13 +432,22 @@ int serve_process_burst(vp_ctx *c, const ServeNf &nf, const vp_mbuf_batch *b, ui
     if (b->len[first + i] > kServeFrame || ti < prev) return 1;
     prev = ti;
   }
-  if (nf.cutoff(c, n1) > (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)n0)) return 1;
   FlowTable *t2 = nf.table2 ? &(c->*nf.table2) : nullptr;  // (the same, on its own floor)
-  if (t2 && nf.cutoff2(c, n1) > (int64_t)std::min<uint64_t>(t2->ts_floor, (uint64_t)n0)) return 1;
-  VP_TRY(serve_ready(c));
-  ServeBox *bx = c->sbox;
-  for (uint32_t a0 = 0; a0 < count; a0 += kServeBurst) {
-    const uint32_t m = std::min(kServeBurst, count - a0);
+  // (with the journal on the kernel expires itself, and serves a request up
+  // to the packet at which the next expiry falls due)
+  const bool due =
+      nf.cutoff(c, n1) > (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)n0) ||
+      (t2 && nf.cutoff2(c, n1) > (int64_t)std::min<uint64_t>(t2->ts_floor, (uint64_t)n0));
+  if (due && !t.jr_on) VP_TRY(serve_seed_now(c));  // (after a bounce: seeded, then served)
+  if (due && !t.jr_on) {
+    serve_handed(c, nf);
+    return 1;
+  }
+  int reseeds = 0;
+  for (uint32_t a0 = 0; a0 < count;) {
+    VP_TRY(serve_ready(c));  // (stopped by a purge or a seed in between: launched again)
+    ServeBox *bx = c->sbox;
+    uint32_t m = std::min(kServeBurst, count - a0);
     // the body first, then the tagged chunk that announces it (ServeBox)
     for (uint32_t i = 0; i < m; i++) {
       const uint32_t p = first + a0 + i;
@@ -345,10 +460,21 @@ int serve_process_burst(vp_ctx *c, const ServeNf &nf, const vp_mbuf_batch *b, ui
     const uint32_t op[3] = {kServeBurstOp | (m << 16), 0, 0};
     serve_post(bx, op, 1, req);
     VP_TRY(serve_wait(c, req, 1));
-    if (bx->amsg[0][0] != kBurstServed) {  // a byte-path frame: nothing of it was done
+    const uint32_t st = bx->amsg[0][0];
+    if (st == kBurstFull && t.jr_on) {  // nothing of it was done: seeded again, once more
+      if (reseeds++) return state_fail("journal full right after a seed");
+      VP_TRY(serve_reseed(c, t));
+      continue;
+    }
+    if ((st & 0xFFu) != kBurstServed) {  // a byte-path frame: nothing of it was done
       c->srv_stats.declined += 1;
       return 1;
     }
+    reseeds = 0;
+    // the packets served: all of them, or with the journal on those before
+    // the one at which an expiry falls due (the rest is the next request)
+    const uint32_t asked = m;
+    if (t.jr_on) m = std::min(std::max(bx->amsg[0][1], 1u), m);
     bool fresh = false, fresh2 = false;
     for (uint32_t i = 0; i < m; i++) {
       const uint32_t p = first + a0 + i, r = bx->bout[i];
@@ -366,6 +492,11 @@ int serve_process_burst(vp_ctx *c, const ServeNf &nf, const vp_mbuf_batch *b, ui
     c->srv_stats.bursts += 1;
     c->srv_stats.burst_packets += m;
     *served += m;
+    if (t.jr_on) {
+      if (m < asked) c->srv_exp.splits += 1;
+      VP_TRY(serve_expired(c, t, bx->amsg[0][2], (st & kBurstTombs) != 0));
+    }
+    a0 += m;
   }
   return 0;
 }

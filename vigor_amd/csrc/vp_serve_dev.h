@@ -74,6 +74,149 @@ __device__ __forceinline__ void serve_stamp(const TableDev &t, uint32_t idx, int
   t.tseq[idx] = seq;
 }
 
+// --------------------------------------------------- the touch journal --
+// Expiry inside the resident kernel (vignat, vigfw; JournalDev, vp_table.h).
+// The wave keeps the journal's control words in registers (wave-uniform) and
+// stores them back after every request (journal_store), so a kernel launched
+// again after an idle exit or a stop goes on from them (journal_load).
+struct JournalSt {
+  uint32_t tail, cnt;  // ring position of the oldest record; records from there
+  int64_t floor;       // lower bound of the live stamps (kJournalNone: none live)
+  uint32_t expired;    // entries this request's walk expired
+  uint32_t flags;      // kOneTombs: the walk left the table past the purge bound
+};
+__device__ __forceinline__ JournalSt journal_load(const JournalDev &j) {
+  JournalSt s{0u, 0u, kJournalNone, 0u, 0u};
+  if (j.ctl) {
+    s.tail = __builtin_amdgcn_readfirstlane(j.ctl->tail);
+    s.cnt = __builtin_amdgcn_readfirstlane(j.ctl->cnt);
+    const uint64_t f = (uint64_t)j.ctl->floor;
+    s.floor = (int64_t)((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)f) |
+                        ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(f >> 32)) << 32));
+  }
+  return s;
+}
+__device__ __forceinline__ void journal_store(const JournalDev &j, const JournalSt &s,
+                                              uint32_t lane) {
+  if (lane == 0) {
+    j.ctl->tail = s.tail;
+    j.ctl->cnt = s.cnt;
+    j.ctl->floor = s.floor;
+  }
+}
+// The cutoff of a packet at `now`: now - E in unsigned 64-bit arithmetic (E
+// from nat_cutoff / fw_cutoff, vignat's 32-bit wrap inside it), compared as
+// the pipeline compares it, signed (exp_collect).
+__device__ __forceinline__ int64_t journal_cutoff(const JournalDev &j, int64_t now) {
+  return (int64_t)((uint64_t)now - j.expire);
+}
+__device__ __forceinline__ uint32_t journal_pos(const JournalDev &j, uint32_t p) {
+  return p >= j.n ? p - j.n : p;  // (p < 2 n: tail < n and at most n records)
+}
+// Room for `need` more records (the caller's touches; need <= n - live holds
+// right after a seed, so a request posted again after one always fits).
+__device__ __forceinline__ bool journal_room(const JournalDev &j, const JournalSt &s,
+                                             uint32_t need) {
+  return j.n - s.cnt >= need;
+}
+
+// expire_items_single_map (expirator.c:110-218) at `cutoff`, by the whole
+// wave, before a request's packets: every current record from the tail whose
+// index is stamped below the cutoff frees its index, oldest first, exactly as
+// exp_apply does -- stack[top + rank], the youngest expired index on top, the
+// bucket entry a tombstone, slot_of = kNone. One compare when nothing is due.
+// The loop consumes at least one record per iteration or ends at a stopper
+// (a current record stamped >= cutoff, the new floor): at most `cnt` (head -
+// tail) iterations, no other exit, nothing another agent writes is read.
+__device__ __forceinline__ void serve_expire(const TableDev &t, const JournalDev &j,
+                                             JournalSt &s, int64_t cutoff, uint32_t lane) {
+  if (cutoff <= s.floor) return;
+  Ctl *c = t.ctl;
+  const uint32_t top = __builtin_amdgcn_readfirstlane(c->stack_top);
+  uint32_t freed = 0;
+  bool stopped = false;
+  for (uint32_t left = s.cnt; left > 0 && !stopped;) {
+    const uint32_t m = min(left, 64u);
+    uint32_t idx = 0;
+    bool cur = false;
+    int64_t ts = 0;
+    if (lane < m) {
+      const uint4 r = j.rec[journal_pos(j, s.tail + lane)];
+      idx = r.z;
+      cur = idx < t.cap && t.slot_of[idx] != kNone &&
+            t.tseq[idx] == ((uint64_t)r.x | ((uint64_t)r.y << 32));
+      if (cur) ts = (int64_t)t.ts[idx];
+    }
+    const uint64_t sb = __ballot(cur && ts >= cutoff);
+    const uint32_t first = sb ? (uint32_t)__ffsll((unsigned long long)sb) - 1 : m;
+    const bool dead = cur && lane < first;  // (below the stopper: ts < cutoff)
+    const uint64_t eb = __ballot(dead);
+    if (dead) {
+      const uint32_t rank = (uint32_t)__popcll(eb & ((1ull << lane) - 1));
+      const uint32_t e = t.slot_of[idx];
+      // (the stack holds an index at most once: top + freed + rank < cap)
+      if (top + freed + rank < t.cap) t.stack[top + freed + rank] = idx;
+      if ((e >> 2) <= t.bmask) t.bk[e >> 2].idx[e & 3] = kTomb;
+      t.slot_of[idx] = kNone;
+    }
+    freed += (uint32_t)__popcll(eb);
+    s.tail = journal_pos(j, s.tail + first);
+    s.cnt -= first;
+    left -= first;
+    if (sb) {
+      const uint64_t u = (uint64_t)ts;
+      s.floor = (int64_t)((uint64_t)(uint32_t)__shfl((int)(uint32_t)u, (int)first) |
+                          ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(u >> 32), (int)first) << 32));
+      stopped = true;
+    }
+  }
+  if (!stopped) s.floor = kJournalNone;  // (the tail reached the head)
+  if (freed) {
+    uint32_t over = 0;
+    if (lane == 0) {
+      c->stack_top = top + freed;
+      const uint32_t nt = c->n_tomb + freed, sl = c->sh_live - freed;
+      c->n_tomb = nt;
+      c->n_live -= freed;
+      c->sh_live = sl;
+      over = nt + sl > j.purge;
+    }
+    if (__builtin_amdgcn_readfirstlane(over)) s.flags |= kOneTombs;
+    s.expired += freed;
+    // (the walk's table writes before the request's lookups: one wave)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
+}
+
+// One record per touch, in packet order: lane 0's after a one-packet request
+// (idx == kNone: the packet touched nothing) ...
+__device__ __forceinline__ void journal_touch(const JournalDev &j, JournalSt &s, uint32_t idx,
+                                              uint64_t seq, int64_t now, uint32_t lane) {
+  if (idx == kNone) return;
+  if (lane == 0)
+    j.rec[journal_pos(j, s.tail + s.cnt)] = make_uint4((uint32_t)seq, (uint32_t)(seq >> 32), idx, 0u);
+  if (s.cnt == 0) s.floor = now;  // (the only live stamp there is)
+  s.cnt += 1;
+}
+// ... and a burst's, the lanes whose stamp won (burst_last) in lane order:
+// an index touched by several packets of the burst is stamped by the last
+// one alone, and the earlier touches' records would be stale the moment they
+// were written. now0: the burst's first time, a lower bound of its stamps.
+__device__ __forceinline__ void journal_touch_burst(const JournalDev &j, JournalSt &s, bool won,
+                                                    uint32_t idx, uint64_t seq, int64_t now0,
+                                                    uint32_t lane) {
+  const uint64_t wb = __ballot(won);
+  if (!wb) return;
+  if (won) {
+    const uint32_t rank = (uint32_t)__popcll(wb & ((1ull << lane) - 1));
+    j.rec[journal_pos(j, journal_pos(j, s.tail + s.cnt) + rank)] =
+        make_uint4((uint32_t)seq, (uint32_t)(seq >> 32), idx, 0u);
+  }
+  if (s.cnt == 0) s.floor = now0;
+  s.cnt += (uint32_t)__popcll(wb);
+}
+
 // A frame's first 64 bytes from its four 16-byte chunks chunk(0..3); bytes
 // past len read as 0.
 template <class Chunk>
@@ -125,8 +268,9 @@ __device__ __forceinline__ void serve_chunks_in(uint32_t *fword, const v4u &c, u
 // A burst request (ServeBox: nf.c's VIGOR_BATCH_SIZE loop, nf.c:178-215)
 // brings n frames as nf_process would take them one after another, lane i =
 // packet i at sequence seq0 + i; the whole wave serves it. The host sends a
-// burst only while no expiry is due anywhere in it (serve_process_burst), so
-// no flow leaves during the burst: a lookup that hits is final the moment it
+// burst only while no expiry is due anywhere in it (serve_process_burst), or
+// with the journal on the wave serves it up to the packet at which one falls
+// due (burst_split), so no flow leaves during the burst: a lookup that hits is final the moment it
 // is made, and only the misses depend on the packets before them
 // (burst_settle). A burst is served whole (kBurstServed) or declined before
 // any table write (kBurstDeclined: a frame with IPv4 options, the
@@ -188,6 +332,29 @@ __device__ __forceinline__ BurstHdr burst_hdr(const BurstIn &b) {
   h.sp = f.w[8] >> 16, h.dp = f.w[9] & 0xFFFF;
   h.sip = f.u32at2(26), h.dip = f.u32at2(30);
   return h;
+}
+
+// A burst with the journal on, behind the decline test and before any other
+// table write: the expiries due at its first packet (serve_expire), then the
+// packets it serves -- with floor F after the walk, the lanes below the first
+// lane k whose cutoff passes min(F, now_0): flows born or touched inside the
+// burst are stamped at or after now_0, so no expiry is due at any of them
+// (run_batch's test). k >= 1: lane 0's cutoff is at most F after its own walk
+// and at most now_0. Returns k, or 0 when the journal has no room for the
+// burst's touches (at most one record per index, journal_touch_burst):
+// nothing was done.
+__device__ __forceinline__ uint32_t burst_split(const TableDev &t, const JournalDev &j,
+                                                JournalSt &s, const BurstIn &b, uint32_t n,
+                                                uint32_t lane, int64_t *now0) {
+  if (!journal_room(j, s, min(n, t.cap))) return 0;
+  const uint64_t u = (uint64_t)b.now;
+  const int64_t n0 = (int64_t)((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)u) |
+                               ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(u >> 32)) << 32));
+  *now0 = n0;
+  serve_expire(t, j, s, journal_cutoff(j, n0), lane);
+  const int64_t lim = s.floor < n0 ? s.floor : n0;
+  const uint64_t due = __ballot(b.act && lane > 0 && journal_cutoff(j, b.now) > lim);
+  return due ? (uint32_t)__ffsll((unsigned long long)due) - 1 : n;
 }
 
 // After round 0 (every lane has looked its flow up in the table as the burst
@@ -253,8 +420,8 @@ __device__ __forceinline__ void burst_out(const BurstIn &b, uint32_t res, uint32
 // A burst's answer (lane 0): the status chunk and the answer word, where a
 // relaunched server starts counting.
 __device__ __forceinline__ void burst_answer(const ServeIo &io, ServeBox *box, uint32_t st,
-                                             uint32_t bn, uint32_t want) {
-  __builtin_amdgcn_raw_buffer_store_b128((v4u){st, bn, 0u, want}, io.as, 0, 0, kSys);
+                                             uint32_t bn, uint32_t want, uint32_t expired = 0) {
+  __builtin_amdgcn_raw_buffer_store_b128((v4u){st, bn, expired, want}, io.as, 0, 0, kSys);
   __hip_atomic_store(&box->ans, (uint64_t)want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 

@@ -341,6 +341,33 @@ int tbl_expire(vp_ctx *c, FlowTable &t, int64_t cutoff, uint32_t *n_out);
 
 // Purge tombstones (rebuild) once live + erased entries pass 85 %.
 int tbl_check_tombs(vp_ctx *c, FlowTable &t);
+// That bound, in entries (tbl_expire's and tbl_check_tombs's own).
+uint32_t tbl_purge_bound(const FlowTable &t);
+
+// The touch journal of a table served by a resident kernel:
+// a ring of n records {seq, idx} in device memory, one per touch the kernel
+// makes (an allocation or a rejuvenation), appended in packet order. A record
+// is current when it is its index's latest touch and the index is still
+// allocated: slot_of[idx] != kNone and tseq[idx] == seq, compared at the full
+// 64 bits. That cannot alias: a sequence number belongs to one packet, a
+// packet touches at most one index of the table, and tseq[idx] is the
+// sequence of idx's last touch, so no second record ever carries the pair
+// (an index freed and allocated again is stamped with the later packet's
+// number). Times never decrease along the sequence (tbl_expire), so the
+// current records read from the tail are the dchain's LRU order, oldest
+// first. The kernel's launch argument; ctl == null: no journal.
+struct JournalDev {
+  JournalCtl *ctl;
+  uint4 *rec;       // {seq low, seq high, idx, 0}
+  uint32_t n;       // records in the ring
+  uint32_t purge;   // tbl_purge_bound: n_tomb + sh_live above it is reported
+  uint64_t expire;  // E: the cutoff of a packet at `now` is now - E (u64)
+};
+// (Re)build t's journal from the table: every live index in (ts, tseq)
+// order -- exp_collect with a cutoff past every stamp, then tbl_expire's
+// sort. The first call allocates the ring (VIGPATH_SERVE_JOURNAL records per
+// index, default 8, at least 2). The resident kernel must not be running.
+int tbl_journal_seed(vp_ctx *c, FlowTable &t);
 
 // Owner mode (rank r of n): a fresh table keeps only the keys it owns in its
 // buckets (sized for 1/n of the keys) and every key by index in kv.

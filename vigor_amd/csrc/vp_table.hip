@@ -226,6 +226,8 @@ void tbl_free(FlowTable &t) {
   hipFree(t.ttotal);
   hipFree(t.lin);
   hipFree(t.kv);
+  hipFree(t.jr);
+  hipFree(t.jrec);
   if (t.h_pin) hipHostFree(t.h_pin);
   if (t.h_pub) hipHostFree(t.h_pub);
   t = FlowTable{};
@@ -1626,6 +1628,66 @@ int tbl_check_tombs(vp_ctx *c, FlowTable &t) {
   return 0;
 }
 
+uint32_t tbl_purge_bound(const FlowTable &t) {
+  const uint64_t base = std::min<uint64_t>(tbl_entries(t), t.nb_base * kBucketEntries);
+  return (uint32_t)std::min<uint64_t>(base * 85 / 100, UINT32_MAX);
+}
+
+// ------------------------------------------------------- touch journal --
+
+// The sorted live set (tseq ascending: LRU order, tbl_expire) as the ring's
+// first k records; the floor is the oldest one's stamp.
+__global__ void jr_fill(TableDev t, const uint64_t *seq, const uint32_t *idx, uint32_t k,
+                        uint4 *rec, JournalCtl *jc) {
+  for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < k; j += gridDim.x * blockDim.x)
+    rec[j] = make_uint4((uint32_t)seq[j], (uint32_t)(seq[j] >> 32), idx[j], 0u);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    jc->tail = 0;
+    jc->cnt = k;
+    jc->floor = k ? (int64_t)t.ts[idx[0]] : kJournalNone;
+  }
+}
+
+int tbl_journal_seed(vp_ctx *c, FlowTable &t) {
+  if (!t.jr) {
+    static const uint32_t mult = [] {
+      const char *e = getenv("VIGPATH_SERVE_JOURNAL");
+      return (uint32_t)std::min(1024, std::max(2, e ? atoi(e) : 8));
+    }();
+    const uint64_t n = std::min<uint64_t>((uint64_t)mult * std::max(t.cap, 1u), 1u << 30);
+    if (n < 2ull * t.cap) return state_fail("journal: table of %u indices is too large", t.cap);
+    VP_TRY(dalloc(&t.jrec, n));
+    VP_TRY(dalloc(&t.jr, 1));
+    t.jr_n = (uint32_t)n;
+  }
+  // every live index: no stamp reaches INT64_MAX (times are >= 0 as int64)
+  VP_HIP(hipMemsetAsync(&t.ctl->exp_count, 0, 4, c->stream));
+  VP_HIP(hipMemsetAsync(&t.ctl->min_ts, 0xFF, 8, c->stream));
+  exp_collect<<<grid_for(t.cap, 256, 512), 256, 0, c->stream>>>(tbl_dev(t), INT64_MAX, t.ekey,
+                                                                t.eidx);
+  VP_HIP(hipGetLastError());
+  VP_TRY(read_ctl(c, t));
+  const uint32_t k = t.h_ctl.exp_count;
+  if (k > t.cap) return state_fail("journal: %u live indices in a table of %u", k, t.cap);
+  const uint64_t *seq = t.ekey;
+  const uint32_t *idx = t.eidx;
+  if (k > 1) {
+    size_t need = 0;
+    hipcub::DeviceRadixSort::SortPairs(nullptr, need, t.ekey, t.ekey2, t.eidx, t.eidx2, (int)k, 0,
+                                       64, c->stream);
+    VP_TRY(cub_reserve(c, need));
+    VP_HIP(hipcub::DeviceRadixSort::SortPairs(c->ws.cub_tmp, c->ws.cub_bytes, t.ekey, t.ekey2,
+                                              t.eidx, t.eidx2, (int)k, 0, 64, c->stream));
+    seq = t.ekey2;
+    idx = t.eidx2;
+  }
+  jr_fill<<<grid_for(std::max(k, 1u)), 256, 0, c->stream>>>(tbl_dev(t), seq, idx, k, t.jrec, t.jr);
+  VP_HIP(hipGetLastError());
+  VP_HIP(stream_wait(c->stream));
+  t.jr_on = true;
+  return 0;
+}
+
 // ---------------------------------------------------------- batch driver --
 
 int ws_reserve(vp_ctx *c, uint32_t n);
@@ -1649,6 +1711,9 @@ int run_batch(vp_ctx *c, const vp_dev_batch *b, ExpiringTable *tabs, int ntabs,
   if (b->slot < 64 || (b->slot & 15) || !b->frames || ((uintptr_t)b->frames & 15) ||
       !b->len || (!b->in_dev && ((c->kind != KIND_NAT && c->kind != KIND_LB) || b->slot != 64)) || !b->out_dev)
     return VP_EINVAL;  // (frames are read as aligned 16-byte chunks; in_dev: see vp_process_device)
+  // the pipeline touches and expires without journalling: a resident kernel's
+  // touch journal no longer describes the tables (seeded again on demand)
+  for (int i = 0; i < ntabs; i++) tabs[i].t->jr_on = false;
   VP_TRY(ws_reserve(c, n));
 
   std::vector<int64_t> h_copy;

@@ -13,7 +13,8 @@ import ctypes as C
 import numpy as np
 
 from . import (BridgeConfigC, DevBatchC, FwConfigC, LbConfigC, MbufBatchC,
-               NatConfigC, PolConfigC, ServeStatsC, TableStatsC, _check, lib)
+               NatConfigC, PolConfigC, ServeExpiryStatsC, ServeStatsC, TableStatsC, _check,
+               lib)
 
 
 def _dptr(t):
@@ -296,6 +297,18 @@ class NfBase:
         st = ServeStatsC()
         self._ck(self.L.vp_serve_stats_get(self.h, C.byref(st)), "vp_serve_stats_get")
         return {k: int(getattr(st, k)) for k, _ in ServeStatsC._fields_}
+
+    def serve_expiry_stats(self) -> dict:
+        """vp_serve_expiry_stats_get: expiry inside the resident kernel
+        (vignat, vigfw; all zero for the other NFs) -- seeds (journal builds),
+        expired (entries the kernel expired), walks (requests that expired at
+        least one), handed (requests that took the pipeline because an expiry
+        was due), splits (bursts served in part, the rest posted again). A
+        host-side counter read: the kernel stays."""
+        st = ServeExpiryStatsC()
+        self._ck(self.L.vp_serve_expiry_stats_get(self.h, C.byref(st)),
+                 "vp_serve_expiry_stats_get")
+        return {k: int(getattr(st, k)) for k, _ in ServeExpiryStatsC._fields_}
 
 
 class Nat(NfBase):
