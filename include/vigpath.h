@@ -201,11 +201,12 @@ int vp_unregister_host(vp_ctx *ctx, void *base);
  * burst requests of up to 64 frames, one lane of a wave per packet, while no
  * expiry is due anywhere in the call (viglb: on its flows or its backends), every frame is at most 2048 bytes
  * and the times do not go back: no launch, no copy call, and the kernel stays
- * for the next call (nf.c's VIGOR_BATCH_SIZE loop, nf.c:178-215). vignat and
- * vigfw hand over only the first call at which an expiry is due: from the
- * next one on their kernel expires the entries itself before each request
- * (vp_serve_expiry_stats_get), and a burst inside which an expiry falls due
- * is served up to that packet and the rest posted as the next request.
+ * for the next call (nf.c's VIGOR_BATCH_SIZE loop, nf.c:178-215). vignat,
+ * vigfw, vigbridge and vigpol hand over only the first call at which an expiry
+ * is due: from the next one on their kernel expires the entries itself before
+ * each request (vp_serve_expiry_stats_get; vigpol, as the reference, only at
+ * packets whose IPv4 header parses), and a burst inside which an expiry falls
+ * due is served up to that packet and the rest posted as the next request.
  * VIGPATH_SERVE_EXPIRE=0 turns that off (every due expiry takes the path
  * above); VIGPATH_SERVE_JOURNAL sets the journal's size in records per table
  * index (default 8, at least 2). A burst
@@ -243,8 +244,8 @@ int vp_process_batch(vp_ctx *ctx, uint32_t n, const uint16_t *in_dev,
  * kernel that polls a host-coherent mailbox (no launch per packet) while no
  * expiry is due at `now`; otherwise, and for the one packet viglb's kernel
  * hands back (the erasure of a flow with no backend alive), it is
- * vp_process_batch with n = 1. vignat and vigfw take that path only for the
- * first packet at which an expiry is due: afterwards the kernel expires the
+ * vp_process_batch with n = 1. vignat, vigfw, vigbridge and vigpol take that
+ * path only for the first packet at which an expiry is due: afterwards the kernel expires the
  * entries itself, before the packet, and stays (vp_serve_expiry_stats_get;
  * VIGPATH_SERVE_EXPIRE=0: off).
  * The kernel leaves after VIGPATH_SERVE_IDLE_MS (default 20) without a
@@ -390,8 +391,9 @@ typedef struct vp_serve_stats {
 } vp_serve_stats;
 int vp_serve_stats_get(vp_ctx *ctx, vp_serve_stats *out);
 
-/* Expiry inside the resident kernel (vignat and vigfw; all zero for the other
- * NFs), since the context was created. The first request at which an expiry
+/* Expiry inside the resident kernel (vignat, vigfw, vigbridge and vigpol;
+ * all zero for viglb, which hands every due expiry over), since the context
+ * was created. The first request at which an expiry
  * is due takes the batch pipeline (`handed`); the next launch builds a touch
  * journal from the table (`seeds`) and from then on the kernel expires entries
  * itself, in the reference's LRU order, before every request. A pipeline call

@@ -13,13 +13,17 @@ and through vp_process_batch in bursts (nf.c:178-215).
   tools/bench_dropin.py --nf lb                      # viglb: 256 backends, 1,024 flows
   tools/bench_dropin.py --nf nat --churn --batches 0,32   # flows expiring all along
 
---churn (vignat, vigfw): every 16th timed packet opens a never-seen flow and
-the others hit the `--flows` most recent flows round robin, so the oldest flow
-goes idle each time; the clock advances 1 us a packet and `--expire` is four
-round-robin turns (4 x flows us), so in steady state about one flow expires
-every 16 packets while no flow that is still hit does. The table holds 2 x
-flows. VIGPATH_SERVE_EXPIRE=0 in the environment gives the path that hands
-every due expiry to the batch pipeline.
+--churn (vignat, vigfw, vigbridge, vigpol): every 16th timed packet opens a
+never-seen flow and the others hit the `--flows` most recent flows round
+robin, so the oldest flow goes idle each time; the clock advances 1 us a
+packet and `--expire` is four round-robin turns (4 x flows us), so in steady
+state about one flow expires every 16 packets while no flow that is still hit
+does. The table holds 2 x flows. A vigbridge flow is a src MAC (every frame is
+addressed to a MAC that is never learnt and floods); a vigpol flow is a
+policed address, and the lifetime burst * 1e9 / rate is set by --rate
+1000000000 --burst 4000 x flows (4,096,000 for 1,024 flows: 4.096 ms, and no
+bucket of 64-byte packets runs dry). VIGPATH_SERVE_EXPIRE=0 in the environment
+gives the path that hands every due expiry to the batch pipeline.
 
 --sweep N,...: each burst size twice in this run, VIGPATH_SERVE_BURST forcing
 the resident kernel (a limit above every N) and the batch pipeline (0): the
@@ -67,18 +71,38 @@ def lan_port(n, flows):
     return np.ones(n, np.uint16)
 
 
-def churn_trace(n, flows):
+def churn_trace(n, flows, nf="nat"):
     """--churn: `flows` flows opened by the warm-up, then packet p of the
     timed part opens flow flows + p / 16 when p is a multiple of 16 and else
-    hits one of the `flows` newest flows, round robin; 1 us a packet."""
+    hits one of the `flows` newest flows, round robin; 1 us a packet. Flow k
+    is a LAN 5-tuple (vignat, vigfw), the src MAC 02:00:00:kk:kk:kk of a frame
+    to ff:00:00:00:00:01 on port 0 (vigbridge), or the policed address
+    10.0.0.0 + k of a WAN packet (vigpol)."""
     p = np.arange(n - flows, dtype=np.int64)
     newest = flows - 1 + (p // 16 + 1)  # (the newest flow once packet p has been seen)
     hit = newest - flows + 1 + (p - p // 16) % flows
     fl = np.concatenate([np.arange(flows, dtype=np.int64), np.where(p % 16 == 0, newest, hit)])
     z = np.zeros_like(fl)
-    frames, lens = T.udp_frames(T.ip4(10, 0, 0, 0) + (fl >> 16), z, fl & 0xFFFF, z, slot=SLOT)
+    if nf == "pol":
+        frames, lens = T.udp_frames(np.full_like(fl, T.ip4(192, 168, 0, 1)),
+                                    T.ip4(10, 0, 0, 0) + fl, z + 53, z + 80, slot=SLOT)
+    else:
+        frames, lens = T.udp_frames(T.ip4(10, 0, 0, 0) + (fl >> 16), z, fl & 0xFFFF, z, slot=SLOT)
+    if nf == "bridge":
+        f = frames.reshape(n, SLOT)
+        f[:, 0:6] = np.array([0xFF, 0, 0, 0, 0, 1], np.uint8)
+        f[:, 6:9] = np.array([0x02, 0, 0], np.uint8)
+        f[:, 9] = (fl >> 16) & 0xFF
+        f[:, 10] = (fl >> 8) & 0xFF
+        f[:, 11] = fl & 0xFF
     now = T.NOW0 + 1000 * np.arange(n, dtype=np.int64)
     return frames, lens, np.zeros(n, np.uint16), now
+
+
+def churn_port(nf, n):
+    """--churn: every packet's out port -- the WAN port (vignat, vigfw), a
+    flood (vigbridge), the LAN port (vigpol)."""
+    return np.full(n, 0xFFFF if nf == "bridge" else 1, np.uint16)
 
 
 LB_BACKENDS = 256
@@ -136,7 +160,10 @@ def run_loop(tree, nf, tin, tout, flows, batch, env, churn=False):
         cmd += ["--batch", str(batch)]
     args, size = list(NF[nf]["args"]), flows
     if churn:  # four round-robin turns of 1 us packets; room for the idle flows
-        args[args.index("--expire") + 1] = str(4 * flows)
+        if nf == "pol":  # (1 B/ns: burst bytes last burst ns)
+            args[args.index("--burst") + 1] = str(4000 * flows)
+        else:
+            args[args.index("--expire") + 1] = str(4 * flows)
         size = 2 * flows
     cmd += ["--"] + args + [NF[nf]["size"], str(size)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300,
@@ -157,16 +184,21 @@ def main():
     ap.add_argument("--sweep", default="", help="burst sizes, each served and through the pipeline")
     ap.add_argument("--repeat", type=int, default=3, help="runs per point (all reported)")
     ap.add_argument("--churn", action="store_true",
-                    help="vignat, vigfw: a flow expires about every 16 packets")
+                    help="vignat, vigfw, vigbridge, vigpol: a flow expires about every 16 "
+                         "packets (vigpol: --rate 1000000000 --burst 4000 x flows)")
     ap.add_argument("--tree", default=ROOT)
     ap.add_argument("--label", default="")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     n = a.flows + a.packets
-    if a.churn and a.nf not in ("nat", "fw"):
-        ap.error("--churn: vignat and vigfw only")
-    fr, ln, dv, now = (churn_trace if a.churn else NF[a.nf]["trace"])(n, a.flows)
-    steady = NF[a.nf]["steady"](n, a.flows)
+    if a.churn and a.nf == "lb":
+        ap.error("--churn: not for viglb")
+    if a.churn:
+        fr, ln, dv, now = churn_trace(n, a.flows, a.nf)
+        steady = churn_port(a.nf, n)
+    else:
+        fr, ln, dv, now = NF[a.nf]["trace"](n, a.flows)
+        steady = NF[a.nf]["steady"](n, a.flows)
     n, warm = len(ln), len(ln) - a.packets  # (viglb: the heartbeats ahead of the flows)
     points = []
     if a.sweep:

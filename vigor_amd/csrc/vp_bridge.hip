@@ -388,10 +388,11 @@ __global__ void bridge_defer_finish(BridgeArgs a) {
 // vp_process_mbufs calls go to bridge_serve, one wave that stays resident and
 // polls the host-coherent mailbox (ServeBox, vp_internal.h), as nat_serve and
 // fw_serve do for vignat and vigfw: no launch and no copy call per packet.
-// The host sends requests only while no expiry is due (serve_process_one /
-// serve_process_burst), so the kernel restates bridge_main.c:311-329 without
-// the expiry step. The bridge never rewrites a frame and reads only its 12
-// MAC bytes.
+// Until the context meets a due expiry the host sends requests only while
+// none is due (serve_process_one / serve_process_burst) and the kernel
+// restates bridge_main.c:311-329 without the expiry step; from then on it runs
+// that step too, from the touch journal (serve_expire, vp_serve_dev.h). The
+// bridge never rewrites a frame and reads only its 12 MAC bytes.
 
 // T holds the CRC tables, then the layout's byte tables (kMixLin).
 constexpr uint32_t kBridgeTabWords = kBridgeTabs * 256 + 1024;
@@ -442,30 +443,46 @@ __device__ __forceinline__ uint32_t bridge_learn(const TableDev &t, uint32_t sh,
 // lookup in bridge_main.c:316-320. A hit of round 0 is final: nothing expires
 // inside a burst and a known MAC's port never changes. Only the learn stamps
 // (bridge_main.c:66-69, 86), so burst_last runs over the src index. Nothing
-// of a frame comes back and no burst is declined.
+// of a frame comes back and no burst is declined. With the journal on (J) the
+// expiries due at the first packet run first (bridge_main.c:311-315: before
+// the learn, so a dst that has just expired is unknown and a src that has is
+// learnt again, from the port it now comes from) and *k <= n packets are
+// served (burst_split); the walk precedes round 0, whose hits stay final.
+template <bool J>
 __device__ __forceinline__ uint32_t bridge_burst(const BridgeArgs &a, const uint32_t *T,
                                                  ServeBox *box, uint32_t n, uint64_t seq0,
-                                                 uint32_t lane) {
+                                                 uint32_t lane, const JournalDev &j,
+                                                 JournalSt &js, uint32_t *k) {
   const TableDev &t = a.t;
   const BurstIn b = burst_load(box, n, lane);
+  bool act = b.act;
+  int64_t now0 = 0;
+  if (J) {
+    n = burst_split(t, j, js, b, n, lane, &now0);
+    if (!n) return kBurstFull;
+    act = act && lane < n;
+  }
+  *k = n;
   const uint32_t in = b.in;
   const Macs m = macs_of(b.f.w[0], b.f.w[1], b.f.w[2]);
   uint32_t sh, dh;
   eth_hash2(T, m.s0, m.s1, m.d0, m.d1, &sh, &dh);
   // round 0, then the misses in packet order
   int32_t st_fwd = 0;
-  const bool st_hit = b.act && bridge_static(a, T, dh, m.d0, m.d1, in, &st_fwd);
+  const bool st_hit = act && bridge_static(a, T, dh, m.d0, m.d1, in, &st_fwd);
   uint32_t si = kNone, di = kNone, port = 0, fresh = 0;
-  if (b.act) {
+  if (act) {
     uint32_t unused = 0;
     si = mac_probe(t, sh, m.s0, m.s1, &unused);
     if (!st_hit) di = mac_probe(t, dh, m.d0, m.d1, &port);
   }
   burst_settle(
-      lane, b.act && si == kNone, b.act && !st_hit && di == kNone,
+      lane, act && si == kNone, act && !st_hit && di == kNone,
       [&] { di = mac_probe(t, dh, m.d0, m.d1, &port); },
       [&] { si = bridge_learn(t, sh, m.s0, m.s1, in, seq0 + lane, &fresh); });
-  if (burst_last(si, n, lane)) serve_stamp(t, si, b.now, seq0 + lane);
+  const bool won = burst_last(si, n, lane);
+  if (won) serve_stamp(t, si, b.now, seq0 + lane);
+  if (J) journal_touch_burst(j, js, won, si, seq0 + lane, now0, lane);
   const uint32_t out = st_hit ? resolve(st_fwd, in)
                        : di != kNone ? (port & 0xFFFFu)
                                      : (uint32_t)VP_FLOOD_FRAME;
@@ -483,9 +500,13 @@ __device__ __forceinline__ uint32_t bridge_burst(const BridgeArgs &a, const uint
 // seq0 + 1, ...; a burst request (bridge_burst) takes as many as it has
 // frames. The kernel leaves on the leave request or after `idle` wall-clock
 // ticks without a request; the host launches it again (serve_wait). flags:
-// serve_poll's.
+// serve_poll's. J: the kernel expires from the touch journal j
+// (vp_serve_dev.h), the whole wave's walk before lane 0's learn, and the answer
+// chunk carries the walk's count; a context whose journal is off runs the
+// instance without any of it.
+template <bool J>
 __global__ __launch_bounds__(64) void bridge_serve(BridgeArgs a, ServeBox *box, uint64_t seq0,
-                                                   uint64_t idle, uint32_t flags) {
+                                                   uint64_t idle, uint32_t flags, JournalDev j) {
   __shared__ uint32_t T[kBridgeTabWords];
   const uint32_t lane = threadIdx.x;
   for (uint32_t i = lane; i < kBridgeTabs * 256; i += 64) T[i] = a.crc_tab[i];
@@ -501,17 +522,22 @@ __global__ __launch_bounds__(64) void bridge_serve(BridgeArgs a, ServeBox *box, 
       &box->ans, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM));
   uint64_t seq = seq0;
   uint64_t t0 = wall_clock64();
+  // the touch journal's control words
+  JournalSt js = journal_load(J ? j : JournalDev{});
   auto serve = [&](const v4u &c) -> int {
     const uint32_t want = done + 1;
     if (__builtin_amdgcn_readfirstlane(c[3]) != want) return -1;
     const uint32_t hi = __builtin_amdgcn_readfirstlane(c[0]);
     if (hi == kServeLeave) return 1;
     const uint32_t in = hi >> 16;
+    js.expired = 0, js.flags = 0;
     if ((hi & 0xFFFFu) == kServeBurstOp) {  // chunk 0 alone, the frames in the burst body
-      const uint32_t bn = min(max(in, 1u), kServeBurst);
-      const uint32_t st = bridge_burst(a, T, box, bn, seq, lane);
-      if (lane == 0) burst_answer(io, box, st, bn, want);
-      seq += bn;
+      uint32_t bn = min(max(in, 1u), kServeBurst);
+      uint32_t st = bridge_burst<J>(a, T, box, bn, seq, lane, j, js, &bn);
+      if (J && st == kBurstServed && js.flags) st |= kBurstTombs;
+      if (J) journal_store(j, js, lane);
+      if (lane == 0) burst_answer(io, box, st, bn, want, js.expired);
+      if ((st & 0xFFu) == kBurstServed) seq += bn;
       t0 = wall_clock64();
       done = want;
       // (every lane's table writes before the next request reads them)
@@ -523,19 +549,29 @@ __global__ __launch_bounds__(64) void bridge_serve(BridgeArgs a, ServeBox *box, 
     const uint32_t got = min(len, 12u);          // frame bytes in chunk 1
     const uint32_t need = (12 + got + 11) / 12;  // chunks carrying the request
     if (__ballot(lane < need && c[3] != want)) return -1;  // not whole yet: poll again
-    const int64_t now = serve_now(c);
+    // (J: the cutoff compare needs the time exact -- both halves widened as
+    // unsigned, as pol_serve reads it)
+    const int64_t now =
+        J ? (int64_t)((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(c[1]) |
+                      ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(c[2]) << 32))
+          : serve_now(c);
     const uint4 h = chunk_keep(make_uint4((uint32_t)__builtin_amdgcn_readlane((int)c[0], 1),
                                           (uint32_t)__builtin_amdgcn_readlane((int)c[1], 1),
                                           (uint32_t)__builtin_amdgcn_readlane((int)c[2], 1), 0u),
                                0, (int)got);
-    uint32_t res = 0;
-    if (lane == 0) {
+    uint32_t res = 0, tix = kNone;
+    const bool full = J && !journal_room(j, js, 1);  // (nothing is done: seeded again)
+    // bridge_main.c:311-315: the expiry before the learn
+    if (J && !full) serve_expire(a.t, j, js, journal_cutoff(j, now), lane);
+    if (full) res = kOneFull;
+    if (lane == 0 && !full) {
       const Macs m = macs_of(h.x, h.y, h.z);
       uint32_t sh, dh;
       eth_hash2(T, m.s0, m.s1, m.d0, m.d1, &sh, &dh);
       uint32_t fresh = 0;
       const uint32_t si = bridge_learn(a.t, sh, m.s0, m.s1, in, seq, &fresh);
       if (si != kNone) serve_stamp(a.t, si, now, seq);
+      tix = si;  // (only the learn touches; the dst lookup does not stamp)
       int32_t fwd = 0;
       uint32_t out;
       if (bridge_static(a, T, dh, m.d0, m.d1, in, &fwd)) {
@@ -545,18 +581,22 @@ __global__ __launch_bounds__(64) void bridge_serve(BridgeArgs a, ServeBox *box, 
         const uint32_t di = mac_probe(a.t, dh, m.d0, m.d1, &port);
         out = di != kNone ? (port & 0xFFFFu) : (uint32_t)VP_FLOOD_FRAME;
       }
-      res = (out & 0xFFFFu) | (fresh << 16);
+      res = (out & 0xFFFFu) | (fresh << 16) | js.flags;
     }
     res = __builtin_amdgcn_readfirstlane(res);
+    if (J) {
+      journal_touch(j, js, __builtin_amdgcn_readfirstlane(tix), seq, now, lane);
+      journal_store(j, js, lane);
+    }
     if (lane == 0) {
-      __builtin_amdgcn_raw_buffer_store_b128((v4u){res, 0u, 0u, want}, io.as, 0, 0, kSys);
+      __builtin_amdgcn_raw_buffer_store_b128((v4u){res, js.expired, 0u, want}, io.as, 0, 0, kSys);
       // (the answer word: where a relaunched server starts counting; the host
       // reads the answer chunk. No release fence at system scope, which would
       // write back the whole L2)
       __hip_atomic_store(&box->ans, (uint64_t)want | ((uint64_t)res << 32), __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    seq += 1;
+    if (!full) seq += 1;
     t0 = wall_clock64();
     done = want;
     // (lane 0's table writes before the next request's lanes read them)
@@ -569,6 +609,8 @@ __global__ __launch_bounds__(64) void bridge_serve(BridgeArgs a, ServeBox *box, 
 
 // =============================================================== host ==
 
+// bridge_main.c:29-36: expiration_time * 1000 in 32 bits. The journal's E is
+// 0 - bridge_cutoff(c, 0) (serve_expire_e): the wrapped product itself.
 static inline int64_t bridge_cutoff(const vp_ctx *c, int64_t t) {
   const uint32_t e = c->brg.expiration_time * 1000u;  // u32, as vignat
   return (int64_t)((uint64_t)t - e);
@@ -680,7 +722,11 @@ int bridge_process_device(vp_ctx *c, const vp_dev_batch *b) {
 int bridge_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
   BridgeArgs a{};
   bridge_tables(c, &a);
-  bridge_serve<<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags);
+  const JournalDev j = serve_journal_dev(c, bridge_serve_nf());
+  if (j.ctl)
+    bridge_serve<true><<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags, j);
+  else
+    bridge_serve<false><<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags, j);
   VP_HIP(hipGetLastError());
   return 0;
 }
@@ -697,10 +743,11 @@ constexpr uint32_t kBridgeBurstRoute = 384;
 // vigbridge through the mailbox (serve_process_one / serve_process_burst,
 // vp_serve.hip): bridge_serve reads a frame's 12 MAC bytes and changes none,
 // so one packet sends 12 bytes and takes none back; a burst copies a frame's
-// first 16 bytes in and nothing back. No stage clock.
+// first 16 bytes in and nothing back. No stage clock. The kernel expires from
+// the touch journal.
 const ServeNf &bridge_serve_nf() {
-  static const ServeNf nf = {bridge_cutoff, &vp_ctx::ft, false, 12, 0, 16, 0, kBridgeBurstRoute,
-                             false};
+  static const ServeNf nf = {bridge_cutoff, &vp_ctx::ft, false,   12,      0,   16, 0,
+                             kBridgeBurstRoute, false,   nullptr, nullptr, true};
   return nf;
 }
 

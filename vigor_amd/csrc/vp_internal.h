@@ -415,7 +415,7 @@ struct ServeBox {
 constexpr uint32_t kServeBurst = 64;       // frames per burst request
 constexpr uint32_t kServeBurstOp = 0xFFFFu;  // message word 0, low half: a burst
 constexpr uint32_t kBurstServed = 0, kBurstDeclined = 1;  // answer chunk 0, word 0
-// With the touch journal on (vignat, vigfw) a burst's answer chunk 0 is
+// With the touch journal on (all but viglb) a burst's answer chunk 0 is
 // {status, k, expired, request number}: k packets were served (the rest is
 // posted again: an expiry falls due at packet k), `expired` entries left
 // before them. kBurstFull: the journal has no room for the request's touches
@@ -492,7 +492,7 @@ struct ServeNf {
   int64_t (*cutoff2)(const vp_ctx *c, int64_t t) = nullptr;
   FlowTable vp_ctx::*table2 = nullptr;
   // the resident kernel expires entries itself from a touch journal once the
-  // context has met a due expiry (vignat, vigfw; serve_journal_ok)
+  // context has met a due expiry (all but viglb; serve_journal_ok)
   bool journal = false;
 };
 const ServeNf &nat_serve_nf();

@@ -449,10 +449,13 @@ __global__ __launch_bounds__(256) void pol_last_ipv4(const uint8_t *frames,
 // vp_process_mbufs calls go to pol_serve, one wave that stays resident and
 // polls the host-coherent mailbox (ServeBox, vp_internal.h), as nat_serve,
 // fw_serve and bridge_serve do for their NFs: no launch and no copy call per
-// packet. The host sends requests only while no expiry is due
-// (serve_process_one / serve_process_burst), so the kernel restates
-// policer_main.c:111-145 and 34-103 without policer_expire_entries. The
-// policer never rewrites a frame and reads only its first 34 bytes (the
+// packet. Until the context meets a due expiry the host sends requests only
+// while none is due (serve_process_one / serve_process_burst) and the kernel
+// restates policer_main.c:111-145 and 34-103 without policer_expire_entries;
+// from then on it runs that too, from the touch journal (serve_expire,
+// vp_serve_dev.h) -- behind the IPv4 parse only, as policer_main.c:113-123
+// does: an IPv4 packet from any device expires, a frame that does not parse
+// never does. The policer never rewrites a frame and reads only its first 34 bytes (the
 // policed address is bytes 30-33); IPv4 options do not matter to it (it never
 // parses L4), so nothing is declined.
 
@@ -528,13 +531,27 @@ __device__ __forceinline__ uint32_t pol_pass(const PolServeArgs &a, bool v4, uin
 // 64-bit mask each member reads afterwards, and stores the bucket once; the
 // chain's last lane stamps (every policed packet rejuvenates,
 // policer_main.c:38).
+//
+// With the journal on (J) the walk runs at the first lane whose IPv4 header
+// parses and the burst is cut at the next parsing lane at which an entry falls
+// due (burst_split_if): *k <= n packets are served and the chains run over
+// those alone. An address that expires at lane k and is policed by lane k so
+// meets the next request's walk first and is allocated afresh there.
+template <bool J>
 __device__ __forceinline__ uint32_t pol_burst(const PolServeArgs &a, const uint32_t *T,
                                               ServeBox *box, uint32_t n, uint64_t seq0,
-                                              uint32_t lane) {
+                                              uint32_t lane, const JournalDev &j, JournalSt &js,
+                                              uint32_t *k) {
   const TableDev &t = a.t;
   const BurstIn b = burst_load(box, n, lane);
   const bool v4 = pol_ipv4_r(b.f.w[3], b.f.w[4], b.len);
-  const bool police = b.act && v4 && b.in == a.wan();
+  int64_t now0 = 0;
+  if (J) {
+    n = burst_split_if(t, j, js, b, v4, n, lane, &now0);
+    if (!n) return kBurstFull;
+  }
+  *k = n;
+  const bool police = b.act && lane < n && v4 && b.in == a.wan();
   const uint32_t dst = b.f.u32at2(30);
   const uint32_t hh = pol_hash(T, dst);
   const uint32_t key[4] = {dst, 0, 0, 0};
@@ -555,7 +572,9 @@ __device__ __forceinline__ uint32_t pol_burst(const PolServeArgs &a, const uint3
   }
   const bool policed = idx != kNone;
   const bool first = policed && own == lane;
-  if (policed && nxt == kServeBurst) serve_stamp(t, idx, b.now, seq0 + lane);
+  const bool won = policed && nxt == kServeBurst;
+  if (won) serve_stamp(t, idx, b.now, seq0 + lane);
+  if (J) journal_touch_burst(j, js, won, idx, seq0 + lane, now0, lane);
   // the ordered replay
   uint64_t size = 0, btu = 0, took = 0;
   if (first) {
@@ -605,9 +624,14 @@ __device__ __forceinline__ uint32_t pol_burst(const PolServeArgs &a, const uint3
 // take global sequence numbers seq0, seq0 + 1, ...; a burst request
 // (pol_burst) takes as many as it has frames. The kernel leaves on the leave
 // request or after `idle` wall-clock ticks without a request; the host
-// launches it again (serve_wait). flags: serve_poll's.
+// launches it again (serve_wait). flags: serve_poll's. J: the kernel expires
+// from the touch journal j (vp_serve_dev.h) -- the whole wave's walk, when the
+// IPv4 header parses (wave-uniform words), before lane 0's packet -- and the
+// answer chunk carries the walk's count; a context whose journal is off runs
+// the instance without any of it.
+template <bool J>
 __global__ __launch_bounds__(64) void pol_serve(PolServeArgs a, ServeBox *box, uint64_t seq0,
-                                                uint64_t idle, uint32_t flags) {
+                                                uint64_t idle, uint32_t flags, JournalDev j) {
   __shared__ uint32_t T[kPolTabWords];
   const uint32_t lane = threadIdx.x;
   for (uint32_t i = lane; i < kPolTabs * 256; i += 64) T[i] = a.crc_tab[i];
@@ -623,17 +647,22 @@ __global__ __launch_bounds__(64) void pol_serve(PolServeArgs a, ServeBox *box, u
       &box->ans, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM));
   uint64_t seq = seq0;
   uint64_t t0 = wall_clock64();
+  // the touch journal's control words
+  JournalSt js = journal_load(J ? j : JournalDev{});
   auto serve = [&](const v4u &c) -> int {
     const uint32_t want = done + 1;
     if (__builtin_amdgcn_readfirstlane(c[3]) != want) return -1;
     const uint32_t hi = __builtin_amdgcn_readfirstlane(c[0]);
     if (hi == kServeLeave) return 1;
     const uint32_t in = hi >> 16;
+    js.expired = 0, js.flags = 0;
     if ((hi & 0xFFFFu) == kServeBurstOp) {  // chunk 0 alone, the frames in the burst body
-      const uint32_t bn = min(max(in, 1u), kServeBurst);
-      const uint32_t st = pol_burst(a, T, box, bn, seq, lane);
-      if (lane == 0) burst_answer(io, box, st, bn, want);
-      seq += bn;
+      uint32_t bn = min(max(in, 1u), kServeBurst);
+      uint32_t st = pol_burst<J>(a, T, box, bn, seq, lane, j, js, &bn);
+      if (J && st == kBurstServed && js.flags) st |= kBurstTombs;
+      if (J) journal_store(j, js, lane);
+      if (lane == 0) burst_answer(io, box, st, bn, want, js.expired);
+      if ((st & 0xFFu) == kBurstServed) seq += bn;
       t0 = wall_clock64();
       done = want;
       // (every lane's table writes before the next request reads them)
@@ -662,9 +691,13 @@ __global__ __launch_bounds__(64) void pol_serve(PolServeArgs a, ServeBox *box, u
                         bytes_mask(0, (int)got - 28);
     const uint32_t w8 = (uint32_t)__builtin_amdgcn_readlane((int)c[2], 3) &
                         bytes_mask(0, (int)got - 32);
-    uint32_t res = 0;
-    if (lane == 0) {
-      const bool v4 = pol_ipv4_r(w3, w4, len);
+    uint32_t res = 0, tix = kNone;
+    const bool v4 = pol_ipv4_r(w3, w4, len);
+    const bool full = J && !journal_room(j, js, 1);  // (nothing is done: seeded again)
+    // policer_main.c:113-123: the expiry behind the parse, whatever the device
+    if (J && !full && v4) serve_expire(a.t, j, js, journal_cutoff(j, now), lane);
+    if (full) res = kOneFull;
+    if (lane == 0 && !full) {
       uint32_t out = pol_pass(a, v4, in), fresh = 0;
       if (v4 && in == a.wan()) {
         const uint32_t dst = (w7 >> 16) | (w8 << 16);  // bytes 30-33
@@ -688,19 +721,24 @@ __global__ __launch_bounds__(64) void pol_serve(PolServeArgs a, ServeBox *box, u
           }
         }
         out = fwd ? a.lan() : a.wan();
+        tix = idx;  // (a policed hit or an allocation: the index the packet touched)
       }
-      res = (out & 0xFFFFu) | (fresh << 16);
+      res = (out & 0xFFFFu) | (fresh << 16) | js.flags;
     }
     res = __builtin_amdgcn_readfirstlane(res);
+    if (J) {
+      journal_touch(j, js, __builtin_amdgcn_readfirstlane(tix), seq, now, lane);
+      journal_store(j, js, lane);
+    }
     if (lane == 0) {
-      __builtin_amdgcn_raw_buffer_store_b128((v4u){res, 0u, 0u, want}, io.as, 0, 0, kSys);
+      __builtin_amdgcn_raw_buffer_store_b128((v4u){res, js.expired, 0u, want}, io.as, 0, 0, kSys);
       // (the answer word: where a relaunched server starts counting; the host
       // reads the answer chunk. No release fence at system scope, which would
       // write back the whole L2)
       __hip_atomic_store(&box->ans, (uint64_t)want | ((uint64_t)res << 32), __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    seq += 1;
+    if (!full) seq += 1;
     t0 = wall_clock64();
     done = want;
     // (lane 0's table writes before the next request's lanes read them)
@@ -915,7 +953,11 @@ int pol_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
   a.bsize = c->pol_size;
   a.btime = c->pol_time;
   a.ports = (uint32_t)c->pol.lan_device | ((uint32_t)c->pol.wan_device << 16);
-  pol_serve<<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags);
+  const JournalDev j = serve_journal_dev(c, pol_serve_nf());
+  if (j.ctl)
+    pol_serve<true><<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags, j);
+  else
+    pol_serve<false><<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags, j);
   VP_HIP(hipGetLastError());
   return 0;
 }
@@ -935,9 +977,13 @@ constexpr uint32_t kPolBurstRoute = 512;
 // vp_serve.hip): pol_serve reads a frame's first 34 bytes and changes none,
 // so one packet sends 34 bytes and takes none back; a burst copies a frame's
 // first 48 bytes in (burst_load reads 64 of the slot; what lies past byte 34
-// is never looked at) and nothing back. No stage clock.
+// is never looked at) and nothing back. No stage clock. The kernel expires
+// from the touch journal; its E is 0 - pol_cutoff(c, 0) (serve_expire_e), the
+// 64-bit burst * 1e9 / rate itself, and a lifetime that does not fit a signed
+// 64-bit time leaves the journal off (serve_journal_ok).
 const ServeNf &pol_serve_nf() {
-  static const ServeNf nf = {pol_cutoff, &vp_ctx::ft, false, 34, 0, 48, 0, kPolBurstRoute, false};
+  static const ServeNf nf = {pol_cutoff,     &vp_ctx::ft, false,   34,      0,   48, 0,
+                             kPolBurstRoute, false,       nullptr, nullptr, true};
   return nf;
 }
 

@@ -181,12 +181,13 @@ uint32_t serve_burst_limit(uint32_t dflt) {  // VIGPATH_SERVE_BURST
 // ------------------------------------------------------ the touch journal --
 // Expiry inside the resident kernel (vp_serve_dev.h). The
 // expiry time E of the NF's cutoff, cutoff(t) = t - E in u64 arithmetic
-// (vignat's 32-bit wrap inside it).
+// (vignat's and vigbridge's 32-bit wrap inside it, vigpol's 64-bit
+// burst * 1e9 / rate).
 static uint64_t serve_expire_e(const vp_ctx *c, const ServeNf &nf) {
   return (uint64_t)0 - (uint64_t)nf.cutoff(c, 0);
 }
 
-// Whether c's kernel may expire: the NF has the walk (vignat, vigfw),
+// Whether c's kernel may expire: the NF has the walk (all but viglb),
 // VIGPATH_SERVE_EXPIRE is not 0, vignat polls with one wave (the journal's
 // control words live in that wave's registers), and E is not negative (a
 // packet would then expire the flow it has just touched).

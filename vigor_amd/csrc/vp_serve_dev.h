@@ -75,7 +75,8 @@ __device__ __forceinline__ void serve_stamp(const TableDev &t, uint32_t idx, int
 }
 
 // --------------------------------------------------- the touch journal --
-// Expiry inside the resident kernel (vignat, vigfw; JournalDev, vp_table.h).
+// Expiry inside the resident kernel (vignat, vigfw, vigbridge, vigpol;
+// JournalDev, vp_table.h).
 // The wave keeps the journal's control words in registers (wave-uniform) and
 // stores them back after every request (journal_store), so a kernel launched
 // again after an idle exit or a stop goes on from them (journal_load).
@@ -354,6 +355,33 @@ __device__ __forceinline__ uint32_t burst_split(const TableDev &t, const Journal
   serve_expire(t, j, s, journal_cutoff(j, n0), lane);
   const int64_t lim = s.floor < n0 ? s.floor : n0;
   const uint64_t due = __ballot(b.act && lane > 0 && journal_cutoff(j, b.now) > lim);
+  return due ? (uint32_t)__ffsll((unsigned long long)due) - 1 : n;
+}
+
+// The same for an NF whose expiry runs only at some packets (vigpol: behind
+// the IPv4 parse, policer_main.c:113-123; `runs` is the lane's predicate, and
+// only such lanes stamp). With v the lowest active lane that runs it, the walk
+// is v's, at its time now_v, and k is the first running lane above v whose
+// cutoff passes min(F, now_v): the stamps of the burst are at or after now_v,
+// and a lane that does not run the expiry never cuts the burst. No running
+// lane: no walk, and all n are served (they touch nothing). *now0 = now_v, the
+// lower bound of the burst's stamps.
+__device__ __forceinline__ uint32_t burst_split_if(const TableDev &t, const JournalDev &j,
+                                                   JournalSt &s, const BurstIn &b, bool runs,
+                                                   uint32_t n, uint32_t lane, int64_t *now0) {
+  if (!journal_room(j, s, min(n, t.cap))) return 0;
+  const uint64_t rb = __ballot(b.act && runs);
+  if (!rb) return n;
+  const int v = __ffsll((unsigned long long)rb) - 1;
+  const uint64_t u = (uint64_t)b.now;
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)(uint32_t)u, v));
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)(uint32_t)(u >> 32), v));
+  const int64_t nv = (int64_t)((uint64_t)lo | ((uint64_t)hi << 32));
+  *now0 = nv;
+  serve_expire(t, j, s, journal_cutoff(j, nv), lane);
+  const int64_t lim = s.floor < nv ? s.floor : nv;
+  const uint64_t due =
+      __ballot(b.act && runs && (int)lane > v && journal_cutoff(j, b.now) > lim);
   return due ? (uint32_t)__ffsll((unsigned long long)due) - 1 : n;
 }
 

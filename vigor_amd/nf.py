@@ -300,7 +300,8 @@ class NfBase:
 
     def serve_expiry_stats(self) -> dict:
         """vp_serve_expiry_stats_get: expiry inside the resident kernel
-        (vignat, vigfw; all zero for the other NFs) -- seeds (journal builds),
+        (vignat, vigfw, vigbridge, vigpol; all zero for viglb, whose due
+        expiries stay the pipeline's) -- seeds (journal builds),
         expired (entries the kernel expired), walks (requests that expired at
         least one), handed (requests that took the pipeline because an expiry
         was due), splits (bursts served in part, the rest posted again). A
