@@ -201,11 +201,13 @@ int vp_unregister_host(vp_ctx *ctx, void *base);
  * burst requests of up to 64 frames, one lane of a wave per packet, while no
  * expiry is due anywhere in the call (viglb: on its flows or its backends), every frame is at most 2048 bytes
  * and the times do not go back: no launch, no copy call, and the kernel stays
- * for the next call (nf.c's VIGOR_BATCH_SIZE loop, nf.c:178-215). vignat,
- * vigfw, vigbridge and vigpol hand over only the first call at which an expiry
- * is due: from the next one on their kernel expires the entries itself before
+ * for the next call (nf.c's VIGOR_BATCH_SIZE loop, nf.c:178-215). Every NF
+ * hands over only the first call at which an expiry
+ * is due: from the next one on its kernel expires the entries itself before
  * each request (vp_serve_expiry_stats_get; vigpol, as the reference, only at
- * packets whose IPv4 header parses), and a burst inside which an expiry falls
+ * packets whose IPv4 header parses; viglb its flows and then its backends,
+ * each on its own lifetime, at every packet whatever its frame), and a burst
+ * inside which an expiry falls
  * due is served up to that packet and the rest posted as the next request.
  * VIGPATH_SERVE_EXPIRE=0 turns that off (every due expiry takes the path
  * above); VIGPATH_SERVE_JOURNAL sets the journal's size in records per table
@@ -215,9 +217,11 @@ int vp_unregister_host(vp_ctx *ctx, void *base);
  * and vigpol, which never parses L4, hand none back. vigpol's packets to one
  * destination address pass through its token bucket in packet order. viglb's
  * heartbeats from unknown addresses, new flows and flows whose backend died
- * settle in packet order inside the burst; the one thing its kernel leaves to
- * the path above is the erasure of a flow whose backend died while no backend
- * is alive: that request is handed back too. */
+ * settle in packet order inside the burst, and a backend that expires in the
+ * kernel is dead for the packets behind it: its flows are re-pointed. The one
+ * thing viglb's kernel leaves to the path above is the erasure of a flow whose
+ * backend died while no backend is alive: that request is handed back too
+ * (the expiries due at it are done by then, and counted). */
 typedef struct vp_mbuf_batch {
   uint32_t n;
   uint8_t *const *frames;
@@ -244,7 +248,7 @@ int vp_process_batch(vp_ctx *ctx, uint32_t n, const uint16_t *in_dev,
  * kernel that polls a host-coherent mailbox (no launch per packet) while no
  * expiry is due at `now`; otherwise, and for the one packet viglb's kernel
  * hands back (the erasure of a flow with no backend alive), it is
- * vp_process_batch with n = 1. vignat, vigfw, vigbridge and vigpol take that
+ * vp_process_batch with n = 1. Every NF takes that
  * path only for the first packet at which an expiry is due: afterwards the kernel expires the
  * entries itself, before the packet, and stays (vp_serve_expiry_stats_get;
  * VIGPATH_SERVE_EXPIRE=0: off).
@@ -391,17 +395,19 @@ typedef struct vp_serve_stats {
 } vp_serve_stats;
 int vp_serve_stats_get(vp_ctx *ctx, vp_serve_stats *out);
 
-/* Expiry inside the resident kernel (vignat, vigfw, vigbridge and vigpol;
- * all zero for viglb, which hands every due expiry over), since the context
+/* Expiry inside the resident kernel (every served NF), since the context
  * was created. The first request at which an expiry
  * is due takes the batch pipeline (`handed`); the next launch builds a touch
  * journal from the table (`seeds`) and from then on the kernel expires entries
  * itself, in the reference's LRU order, before every request. A pipeline call
  * that processes packets (a large batch, a declined burst) drops the journal:
- * the next due expiry is handed over once more and seeds it again. A read of
+ * the next due expiry is handed over once more and seeds it again. viglb has
+ * two expiring tables and a journal for each: `handed` counts a request at
+ * which either table was due, `seeds` counts tables, so one seeding of viglb
+ * adds 2, and `expired` is the sum over both. A read of
  * host-side counters: the kernel stays. */
 typedef struct vp_serve_expiry_stats {
-  uint64_t seeds;    /* journal builds from the table (first and re-seeds) */
+  uint64_t seeds;    /* journal builds from a table (first and re-seeds; viglb: 2 a time) */
   uint64_t expired;  /* entries the resident kernel expired */
   uint64_t walks;    /* requests at which it expired at least one */
   uint64_t handed;   /* requests that took the pipeline because an expiry was due */

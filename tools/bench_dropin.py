@@ -13,7 +13,7 @@ and through vp_process_batch in bursts (nf.c:178-215).
   tools/bench_dropin.py --nf lb                      # viglb: 256 backends, 1,024 flows
   tools/bench_dropin.py --nf nat --churn --batches 0,32   # flows expiring all along
 
---churn (vignat, vigfw, vigbridge, vigpol): every 16th timed packet opens a
+--churn (every NF; viglb's trace is below): every 16th timed packet opens a
 never-seen flow and the others hit the `--flows` most recent flows round
 robin, so the oldest flow goes idle each time; the clock advances 1 us a
 packet and `--expire` is four round-robin turns (4 x flows us), so in steady
@@ -24,6 +24,14 @@ policed address, and the lifetime burst * 1e9 / rate is set by --rate
 1000000000 --burst 4000 x flows (4,096,000 for 1,024 flows: 4.096 ms, and no
 bucket of 64-byte packets runs dry). VIGPATH_SERVE_EXPIRE=0 in the environment
 gives the path that hands every due expiry to the batch pipeline.
+
+--churn --nf lb: the warm-up announces 16 backends ahead of the flows; flows
+churn as above; every 16th timed packet at offset 8 is a heartbeat, round robin
+over the backends except one in turn, which stays silent for 5 x flows packets
+-- longer than the backend lifetime -- so a backend expires, its flows are
+re-pointed, and it comes back, again and again in the run. Both lifetimes are
+4 x flows us. The tool prints the CPU oracle's expiry counts per table for the
+trace first.
 
 --sweep N,...: each burst size twice in this run, VIGPATH_SERVE_BURST forcing
 the resident kernel (a limit above every N) and the batch pipeline (0): the
@@ -106,6 +114,57 @@ def churn_port(nf, n):
 
 
 LB_BACKENDS = 256
+LB_CHURN_BACKENDS = 16
+
+
+def lb_churn_trace(n, flows):
+    """--churn --nf lb: LB_CHURN_BACKENDS heartbeats and `flows` WAN flows for
+    the warm-up, then n - flows timed packets, 1 us each: packet p opens flow
+    flows + p / 16 when p is a multiple of 16, is a heartbeat when p mod 16 is
+    8 -- of backend (p / 16) mod 16, or of the next one while that one is the
+    silent backend (p / (5 flows)) mod 16 --, and else hits one of the `flows`
+    newest flows, round robin."""
+    nb = LB_CHURN_BACKENDS
+    p = np.arange(n - flows, dtype=np.int64)
+    newest = flows - 1 + (p // 16 + 1)
+    hit = newest - flows + 1 + (p - p // 16 - (p + 8) // 16) % flows
+    fl = np.concatenate([np.arange(flows, dtype=np.int64), np.where(p % 16 == 0, newest, hit)])
+    z = np.zeros_like(fl)
+    frames, lens = T.udp_frames(T.ip4(11, 0, 0, 0) + fl, z, z, z, slot=SLOT)
+    dv = np.full(n, 2, np.uint16)
+    silent = (p // (5 * flows)) % nb
+    b = (p // 16) % nb
+    b = np.where(b == silent, (b + 1) % nb, b)
+    hb = np.nonzero(p % 16 == 8)[0]
+    hf, _, hd, _ = T.lb_heartbeats(nb)
+    f = frames.reshape(n, SLOT)
+    f[flows + hb] = hf.reshape(nb, SLOT)[b[hb]]
+    dv[flows + hb] = hd[b[hb]]
+    w = T.lb_heartbeats(nb)
+    frames = np.concatenate([w[0], f.reshape(-1)])
+    lens = np.concatenate([w[1], lens])
+    dv = np.concatenate([w[2], dv])
+    now = T.NOW0 + 1000 * np.arange(nb + n, dtype=np.int64)
+    return frames, lens, dv, now
+
+
+def lb_churn_oracle(frames, lens, dv, now, flows):
+    """The CPU oracle's expiry counts per table over that trace: the entries
+    allocated before a packet and stamped below its time less the lifetime."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import orc
+    fcap, bcap, e_ns = 2 * flows, LB_CHURN_BACKENDS, 4 * flows * 1000
+    cfg = orc.LbCfg(flow_capacity=fcap, flow_expiration_time=4 * flows, backend_capacity=bcap,
+                    cht_height=17, backend_expiration_time=4 * flows, wan_device=2, n_devices=3)
+    o = orc.Oracle("lb", cfg)
+    F = frames.reshape(-1, SLOT).copy()
+    nf = nb = 0
+    for i in range(F.shape[0]):
+        (fa, ft, _, _), (ba, bt, _, _, _) = o.lb_dump(fcap, bcap)
+        nf += int(((fa == 1) & (ft < int(now[i]) - e_ns)).sum())
+        nb += int(((ba == 1) & (bt < int(now[i]) - e_ns)).sum())
+        o.run(F[i], lens[i:i + 1], dv[i:i + 1], now[i:i + 1], SLOT)
+    return {"flows_expired": nf, "backends_expired": nb}
 
 
 def lb_trace(n, flows):
@@ -154,17 +213,23 @@ NF = {
 
 def run_loop(tree, nf, tin, tout, flows, batch, env, churn=False):
     """One nf_loop run: us per timed packet (its out ports are left in tout)."""
-    cmd = [os.path.join(tree, "host", NF[nf]["loop"]), tin, tout, "--warm",
-           str(flows + NF[nf].get("warm", 0))]
+    cmd = [os.path.join(tree, "host", NF[nf]["loop"]), tin, tout]
     if batch:
         cmd += ["--batch", str(batch)]
     args, size = list(NF[nf]["args"]), flows
+    warm = NF[nf].get("warm", 0)
     if churn:  # four round-robin turns of 1 us packets; room for the idle flows
         if nf == "pol":  # (1 B/ns: burst bytes last burst ns)
             args[args.index("--burst") + 1] = str(4000 * flows)
+        elif nf == "lb":
+            warm = LB_CHURN_BACKENDS
+            for k, v in [("--backend-capacity", LB_CHURN_BACKENDS), ("--cht-height", 17),
+                         ("--flow-expiration", 4 * flows), ("--backend-expiration", 4 * flows)]:
+                args[args.index(k) + 1] = str(v)
         else:
             args[args.index("--expire") + 1] = str(4 * flows)
         size = 2 * flows
+    cmd[3:3] = ["--warm", str(flows + warm)]
     cmd += ["--"] + args + [NF[nf]["size"], str(size)]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300,
                        env=dict(os.environ, **NF[nf].get("env", {}), **env))
@@ -184,16 +249,19 @@ def main():
     ap.add_argument("--sweep", default="", help="burst sizes, each served and through the pipeline")
     ap.add_argument("--repeat", type=int, default=3, help="runs per point (all reported)")
     ap.add_argument("--churn", action="store_true",
-                    help="vignat, vigfw, vigbridge, vigpol: a flow expires about every 16 "
-                         "packets (vigpol: --rate 1000000000 --burst 4000 x flows)")
+                    help="a flow expires about every 16 packets (vigpol: --rate 1000000000 "
+                         "--burst 4000 x flows; viglb: a backend falls silent in turn as well)")
     ap.add_argument("--tree", default=ROOT)
     ap.add_argument("--label", default="")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     n = a.flows + a.packets
     if a.churn and a.nf == "lb":
-        ap.error("--churn: not for viglb")
-    if a.churn:
+        fr, ln, dv, now = lb_churn_trace(n, a.flows)
+        steady = None  # (a backend's device, or a heartbeat's own: 0 or 1, never the WAN's)
+        print(json.dumps(dict(lb_churn_oracle(fr, ln, dv, now, a.flows), nf="lb",
+                              packets=a.packets, flows=a.flows)), flush=True)
+    elif a.churn:
         fr, ln, dv, now = churn_trace(n, a.flows, a.nf)
         steady = churn_port(a.nf, n)
     else:

@@ -415,21 +415,23 @@ struct ServeBox {
 constexpr uint32_t kServeBurst = 64;       // frames per burst request
 constexpr uint32_t kServeBurstOp = 0xFFFFu;  // message word 0, low half: a burst
 constexpr uint32_t kBurstServed = 0, kBurstDeclined = 1;  // answer chunk 0, word 0
-// With the touch journal on (all but viglb) a burst's answer chunk 0 is
+// With the touch journal on a burst's answer chunk 0 is
 // {status, k, expired, request number}: k packets were served (the rest is
 // posted again: an expiry falls due at packet k), `expired` entries left
-// before them. kBurstFull: the journal has no room for the request's touches
+// before them (viglb: on its two tables together). kBurstFull: the journal has no room for the request's touches
 // and nothing was done (the host seeds it again); kBurstTombs, or-ed into a
-// served status: the table passed the purge bound (the host runs
-// tbl_check_tombs before the next request). A one-packet result carries the
+// served status, or into viglb's kBurstDeclined behind a walk: a table passed
+// the purge bound (the host runs tbl_check_tombs before the next request). A one-packet result carries the
 // same as kOneFull / kOneTombs, the expired count in answer chunk 0's word 1.
 constexpr uint32_t kBurstFull = 2, kBurstTombs = 0x100;
 constexpr uint32_t kOneFull = 1u << 20, kOneTombs = 1u << 21;
 // Beside `fresh` (bit 16) in a burst's out word and in a one-packet result:
 // an entry of the NF's second table was allocated (viglb: a backend).
 constexpr uint32_t kOneFresh2 = 1u << 18;
-// A one-packet result: the request was declined with nothing written (viglb's
-// erasure of a flow, vp_lb.hip); the caller takes the batch path.
+// A one-packet result: the request was declined and its packet wrote nothing
+// (viglb's erasure of a flow, vp_lb.hip); the caller takes the batch path.
+// With the journals on the walks in front of it are done, and the answer
+// carries their count and kOneTombs as a served one's does.
 constexpr uint32_t kOneDeclined = 1u << 19;
 static_assert(sizeof(((ServeBox *)nullptr)->bframe) == kServeBurst * kServeFrame, "burst slots");
 // The request chunks of a message m (3 words per chunk, `need` chunks) as
@@ -486,13 +488,13 @@ struct ServeNf {
   uint32_t burst_in, burst_back;  // a burst's frame: the most bytes in, and back
   uint32_t burst_route;           // the largest host batch routed as burst requests
   bool prof;                      // VIGPATH_SERVE_PROF's stage clock (nat_serve's)
-  // a second expiring table (viglb's backends), null for the others: a
-  // request is sent only while no expiry is due on it either, and kOneFresh2
-  // lowers its floor
+  // a second expiring table (viglb's backends), null for the others: with the
+  // journals off a request is sent only while no expiry is due on it either,
+  // kOneFresh2 lowers its floor, and it has a journal of its own
   int64_t (*cutoff2)(const vp_ctx *c, int64_t t) = nullptr;
   FlowTable vp_ctx::*table2 = nullptr;
-  // the resident kernel expires entries itself from a touch journal once the
-  // context has met a due expiry (all but viglb; serve_journal_ok)
+  // the resident kernel expires entries itself from a touch journal (one per
+  // expiring table) once the context has met a due expiry (serve_journal_ok)
   bool journal = false;
 };
 const ServeNf &nat_serve_nf();
@@ -534,9 +536,10 @@ void serve_free(vp_ctx *c);
 // saw the request). The caller holds c->srv_mu.
 int serve_ready(vp_ctx *c);
 int serve_wait(vp_ctx *c, uint32_t req, uint32_t need);
-// The journal's launch arguments for c's table (off: ctl == null).
+// The journal's launch arguments for c's table, or for its second one (off:
+// ctl == null), E from that table's own cutoff.
 struct JournalDev;
-JournalDev serve_journal_dev(const vp_ctx *c, const ServeNf &nf);
+JournalDev serve_journal_dev(const vp_ctx *c, const ServeNf &nf, bool second = false);
 bool serve_off();   // VIGPATH_SERVE=0
 bool serve_prof();  // VIGPATH_SERVE_PROF (vignat's stage clock)
 // The largest host batch routed as burst requests: VIGPATH_SERVE_BURST, else

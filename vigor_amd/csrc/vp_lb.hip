@@ -591,16 +591,24 @@ __global__ void lb_hb_finish(LbArgs a, const uint32_t *list, uint32_t n,
 // vp_process_mbufs calls go to lb_serve, one wave that stays resident and
 // polls the host-coherent mailbox (ServeBox, vp_internal.h), as nat_serve,
 // fw_serve, bridge_serve and pol_serve do for their NFs: no launch and no
-// copy call per packet. The host sends requests only while no expiry is due
-// on the flow table or on the backend table (serve_process_one /
-// serve_process_burst), so the kernel restates lb_main.c:20-68 and
-// lb_balancer.c:38-143 without lb_expire_flows / lb_expire_backends.
+// copy call per packet. The kernel restates lb_main.c:20-68 and
+// lb_balancer.c:38-143. Until the context has met a due expiry the host sends
+// requests only while none is due on the flow table or on the backend table
+// (serve_process_one / serve_process_burst) and the instance without the
+// journal runs; from then on the instance with it runs lb_expire_flows and
+// lb_expire_backends itself, from one touch journal per table (serve_expire,
+// vp_serve_dev.h), at the top of every packet as lb_main.c:21-22 does -- before
+// the parse, so a frame that is no TCP or UDP packet over IPv4 expires too.
+// A backend the walk has freed is gone for the lookups behind it: they test
+// slot_of, which the walk sets to kNone (cht_choose, lb_one, lb_burst).
 //
 // One case is left to the batch pipeline: a WAN packet whose flow points at a
 // dead backend while no backend is alive erases the flow and frees its index
-// (lb_stale_free_seq). The host's control mirror and its tombstone check
-// (tbl_check_tombs) do not see what a resident kernel does, so lb_serve never
-// erases: it declines such a request before it has written anything.
+// (lb_stale_free_seq). lb_serve never erases: it declines such a request
+// before the packet itself has written anything. The walk in front of it may
+// have expired entries (it can be what took the last backend), which the
+// answer still reports; the pipeline's own expiry at that packet then finds
+// nothing left due.
 
 // lb_one's answers that are no backend index.
 constexpr uint32_t kLbPass = 0xFFFFFFFEu;     // out = in, the frame as it came
@@ -661,16 +669,20 @@ __device__ __forceinline__ void lb_flow_repoint(const LbArgs &a, uint32_t fi, ui
 
 // lb_process in packet order for one parsed TCP/UDP packet: the backend whose
 // record rewrites it, kLbPass or kLbDecline. *fresh: bit 0 a flow was
-// allocated, bit 1 a backend. T: the 17 CRC tables.
+// allocated, bit 1 a backend. *tf, *tb: the flow and the backend index it
+// stamped (the journals' touches; a packet stamps one of them or neither).
+// T: the 17 CRC tables.
 __device__ __forceinline__ uint32_t lb_one(const LbArgs &a, const uint32_t *T, uint32_t in,
                                            uint32_t sip, uint32_t dip, uint32_t sp, uint32_t dp,
                                            uint32_t proto, uint32_t m0, uint32_t m1, int64_t now,
-                                           uint64_t seq, uint32_t *fresh) {
+                                           uint64_t seq, uint32_t *fresh, uint32_t *tf,
+                                           uint32_t *tb) {
   if (in != a.wan) {  // a heartbeat
     uint32_t born = 0;
     const uint32_t bi =
         lb_backend_seen(a, ip_hash(T + kLbFlowTabs * 256, sip), sip, m0, m1, in, seq, &born);
     if (bi != kNone) serve_stamp(a.bt, bi, now, seq);
+    *tb = bi;
     *fresh |= born << 1;
     return kLbPass;
   }
@@ -681,10 +693,11 @@ __device__ __forceinline__ uint32_t lb_one(const LbArgs &a, const uint32_t *T, u
     uint32_t bi = w3 >> 8;
     if (a.bt.slot_of[bi] == kNone) {  // its backend is gone
       bi = cht_choose(a, h);
-      if (bi == kNone) return kLbDecline;  // (nothing written so far)
+      if (bi == kNone) return kLbDecline;  // (the packet has written nothing so far)
       lb_flow_repoint(a, fi, proto, bi);
     }
     serve_stamp(a.ft, fi, now, seq);
+    *tf = fi;
     return bi;
   }
   const uint32_t c = cht_choose(a, h);
@@ -692,6 +705,7 @@ __device__ __forceinline__ uint32_t lb_one(const LbArgs &a, const uint32_t *T, u
   uint32_t born = 0;
   const uint32_t idx = lb_flow_new(a, h, sip, dip, sp | (dp << 16), proto, c, seq, &born);
   if (idx != kNone) serve_stamp(a.ft, idx, now, seq);
+  *tf = idx;
   *fresh |= born;
   return c;  // (also when no index was free, lb_balancer.c:66)
 }
@@ -713,22 +727,43 @@ __device__ __forceinline__ uint32_t lb_one(const LbArgs &a, const uint32_t *T, u
 // then takes for the flow's live backend: a plain hit) or the flow re-pointed
 // by an earlier S. As many rounds as pending lanes; steady traffic has none.
 // The erasure (S with no backend alive) declines the burst: when round 0
-// finds an S lane and the backend table's n_live is 0 at the burst's start.
+// finds an S lane and the backend table's n_live is 0 behind the walks.
 // Conservative (an earlier H of the burst might have revived a backend) but
-// exact, since the pipeline then gets the burst whole; with n_live above 0 at
-// the start it stays so, and no S lane can find cht_choose empty later.
+// exact, since the pipeline then gets the burst whole; with n_live above 0
+// there it stays so (nothing expires among the served lanes), and no S lane
+// can find cht_choose empty later.
+// With the journals on (J; jf / fs the flows', jb / bs the backends'), behind
+// the IPv4-options decline, which still writes nothing: both journals need
+// room or the answer is kBurstFull with nothing done; then both walks at the
+// first packet's time and the cut (burst_split2) -- *k <= n packets are served,
+// round 0, the settle loop, the stamps and the rewrite run over those lanes
+// only, and the winners of the two stamp passes are the journals' touches. A
+// backend the walk has freed is dead for round 0 (slot_of), so its flows are
+// S lanes; the erasure's decline comes behind the walk, which may be what
+// took n_live to 0, and the caller reports what the walk did with it.
+template <bool J>
 __device__ __forceinline__ uint32_t lb_burst(const LbArgs &a, const uint32_t *T, ServeBox *box,
-                                             uint32_t n, uint64_t seq0, uint32_t lane) {
+                                             uint32_t n, uint64_t seq0, uint32_t lane,
+                                             const JournalDev &jf, JournalSt &fs,
+                                             const JournalDev &jb, JournalSt &bs, uint32_t *k) {
   BurstIn b = burst_load(box, n, lane);
   const BurstHdr h = burst_hdr(b);
   if (h.decline) return kBurstDeclined;
+  int64_t now0 = 0;
+  bool go = h.go;
+  if (J) {
+    n = burst_split2(a.ft, jf, fs, a.bt, jb, bs, b, n, lane, &now0);
+    if (!n) return kBurstFull;
+    go = go && lane < n;
+  }
+  *k = n;
   RFrame &f = b.f;
   const uint32_t in = b.in;
   // the L4 checksum's bytes past 64, [64, min(14 + total_length, len)), summed
   // straight from the mailbox (as nat_serve's burst)
   uint32_t tail = 0;
   {
-    const uint32_t end = h.go && in == a.wan ? min(14 + h.tl, b.len) : 0u;
+    const uint32_t end = go && in == a.wan ? min(14 + h.tl, b.len) : 0u;
     for (uint32_t base = 64; __ballot(base < end); base += 128) {
       v4u x[8];
 #pragma unroll
@@ -746,7 +781,7 @@ __device__ __forceinline__ uint32_t lb_burst(const LbArgs &a, const uint32_t *T,
       }
     }
   }
-  const bool hbp = h.go && in != a.wan, wanp = h.go && in == a.wan;
+  const bool hbp = go && in != a.wan, wanp = go && in == a.wan;
   const uint32_t ports = h.sp | (h.dp << 16);
   const uint32_t hf = lbflow_hash_batched(T, h.sip, h.dip, h.sp, h.dp, h.proto);
   const uint32_t hi = ip_hash(T + kLbFlowTabs * 256, h.sip);
@@ -794,8 +829,13 @@ __device__ __forceinline__ uint32_t lb_burst(const LbArgs &a, const uint32_t *T,
   // packet that went to a backend stamps its flow if it has one (a miss that
   // found no index free has none), a heartbeat its backend.
   if (be == kNone) fi = kNone;
-  if (burst_last(fi, n, lane)) serve_stamp(a.ft, fi, b.now, seq0 + lane);
-  if (burst_last(bi, n, lane)) serve_stamp(a.bt, bi, b.now, seq0 + lane);
+  const bool fwon = burst_last(fi, n, lane), bwon = burst_last(bi, n, lane);
+  if (fwon) serve_stamp(a.ft, fi, b.now, seq0 + lane);
+  if (bwon) serve_stamp(a.bt, bi, b.now, seq0 + lane);
+  if (J) {
+    journal_touch_burst(jf, fs, fwon, fi, seq0 + lane, now0, lane);
+    journal_touch_burst(jb, bs, bwon, bi, seq0 + lane, now0, lane);
+  }
   // the rewrite, each lane its own frame; back go a rewritten frame's first 64
   // bytes (a rewrite touches nothing past byte 51)
   uint32_t out = in, rew = 0;
@@ -818,13 +858,22 @@ __device__ __forceinline__ uint32_t lb_burst(const LbArgs &a, const uint32_t *T,
 // sums the L4 bytes past byte 64, lane 0 runs the packet (in registers when
 // IHL = 5, byte-addressed over the LDS copy otherwise), the frame goes back
 // and the answer follows: out | flow allocated << 16 | backend allocated << 18,
-// or kOneDeclined with nothing written (the erasure). Packets take global
-// sequence numbers seq0, seq0 + 1, ...; a burst request (lb_burst) takes as
-// many as it has frames, a declined request none. The kernel leaves on the
-// leave request or after `idle` wall-clock ticks without a request; the host
-// launches it again (serve_wait). flags: serve_poll's.
+// or kOneDeclined when the packet is the erasure and has written nothing.
+// Packets take global sequence numbers seq0, seq0 + 1, ...; a burst request
+// (lb_burst) takes as many as it serves, a declined request none. The kernel
+// leaves on the leave request or after `idle` wall-clock ticks without a
+// request; the host launches it again (serve_wait). flags: serve_poll's.
+// J: the kernel expires from the touch journals jf (flows, a.ft) and jb
+// (backends, a.bt), whose control words it keeps in registers (fs, bs) and
+// stores back after every request; the whole wave walks both before lane 0
+// parses, and the answer carries the two walks' count (their sum) and
+// kOneTombs / kBurstTombs when either table passed its purge bound -- also
+// beside kOneDeclined / kBurstDeclined, whose walk is done all the same. A
+// context whose journals are off runs the instance without any of it.
+template <bool J>
 __global__ __launch_bounds__(64) void lb_serve(LbArgs a, ServeBox *box, uint64_t seq0,
-                                               uint64_t idle, uint32_t flags) {
+                                               uint64_t idle, uint32_t flags, JournalDev jf,
+                                               JournalDev jb) {
   __shared__ uint32_t T[kLbTabs * 256];
   __shared__ uint4 fr[kServeFrame / 16];
   const uint32_t lane = threadIdx.x;
@@ -838,17 +887,27 @@ __global__ __launch_bounds__(64) void lb_serve(LbArgs a, ServeBox *box, uint64_t
       &box->ans, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM));
   uint64_t seq = seq0;
   uint64_t t0 = wall_clock64();
+  // the touch journals' control words
+  JournalSt fs = journal_load(J ? jf : JournalDev{});
+  JournalSt bs = journal_load(J ? jb : JournalDev{});
   auto serve = [&](const v4u &c) -> int {
     const uint32_t want = done + 1;
     if (__builtin_amdgcn_readfirstlane(c[3]) != want) return -1;
     const uint32_t hi = __builtin_amdgcn_readfirstlane(c[0]);
     if (hi == kServeLeave) return 1;
     const uint32_t in = hi >> 16;
+    fs.expired = 0, fs.flags = 0;
+    bs.expired = 0, bs.flags = 0;
     if ((hi & 0xFFFFu) == kServeBurstOp) {  // chunk 0 alone, the frames in the burst body
-      const uint32_t bn = min(max(in, 1u), kServeBurst);
-      const uint32_t st = lb_burst(a, T, box, bn, seq, lane);
-      if (lane == 0) burst_answer(io, box, st, bn, want);
-      if (st == kBurstServed) seq += bn;
+      uint32_t bn = min(max(in, 1u), kServeBurst);
+      uint32_t st = lb_burst<J>(a, T, box, bn, seq, lane, jf, fs, jb, bs, &bn);
+      if (J && st != kBurstFull) {  // (a declined burst's walk counts too)
+        if (fs.flags | bs.flags) st |= kBurstTombs;
+        journal_store(jf, fs, lane);
+        journal_store(jb, bs, lane);
+      }
+      if (lane == 0) burst_answer(io, box, st, bn, want, fs.expired + bs.expired);
+      if ((st & 0xFFu) == kBurstServed) seq += bn;
       t0 = wall_clock64();
       done = want;
       // (every lane's table writes before the next request reads them)
@@ -885,8 +944,15 @@ __global__ __launch_bounds__(64) void lb_serve(LbArgs a, ServeBox *box, uint64_t
         tail = sum16x4(chunk_keep(fr[cc / 16], 0, (int)end - (int)cc), tail);
       for (int o = 32; o > 0; o >>= 1) tail += __shfl_xor(tail, o);
     }
-    uint32_t res = 0;
-    if (lane == 0) {
+    // lb_main.c:21-22: both expiries before the parse, whatever the frame is
+    const bool full = J && !(journal_room(jf, fs, 1) && journal_room(jb, bs, 1));
+    if (J && !full) {
+      serve_expire(a.ft, jf, fs, journal_cutoff(jf, now), lane);
+      serve_expire(a.bt, jb, bs, journal_cutoff(jb, now), lane);
+    }
+    uint32_t res = 0, tf = kNone, tb = kNone;
+    if (full) res = kOneFull;  // (nothing is done: seeded again)
+    if (lane == 0 && !full) {
       uint32_t fresh = 0, out = in, be = kLbPass;
       RFrame f = serve_rframe([&](int j) { return fr[j]; }, len);
       const uint32_t et = f.w[3] & 0xFFFF, ihl = (f.w[3] >> 16) & 0x0F;
@@ -897,7 +963,7 @@ __global__ __launch_bounds__(64) void lb_serve(LbArgs a, ServeBox *box, uint64_t
         if ((unread >= 20) & (unread >= tl) & ((proto == 6) | (proto == 17)) &
             ((uint32_t)(len - 34) >= 4u)) {
           be = lb_one(a, T, in, f.u32at2(26), f.u32at2(30), f.w[8] >> 16, f.w[9] & 0xFFFF, proto,
-                      f.u32at2(6), f.w[2] >> 16, now, seq, &fresh);
+                      f.u32at2(6), f.w[2] >> 16, now, seq, &fresh, &tf, &tb);
           if (be < kLbDecline) {
             uint32_t rew = 0;
             out = lb_serve_rewrite(a, f, a.be_rec[be], proto, tl, tail, &rew);
@@ -913,7 +979,7 @@ __global__ __launch_bounds__(64) void lb_serve(LbArgs a, ServeBox *box, uint64_t
         const L34 l = parse_l34(g, len);
         if (l.ok) {
           be = lb_one(a, T, in, g.r32(l.ip + 12), g.r32(l.ip + 16), g.r16(l.l4), g.r16(l.l4 + 2),
-                      g.r8(l.ip + 9), g.r32(6), g.r16(10), now, seq, &fresh);
+                      g.r8(l.ip + 9), g.r32(6), g.r16(10), now, seq, &fresh, &tf, &tb);
           if (be < kLbDecline) {
             const uint4 rec = a.be_rec[be];
             out = rec.z >> 16;
@@ -932,9 +998,18 @@ __global__ __launch_bounds__(64) void lb_serve(LbArgs a, ServeBox *box, uint64_t
     }
     wave_lds_sync();
     res = __builtin_amdgcn_readfirstlane(res);
+    uint32_t expired = 0;
+    if (J && !full) {
+      res |= fs.flags | bs.flags;
+      expired = fs.expired + bs.expired;
+      journal_touch(jf, fs, __builtin_amdgcn_readfirstlane(tf), seq, now, lane);
+      journal_touch(jb, bs, __builtin_amdgcn_readfirstlane(tb), seq, now, lane);
+      journal_store(jf, fs, lane);
+      journal_store(jb, bs, lane);
+    }
     if (inl) {  // the answer chunks: the result and the frame in one store
       if (lane < need) {
-        const v4u v = lane == 0 ? (v4u){res, 0u, 0u, want}
+        const v4u v = lane == 0 ? (v4u){res, expired, 0u, want}
                                 : (v4u){fw[3 * lane - 3], fw[3 * lane - 2], fw[3 * lane - 1], want};
         __builtin_amdgcn_raw_buffer_store_b128(v, io.as, (int)(16 * lane), 0, kSys);
       }
@@ -949,7 +1024,7 @@ __global__ __launch_bounds__(64) void lb_serve(LbArgs a, ServeBox *box, uint64_t
       __builtin_amdgcn_s_waitcnt(0);
       __atomic_signal_fence(__ATOMIC_SEQ_CST);
       if (lane == 0)
-        __builtin_amdgcn_raw_buffer_store_b128((v4u){res, 0u, 0u, want}, io.as, 0, 0, kSys);
+        __builtin_amdgcn_raw_buffer_store_b128((v4u){res, expired, 0u, want}, io.as, 0, 0, kSys);
     }
     if (lane == 0) {
       // (the answer word: where a relaunched server starts counting; the host
@@ -958,7 +1033,7 @@ __global__ __launch_bounds__(64) void lb_serve(LbArgs a, ServeBox *box, uint64_t
       __hip_atomic_store(&box->ans, (uint64_t)want | ((uint64_t)res << 32), __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    if (!(res & kOneDeclined)) seq += 1;
+    if (!(res & (kOneDeclined | kOneFull))) seq += 1;
     t0 = wall_clock64();
     done = want;
     // (lane 0's table writes before the next request's lanes read them)
@@ -1255,7 +1330,9 @@ int lb_process_device(vp_ctx *c, const vp_dev_batch *b) {
 // ---------------------------------------------------- vp_process_one --
 // viglb's launcher of the resident kernel (serve_launch, vp_serve.hip): of
 // LbArgs what lb_serve reads -- both tables, the backend records, the CHT, the
-// CRC tables and the devices' MACs; the batch's fields stay empty.
+// CRC tables and the devices' MACs; the batch's fields stay empty. The
+// instance with the journals runs once both tables' are seeded (serve_ready
+// seeds them together).
 int lb_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
   LbArgs a{};
   a.ft = tbl_dev(c->ft);
@@ -1268,7 +1345,13 @@ int lb_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
   a.dmacw = c->dmacw;
   a.wan = c->lb.wan_device;
   a.n_dev = c->lb.n_devices;
-  lb_serve<<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags);
+  const JournalDev jf = serve_journal_dev(c, lb_serve_nf()),
+                   jb = serve_journal_dev(c, lb_serve_nf(), true);
+  if (jf.ctl && jb.ctl)
+    lb_serve<true><<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags, jf, jb);
+  else
+    lb_serve<false><<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags, JournalDev{},
+                                             JournalDev{});
   VP_HIP(hipGetLastError());
   return 0;
 }
@@ -1289,12 +1372,12 @@ constexpr uint32_t kLbBurstRoute = 128;
 // and 24-25, 30-33, 40-41 or 50-51, and the L4 checksum is recomputed over
 // [34, 14 + total_length), so the whole frame goes, one longer than
 // kServeInline through `frame`, and a burst's frame comes back in its first 64
-// bytes. Two expiring tables: requests go only while no expiry is due on the
-// flows or on the backends. No stage clock.
+// bytes. Two expiring tables, each with its own lifetime and its own touch
+// journal: the kernel expires both. No stage clock.
 const ServeNf &lb_serve_nf() {
   static const ServeNf nf = {lb_flow_cutoff, &vp_ctx::ft,   true,          kServeInline,
                              kServeInline,   kServeFrame,   64,            kLbBurstRoute,
-                             false,          lb_backend_cutoff, &vp_ctx::ft2};
+                             false,          lb_backend_cutoff, &vp_ctx::ft2, true};
   return nf;
 }
 

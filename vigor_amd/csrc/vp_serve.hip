@@ -180,17 +180,23 @@ uint32_t serve_burst_limit(uint32_t dflt) {  // VIGPATH_SERVE_BURST
 
 // ------------------------------------------------------ the touch journal --
 // Expiry inside the resident kernel (vp_serve_dev.h). The
-// expiry time E of the NF's cutoff, cutoff(t) = t - E in u64 arithmetic
+// expiry time E of a table's cutoff, cutoff(t) = t - E in u64 arithmetic
 // (vignat's and vigbridge's 32-bit wrap inside it, vigpol's 64-bit
-// burst * 1e9 / rate).
-static uint64_t serve_expire_e(const vp_ctx *c, const ServeNf &nf) {
-  return (uint64_t)0 - (uint64_t)nf.cutoff(c, 0);
+// burst * 1e9 / rate, viglb's two 64-bit lifetimes). An NF with a second
+// expiring table (viglb: table2 / cutoff2) has a journal per table; the two
+// are seeded, dropped and seeded again together.
+typedef int64_t (*CutoffFn)(const vp_ctx *c, int64_t t);
+static uint64_t serve_expire_e(const vp_ctx *c, CutoffFn cutoff) {
+  return (uint64_t)0 - (uint64_t)cutoff(c, 0);
+}
+static bool serve_jr_on(const vp_ctx *c, const ServeNf &nf) {
+  return (c->*nf.table).jr_on && (!nf.table2 || (c->*nf.table2).jr_on);
 }
 
-// Whether c's kernel may expire: the NF has the walk (all but viglb),
+// Whether c's kernel may expire: the NF has the walk,
 // VIGPATH_SERVE_EXPIRE is not 0, vignat polls with one wave (the journal's
-// control words live in that wave's registers), and E is not negative (a
-// packet would then expire the flow it has just touched).
+// control words live in that wave's registers), and no table's E is negative
+// (a packet would then expire the entry it has just touched).
 static bool serve_journal_ok(const vp_ctx *c, const ServeNf &nf) {
   static const bool off = [] {
     const char *e = getenv("VIGPATH_SERVE_EXPIRE");
@@ -202,13 +208,15 @@ static bool serve_journal_ok(const vp_ctx *c, const ServeNf &nf) {
     return v == 2 || v == 4;
   }();
   return nf.journal && !off && !(waves && c->kind == KIND_NAT) &&
-         (int64_t)serve_expire_e(c, nf) >= 0;
+         (int64_t)serve_expire_e(c, nf.cutoff) >= 0 &&
+         (!nf.table2 || (int64_t)serve_expire_e(c, nf.cutoff2) >= 0);
 }
 
-JournalDev serve_journal_dev(const vp_ctx *c, const ServeNf &nf) {
-  const FlowTable &t = c->*nf.table;
+JournalDev serve_journal_dev(const vp_ctx *c, const ServeNf &nf, bool second) {
+  const FlowTable &t = c->*(second ? nf.table2 : nf.table);
   if (!t.jr_on) return JournalDev{};
-  return JournalDev{t.jr, t.jrec, t.jr_n, tbl_purge_bound(t), serve_expire_e(c, nf)};
+  return JournalDev{t.jr, t.jrec, t.jr_n, tbl_purge_bound(t),
+                    serve_expire_e(c, second ? nf.cutoff2 : nf.cutoff)};
 }
 
 // A request found an expiry due while the journal was off: it takes the
@@ -220,11 +228,12 @@ static void serve_handed(vp_ctx *c, const ServeNf &nf) {
 }
 
 // What a journal request's answer says beside its results: `expired` entries
-// left in its walk; kOneTombs / kBurstTombs (tombs): the table passed the
-// purge bound, so the kernel stops for the pipeline's own check and is
-// launched again by the next request. The journal stays: a rebuild moves
-// entries, not stamps.
-static int serve_expired(vp_ctx *c, FlowTable &t, uint32_t expired, bool tombs) {
+// left in its walk (viglb: in its two walks); kOneTombs / kBurstTombs (tombs):
+// a table passed the purge bound, so the kernel stops for the pipeline's own
+// check -- of both tables when there are two: the check reads the control block
+// back first and is cheap -- and is launched again by the next request. The
+// journal stays: a rebuild moves entries, not stamps.
+static int serve_expired(vp_ctx *c, const ServeNf &nf, uint32_t expired, bool tombs) {
   if (expired) {
     c->srv_exp.expired += expired;
     c->srv_exp.walks += 1;
@@ -232,14 +241,16 @@ static int serve_expired(vp_ctx *c, FlowTable &t, uint32_t expired, bool tombs) 
   if (!tombs) return 0;
   VP_TRY(serve_stop(c));
   VP_HIP(hipSetDevice(c->gpu));
-  return tbl_check_tombs(c, t);
+  VP_TRY(tbl_check_tombs(c, c->*nf.table));
+  return nf.table2 ? tbl_check_tombs(c, c->*nf.table2) : 0;
 }
 
-// The ring is full: stop, and the launch that follows seeds it again from the
-// table, on all CUs -- the journal's compaction.
-static int serve_reseed(vp_ctx *c, FlowTable &t) {
+// A ring is full: stop, and the launch that follows seeds it again from the
+// table, on all CUs -- the journal's compaction (viglb: of both rings).
+static int serve_reseed(vp_ctx *c, const ServeNf &nf) {
   VP_TRY(serve_stop(c));
-  t.jr_on = false;
+  (c->*nf.table).jr_on = false;
+  if (nf.table2) (c->*nf.table2).jr_on = false;
   c->jr_want = true;
   return serve_ready(c);
 }
@@ -272,11 +283,11 @@ int serve_ready(vp_ctx *c) {
     // kernel expires itself, from a journal of the table as it is now
     if (c->jr_want) {
       const ServeNf *nf = serve_nf(c->kind);
-      FlowTable &t = c->*nf->table;
       c->jr_want = false;
-      if (!t.jr_on) {
-        VP_TRY(tbl_journal_seed(c, t));
-        c->srv_exp.seeds += 1;
+      for (FlowTable vp_ctx::*m : {nf->table, nf->table2}) {
+        if (!m || (c->*m).jr_on) continue;
+        VP_TRY(tbl_journal_seed(c, c->*m));
+        c->srv_exp.seeds += 1;  // (tables seeded: viglb's two count 2)
       }
     }
     // the batch path may leave a timestamp fold running: the server is
@@ -355,8 +366,8 @@ int serve_process_one(vp_ctx *c, const ServeNf &nf, uint16_t in_dev, uint8_t *fr
   const bool due = nf.cutoff(c, now) > (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)now) ||
                    (t2 && nf.cutoff2(c, now) >
                               (int64_t)std::min<uint64_t>(t2->ts_floor, (uint64_t)now));
-  if (due && !t.jr_on) VP_TRY(serve_seed_now(c));  // (after a bounce: seeded, then served)
-  if (due && !t.jr_on) {
+  if (due && !serve_jr_on(c, nf)) VP_TRY(serve_seed_now(c));  // (after a bounce: seeded, then served)
+  if (due && !serve_jr_on(c, nf)) {
     serve_handed(c, nf);
     VP_TRY(serve_stop(c));
     return 1;
@@ -389,10 +400,15 @@ int serve_process_one(vp_ctx *c, const ServeNf &nf, uint16_t in_dev, uint8_t *fr
     // the journal's ring is full and nothing was done: seeded again, then
     // the same packet once more (it fits: at most cap records of >= 2 cap)
     if (attempt) return state_fail("journal full right after a seed");
-    VP_TRY(serve_reseed(c, t));
+    VP_TRY(serve_reseed(c, nf));
   }
-  if (res & kOneDeclined) {  // nothing of it was done: the batch path, as an ineligible one
+  const bool jr = serve_jr_on(c, nf);
+  if (res & kOneDeclined) {
+    // the packet itself wrote nothing: the batch path, as an ineligible one
+    // (the walk in front of it is done and counted; the pipeline's own expiry
+    // at this packet finds nothing left due)
     c->srv_stats.declined += 1;
+    if (jr) VP_TRY(serve_expired(c, nf, bx->amsg[0][1], (res & kOneTombs) != 0));
     VP_TRY(serve_stop(c));
     return 1;
   }
@@ -407,7 +423,7 @@ int serve_process_one(vp_ctx *c, const ServeNf &nf, uint16_t in_dev, uint8_t *fr
   c->last_now = now;
   c->srv_stats.packets_one += 1;
   if (prof) serve_prof_add(c, h0);
-  if (t.jr_on) VP_TRY(serve_expired(c, t, bx->amsg[0][1], (res & kOneTombs) != 0));
+  if (jr) VP_TRY(serve_expired(c, nf, bx->amsg[0][1], (res & kOneTombs) != 0));
   return 0;
 }
 
@@ -439,8 +455,8 @@ int serve_process_burst(vp_ctx *c, const ServeNf &nf, const vp_mbuf_batch *b, ui
   const bool due =
       nf.cutoff(c, n1) > (int64_t)std::min<uint64_t>(t.ts_floor, (uint64_t)n0) ||
       (t2 && nf.cutoff2(c, n1) > (int64_t)std::min<uint64_t>(t2->ts_floor, (uint64_t)n0));
-  if (due && !t.jr_on) VP_TRY(serve_seed_now(c));  // (after a bounce: seeded, then served)
-  if (due && !t.jr_on) {
+  if (due && !serve_jr_on(c, nf)) VP_TRY(serve_seed_now(c));  // (after a bounce: seeded, then served)
+  if (due && !serve_jr_on(c, nf)) {
     serve_handed(c, nf);
     return 1;
   }
@@ -462,20 +478,24 @@ int serve_process_burst(vp_ctx *c, const ServeNf &nf, const vp_mbuf_batch *b, ui
     serve_post(bx, op, 1, req);
     VP_TRY(serve_wait(c, req, 1));
     const uint32_t st = bx->amsg[0][0];
-    if (st == kBurstFull && t.jr_on) {  // nothing of it was done: seeded again, once more
+    const bool jr = serve_jr_on(c, nf);
+    if (st == kBurstFull && jr) {  // nothing of it was done: seeded again, once more
       if (reseeds++) return state_fail("journal full right after a seed");
-      VP_TRY(serve_reseed(c, t));
+      VP_TRY(serve_reseed(c, nf));
       continue;
     }
-    if ((st & 0xFFu) != kBurstServed) {  // a byte-path frame: nothing of it was done
+    if ((st & 0xFFu) != kBurstServed) {
+      // a byte-path frame, or viglb's erasure: none of its packets was done (a
+      // walk in front of the erasure is, and is counted)
       c->srv_stats.declined += 1;
+      if (jr) VP_TRY(serve_expired(c, nf, bx->amsg[0][2], (st & kBurstTombs) != 0));
       return 1;
     }
     reseeds = 0;
     // the packets served: all of them, or with the journal on those before
     // the one at which an expiry falls due (the rest is the next request)
     const uint32_t asked = m;
-    if (t.jr_on) m = std::min(std::max(bx->amsg[0][1], 1u), m);
+    if (jr) m = std::min(std::max(bx->amsg[0][1], 1u), m);
     bool fresh = false, fresh2 = false;
     for (uint32_t i = 0; i < m; i++) {
       const uint32_t p = first + a0 + i, r = bx->bout[i];
@@ -493,9 +513,9 @@ int serve_process_burst(vp_ctx *c, const ServeNf &nf, const vp_mbuf_batch *b, ui
     c->srv_stats.bursts += 1;
     c->srv_stats.burst_packets += m;
     *served += m;
-    if (t.jr_on) {
+    if (jr) {
       if (m < asked) c->srv_exp.splits += 1;
-      VP_TRY(serve_expired(c, t, bx->amsg[0][2], (st & kBurstTombs) != 0));
+      VP_TRY(serve_expired(c, nf, bx->amsg[0][2], (st & kBurstTombs) != 0));
     }
     a0 += m;
   }

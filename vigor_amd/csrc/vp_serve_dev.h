@@ -75,8 +75,8 @@ __device__ __forceinline__ void serve_stamp(const TableDev &t, uint32_t idx, int
 }
 
 // --------------------------------------------------- the touch journal --
-// Expiry inside the resident kernel (vignat, vigfw, vigbridge, vigpol;
-// JournalDev, vp_table.h).
+// Expiry inside the resident kernel (JournalDev, vp_table.h; viglb keeps
+// two, one per expiring table).
 // The wave keeps the journal's control words in registers (wave-uniform) and
 // stores them back after every request (journal_store), so a kernel launched
 // again after an idle exit or a stop goes on from them (journal_load).
@@ -106,7 +106,7 @@ __device__ __forceinline__ void journal_store(const JournalDev &j, const Journal
   }
 }
 // The cutoff of a packet at `now`: now - E in unsigned 64-bit arithmetic (E
-// from nat_cutoff / fw_cutoff, vignat's 32-bit wrap inside it), compared as
+// from the table's own cutoff, vignat's 32-bit wrap inside it), compared as
 // the pipeline compares it, signed (exp_collect).
 __device__ __forceinline__ int64_t journal_cutoff(const JournalDev &j, int64_t now) {
   return (int64_t)((uint64_t)now - j.expire);
@@ -343,18 +343,47 @@ __device__ __forceinline__ BurstHdr burst_hdr(const BurstIn &b) {
 // (run_batch's test). k >= 1: lane 0's cutoff is at most F after its own walk
 // and at most now_0. Returns k, or 0 when the journal has no room for the
 // burst's touches (at most one record per index, journal_touch_burst):
-// nothing was done.
+// nothing was done. burst_now0: the burst's first time, wave-uniform.
+__device__ __forceinline__ int64_t burst_now0(const BurstIn &b) {
+  const uint64_t u = (uint64_t)b.now;
+  return (int64_t)((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)u) |
+                   ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(u >> 32)) << 32));
+}
+// One table's share of it: the walk at n0, then the lanes above 0 at which
+// this table's next expiry falls due.
+__device__ __forceinline__ uint64_t burst_walk(const TableDev &t, const JournalDev &j,
+                                               JournalSt &s, const BurstIn &b, int64_t n0,
+                                               uint32_t lane) {
+  serve_expire(t, j, s, journal_cutoff(j, n0), lane);
+  const int64_t lim = s.floor < n0 ? s.floor : n0;
+  return __ballot(b.act && lane > 0 && journal_cutoff(j, b.now) > lim);
+}
 __device__ __forceinline__ uint32_t burst_split(const TableDev &t, const JournalDev &j,
                                                 JournalSt &s, const BurstIn &b, uint32_t n,
                                                 uint32_t lane, int64_t *now0) {
   if (!journal_room(j, s, min(n, t.cap))) return 0;
-  const uint64_t u = (uint64_t)b.now;
-  const int64_t n0 = (int64_t)((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)u) |
-                               ((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(u >> 32)) << 32));
+  const int64_t n0 = burst_now0(b);
   *now0 = n0;
-  serve_expire(t, j, s, journal_cutoff(j, n0), lane);
-  const int64_t lim = s.floor < n0 ? s.floor : n0;
-  const uint64_t due = __ballot(b.act && lane > 0 && journal_cutoff(j, b.now) > lim);
+  const uint64_t due = burst_walk(t, j, s, b, n0, lane);
+  return due ? (uint32_t)__ffsll((unsigned long long)due) - 1 : n;
+}
+
+// The same for an NF with two expiring tables whose expiries both precede the
+// parse (viglb: lb_main.c:21-22, flows then backends, each on its own lifetime
+// and journal): room on both journals or nothing is done, both walks at now_0,
+// and k is the first lane above 0 at which either table's next expiry falls
+// due -- every active lane counts, parsed or not. A lane's touches go to one
+// journal or the other, so each needs room for min(n, its cap) records.
+__device__ __forceinline__ uint32_t burst_split2(const TableDev &t1, const JournalDev &j1,
+                                                 JournalSt &s1, const TableDev &t2,
+                                                 const JournalDev &j2, JournalSt &s2,
+                                                 const BurstIn &b, uint32_t n, uint32_t lane,
+                                                 int64_t *now0) {
+  if (!journal_room(j1, s1, min(n, t1.cap)) || !journal_room(j2, s2, min(n, t2.cap))) return 0;
+  const int64_t n0 = burst_now0(b);
+  *now0 = n0;
+  uint64_t due = burst_walk(t1, j1, s1, b, n0, lane);
+  due |= burst_walk(t2, j2, s2, b, n0, lane);
   return due ? (uint32_t)__ffsll((unsigned long long)due) - 1 : n;
 }
 

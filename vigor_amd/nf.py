@@ -300,11 +300,12 @@ class NfBase:
 
     def serve_expiry_stats(self) -> dict:
         """vp_serve_expiry_stats_get: expiry inside the resident kernel
-        (vignat, vigfw, vigbridge, vigpol; all zero for viglb, whose due
-        expiries stay the pipeline's) -- seeds (journal builds),
-        expired (entries the kernel expired), walks (requests that expired at
-        least one), handed (requests that took the pipeline because an expiry
-        was due), splits (bursts served in part, the rest posted again). A
+        (every served NF) -- seeds (journal builds, one per table: a viglb
+        seeding builds the flows' and the backends' and counts 2),
+        expired (entries the kernel expired; viglb: flows and backends
+        together), walks (requests that expired at least one), handed
+        (requests that took the pipeline because an expiry was due, on either
+        table), splits (bursts served in part, the rest posted again). A
         host-side counter read: the kernel stays."""
         st = ServeExpiryStatsC()
         self._ck(self.L.vp_serve_expiry_stats_get(self.h, C.byref(st)),
