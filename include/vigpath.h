@@ -167,6 +167,61 @@ typedef struct vp_dev_batch {
  * completes entirely before the call returns. */
 int vp_process_device(vp_ctx *ctx, const vp_dev_batch *batch, void *stream);
 
+/* ----------------------------------------------------------- transmit --
+ * What nf.c does with nf_process's return value (nf.c:159-174; 201-209 in
+ * the batched loop), for a batch that stays in device memory: per-port lists
+ * of packet indices, built on the GPU from out_dev. The frames stay where
+ * they are and are never read. */
+
+typedef struct vp_tx_stats {
+  uint64_t packets[VP_MAX_DEVICES]; /* entries of port d's list, flood copies included */
+  uint64_t bytes[VP_MAX_DEVICES];   /* sum of len[] over those entries */
+  uint64_t dropped;                 /* out_dev == in port (nf.c:159) */
+  uint64_t flooded;                 /* out_dev == VP_FLOOD_FRAME (packets, not copies) */
+  uint64_t bad_port;                /* anything else >= n_devices: in no list */
+} vp_tx_stats;
+
+typedef struct vp_tx_lists {
+  uint32_t *idx;      /* device, `cap` entries: packet indices, port 0's list first,
+                         then port 1's, ...; inside a list ascending (packet order) */
+  uint32_t cap;
+  uint32_t *offset;   /* device, n_devices + 1 entries: list d = idx[offset[d] .. offset[d+1]) */
+  vp_tx_stats *stats; /* device, or NULL */
+} vp_tx_lists;
+
+/* Build the transmit lists of a device-resident batch (after
+ * vp_process_device filled its out_dev). Reads batch->n, out_dev, in_dev (or
+ * in_port when in_dev is NULL) and len (only with stats; may then not be
+ * NULL), and nothing else of the batch. n_devices is the context's own
+ * (its vp_*_config). Per packet i, in = its input port, out = out_dev[i], in
+ * this order:
+ *   out == in               dropped                              (nf.c:159)
+ *   out == VP_FLOOD_FRAME   i joins the list of every port d < n_devices,
+ *                           d != in (flood(), nf.c:82-96; an in >= n_devices
+ *                           skips no port); counted once in `flooded`
+ *   out < n_devices         i joins list `out`       (rte_eth_tx_burst(out))
+ *   otherwise               counted in bad_port, in no list
+ * Every list is in ascending packet order -- the order of nf.c's tx_burst
+ * calls for that port -- and the result is deterministic: the same input
+ * gives the same bytes. offset[] and *stats are written whole by every call
+ * (never accumulated) and always hold the true counts. When the total
+ * offset[n_devices] exceeds cap, positions at or beyond cap are not written,
+ * positions below it hold what they would with enough room, and the call
+ * still returns 0: the caller sees offset[n_devices] > cap.
+ * The work (three kernel launches) is enqueued on `stream` (a hipStream_t,
+ * or NULL for the context's own stream), ordered after the work already on
+ * that stream, and the call MAY RETURN BEFORE THE LISTS ARE WRITTEN: wait for
+ * the stream before reading them on the host. It makes no host round trip.
+ * Like every call that launches device work on the context, it ends the NF's
+ * resident kernel (vp_process_one): the kernel leaves, and the next small
+ * call launches it again. After a multi-GPU attach the call is local to the
+ * rank: not a collective, and it covers only this rank's slice.
+ * VP_EINVAL: a NULL ctx, batch, lists, out_dev or offset; a NULL idx with
+ * cap > 0; a NULL len with stats; in_dev NULL and in_port > 0xFFFF; n *
+ * max(1, n_devices - 1) beyond 32 bits; a context with more than
+ * VP_MAX_DEVICES devices. n == 0: all offsets 0, stats zero. */
+int vp_tx_build(vp_ctx *ctx, const vp_dev_batch *batch, const vp_tx_lists *lists, void *stream);
+
 /* Host memory the GPU may read and write frames in directly: a DPDK mbuf
  * pool's memory (the hugepages rte_pktmbuf_pool_create, nf.c:235-242, lays
  * the mbufs out in), registered once after the pool is created. Page-locked

@@ -53,6 +53,22 @@ class ServeExpiryStatsC(C.Structure):
                 ("splits", C.c_uint64)]
 
 
+class TxStatsC(C.Structure):
+    """vp_tx_stats (include/vigpath.h)."""
+    _fields_ = [("packets", C.c_uint64 * MAX_DEV), ("bytes", C.c_uint64 * MAX_DEV),
+                ("dropped", C.c_uint64), ("flooded", C.c_uint64),
+                ("bad_port", C.c_uint64)]
+
+
+class TxListsC(C.Structure):
+    """vp_tx_lists (include/vigpath.h): device pointers."""
+    _fields_ = [("idx", C.c_void_p), ("cap", C.c_uint32), ("offset", C.c_void_p),
+                ("stats", C.c_void_p)]
+
+
+# packets per block of vp_tx_build's kernels (vp_tx.hip kTxBlockPackets)
+TX_BLOCK_PACKETS = 2048
+
 MacTable = (C.c_uint8 * 6) * MAX_DEV
 
 
@@ -142,7 +158,7 @@ EXPORTS = ["vp_nat_create", "vp_bridge_create", "vp_lb_create", "vp_fw_create",
            "vp_last_error", "vp_register_host", "vp_unregister_host", "vp_process_mbufs",
            "vp_last_stage_ms", "vp_stage_ms", "vp_comm_abort", "vp_probe_slots",
            "vp_probe_slots_w", "vp_process_one", "vp_last_kernel", "vp_serve_stats_get",
-           "vp_serve_expiry_stats_get"]
+           "vp_serve_expiry_stats_get", "vp_tx_build"]
 
 _libs = {}
 
@@ -243,6 +259,9 @@ def lib(path: str | None = None):
     L.vp_serve_stats_get.restype = C.c_int
     L.vp_serve_expiry_stats_get.argtypes = [C.c_void_p, C.POINTER(ServeExpiryStatsC)]
     L.vp_serve_expiry_stats_get.restype = C.c_int
+    L.vp_tx_build.argtypes = [C.c_void_p, C.POINTER(DevBatchC), C.POINTER(TxListsC),
+                              C.c_void_p]
+    L.vp_tx_build.restype = C.c_int
     L.vp_last_error.argtypes = []
     L.vp_last_error.restype = C.c_char_p
     _libs[path] = L

@@ -98,6 +98,7 @@ hipError_t preload_fw(hipStream_t s);
 hipError_t preload_pol(hipStream_t s);
 hipError_t preload_comm(hipStream_t s);
 hipError_t preload_mbuf(hipStream_t s);
+hipError_t preload_tx(hipStream_t s);
 
 // Owner-mode phase A stages (vp_last_stage_ms).
 constexpr int kStages = 8;
@@ -238,6 +239,13 @@ struct Workspace {
   uint32_t *pairs = nullptr;  // tbl_touch_reduce's scattered (position, index) words
   uint16_t *in_fill = nullptr;  // a batch's one port as an array (vp_dev_batch.in_port)
   size_t in_fill_n = 0;
+  // vp_tx_build (vp_tx.hip): entries per block and port, scanned in place into
+  // write positions; the last call's end and the stream it ran on
+  uint32_t *tx_cnt = nullptr;
+  size_t tx_cnt_n = 0;
+  hipEvent_t tx_ev = nullptr;
+  hipStream_t tx_last = nullptr;
+  bool tx_used = false;
   // tbl_new_keys_unsorted: the tagged key set (3 x u64 per slot, never
   // reset: a slot of an older tag is empty), its tag, first-sighting bits
   // per position and their scan, the first sightings' miss ordinals and

@@ -13,8 +13,8 @@ import ctypes as C
 import numpy as np
 
 from . import (BridgeConfigC, DevBatchC, FwConfigC, LbConfigC, MbufBatchC,
-               NatConfigC, PolConfigC, ServeExpiryStatsC, ServeStatsC, TableStatsC, _check,
-               lib)
+               NatConfigC, PolConfigC, ServeExpiryStatsC, ServeStatsC, TableStatsC,
+               TxListsC, TxStatsC, _check, lib)
 
 
 def _dptr(t):
@@ -120,6 +120,34 @@ class NfBase:
                 _check(rc, "vp_process_device (call %d)" % done.value, self.L)
         run.tensors = keep
         return run
+
+    def tx_build(self, out, in_dev, lens, idx, offset, stats=None, stream=None):
+        """vp_tx_build: the per-port transmit lists of a device-resident batch
+        from its out ports (what nf.c does with nf_process's return value,
+        nf.c:159-174). out / lens: 16-bit CUDA tensors of n; in_dev: the same,
+        or an int (every packet on that port), as for process_device. idx:
+        int32/uint32 CUDA tensor whose length is the capacity (None: capacity
+        0, only offsets and stats); offset: the same kind, n_devices + 1
+        entries; stats: None or a CUDA tensor of at least
+        sizeof(vigor_amd.TxStatsC) bytes. Enqueued on `stream` (the context's
+        own for None) and not waited for: synchronize before reading."""
+        port = isinstance(in_dev, int)
+        n = out.numel()
+        # (an empty tensor has no address and a NULL out_dev is VP_EINVAL: with
+        # n == 0 nothing is read through it, any device address serves)
+        b = DevBatchC(n=n, len=_dptr(lens),
+                      in_dev=None if port else in_dev.data_ptr(),
+                      out_dev=out.data_ptr() if n else offset.data_ptr(),
+                      in_port=in_dev if port else 0)
+        if idx is not None:
+            assert idx.is_cuda and idx.element_size() == 4
+        assert offset.is_cuda and offset.element_size() == 4
+        if stats is not None:
+            assert stats.is_cuda and stats.numel() * stats.element_size() >= C.sizeof(TxStatsC)
+        lists = TxListsC(idx=_dptr(idx), cap=idx.numel() if idx is not None else 0,
+                         offset=offset.data_ptr(), stats=_dptr(stats))
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._ck(self.L.vp_tx_build(self.h, C.byref(b), C.byref(lists), s), "vp_tx_build")
 
     def sync_state(self):
         """Multi-GPU: merge the ranks' timestamps (collective)."""
