@@ -222,6 +222,55 @@ typedef struct vp_tx_lists {
  * VP_MAX_DEVICES devices. n == 0: all offsets 0, stats zero. */
 int vp_tx_build(vp_ctx *ctx, const vp_dev_batch *batch, const vp_tx_lists *lists, void *stream);
 
+typedef struct vp_tx_frames {
+  uint8_t *data;      /* device, 16-byte aligned, cap_bytes bytes; may be NULL iff cap_bytes == 0 */
+  uint64_t cap_bytes;
+  uint64_t *port_off; /* device, n_devices + 1: port d's bytes are data[port_off[d] .. port_off[d+1]) */
+  uint64_t *pos;      /* device, lists->cap entries, or NULL: pos[e] = byte offset in data of
+                         entry e's frame */
+} vp_tx_frames;
+
+/* Pack the frames that the lists of vp_tx_build name into one contiguous
+ * byte stream per port, in transmit order: what flood()'s reference counts
+ * and rte_eth_tx_burst's mbuf pointers (nf.c:82-96, 159-174) amount to for a
+ * batch in device memory. Reads batch->frames, slot, n and len, and the lists'
+ * idx, cap and offset (device memory); writes nothing but out's buffers, and
+ * never the frames. With
+ *   E       = min(offset[n_devices], cap)   the entries idx really holds
+ *   i       = idx[e]
+ *   clen(e) = min(len[i], slot), pad(e) = (clen(e) + 15) & ~15     when i < n
+ *   clen(e) = pad(e) = 0, and nothing is read through i            when i >= n
+ *             (vp_tx_build writes no such entry; a garbage list cannot make
+ *             the call read outside the batch)
+ *   pos(e)  = sum of pad(k) over k < e, k < E   (64 bits)
+ * the lists being port-major, one running sum lays port 0's frames first,
+ * then port 1's, each port in packet order:
+ *   data[pos(e) .. pos(e) + clen(e))            frame i's first clen bytes
+ *   data[pos(e) + clen(e) .. pos(e) + pad(e))   zero
+ *   port_off[d] = pos(min(offset[d], cap)) for d <= n_devices; port_off[n_devices]
+ *                                               is the total
+ *   pos[e] = pos(e) for e < E, when pos is not NULL; nothing at or beyond pos[E]
+ * A flooded frame is copied once per list it stands in. An entry is written
+ * whole or not at all: iff pos(e) + pad(e) <= cap_bytes. port_off[] and pos[]
+ * always hold the true values, and the call still returns 0 when frames did
+ * not fit: the caller sees port_off[n_devices] > cap_bytes (as vp_tx_build
+ * does with cap). No byte of data at or beyond min(total, cap_bytes) is
+ * written. The result is deterministic: the same inputs give the same bytes
+ * everywhere the call writes. With cap == 0 every port_off is 0.
+ * The work (three kernel launches, the grid sized from lists->cap) is enqueued
+ * on `stream` (NULL: the context's own), after the work already there, and
+ * the call MAY RETURN BEFORE IT RAN. It makes no host round trip: offset[] is
+ * read on the device only. Ordering against the vp_tx_build that filled the
+ * lists is the caller's (the same stream, or an event); the library orders its
+ * own workspace. Like vp_tx_build it ends the NF's resident kernel, and after
+ * a multi-GPU attach it is local to the rank.
+ * VP_EINVAL: a NULL ctx, batch, lists, out, port_off or offset; a NULL idx
+ * with cap > 0; a NULL frames or len with n > 0 and cap > 0; slot below 64 or
+ * not a multiple of 16; frames or data not 16-byte aligned; a NULL data with
+ * cap_bytes > 0; a context with more than VP_MAX_DEVICES devices. */
+int vp_tx_pack(vp_ctx *ctx, const vp_dev_batch *batch, const vp_tx_lists *lists,
+               const vp_tx_frames *out, void *stream);
+
 /* Host memory the GPU may read and write frames in directly: a DPDK mbuf
  * pool's memory (the hugepages rte_pktmbuf_pool_create, nf.c:235-242, lays
  * the mbufs out in), registered once after the pool is created. Page-locked

@@ -1,0 +1,18 @@
+"""vp_tx_pack's three kernels (vp_txpack.hip) keep nothing in scratch memory:
+their kernel descriptors in the gfx950 code object that ships in
+vigor_amd/libvigpath.so have a private segment of 0 bytes (read as
+test_codeobj reads them). CPU only."""
+import pytest
+
+from test_codeobj import _find, _private_segments
+
+
+@pytest.fixture(scope="module")
+def segs():
+    return _private_segments()
+
+
+@pytest.mark.parametrize("kernel", ["txp_sizes", "txp_scan", "txp_copy"])
+def test_txpack_kernels_have_no_private_segment(segs, kernel):
+    for name, size in _find(segs, kernel).items():
+        assert size == 0, "%s keeps %d bytes per lane in scratch memory" % (name, size)

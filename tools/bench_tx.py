@@ -1,7 +1,7 @@
 """vp_tx_build over one headline-sized batch: the time of its three launches
 beside the bytes the algorithm has to move. Run by hand; not part of bench.py.
 
-  python3 tools/bench_tx.py [--packets 16777216] [--reps 20] [--step-ms MS]
+  python3 tools/bench_tx.py [--packets 16777216] [--reps 20] [--step-ms MS] [--pack]
 
 Three cases:
   two-port         vignat's headline outputs: every packet from port 0 (one
@@ -17,6 +17,12 @@ array and len, 6 B per packet (4 B with in_port: no port array), plus 4 B per
 list entry written. (tx_scatter does not read len, so the figure is an upper
 bound of what the kernels request.) Each call is timed between two events on
 the stream it is enqueued on, the calls back to back.
+--pack: after a case's lists are built, vp_tx_pack over them
+is timed the same way, with and without pos[], and in the same run on the same
+stream a plain device-to-device copy (torch's copy_, one hipMemcpyAsync) of
+the streams' total bytes. The frames are 64-byte slots of random bytes.
+Algorithmic bytes of a pack: idx and len read in two passes (12 B per entry),
+the payload read and written, and 8 B per entry of pos[].
 --step-ms: the headline step (bench.py's ms_per_step of the same session);
 every time is then also given as a fraction of it.
 """
@@ -60,6 +66,7 @@ def bridge_flood_outputs(n, dev):
 
 
 def measure(nf, nd, out, in_dev, lens, reps, dev):
+    """(result, (idx, offset, total)): the timed vp_tx_build and its lists."""
     n = out.numel()
     off = torch.zeros(nd + 1, dtype=torch.int32, device=dev)
     st = torch.zeros(C.sizeof(vigor_amd.TxStatsC), dtype=torch.uint8, device=dev)
@@ -86,7 +93,69 @@ def measure(nf, nd, out, in_dev, lens, reps, dev):
             "ms_median": round(ms[len(ms) // 2], 4), "ms_min": round(ms[0], 4),
             "ms_max": round(ms[-1], 4), "reps": reps,
             "alg_bytes": alg, "alg_bytes_per_packet": round(alg / max(n, 1), 2),
-            "alg_gb_per_s": round(alg / (ms[len(ms) // 2] * 1e-3) / 1e9, 1)}
+            "alg_gb_per_s": round(alg / (ms[len(ms) // 2] * 1e-3) / 1e9, 1)}, (idx, off, total)
+
+
+def timed(s, reps, call):
+    """ms of `reps` calls back to back on stream s, each between two events,
+    after 3 untimed ones; sorted."""
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(reps + 1)]
+    with torch.cuda.stream(s):
+        for _ in range(3):
+            call()
+        ev[0].record(s)
+        for k in range(reps):
+            call()
+            ev[k + 1].record(s)
+    s.synchronize()
+    return sorted(ev[k].elapsed_time(ev[k + 1]) for k in range(reps))
+
+
+def measure_pack(nf, nd, lens, idx, off, total, reps, dev):
+    """vp_tx_pack over built lists and 64-byte slots, and a plain copy of the
+    same payload on the same stream."""
+    n, slot = lens.numel(), 64
+    frames = torch.randint(0, 256, (n * slot,), dtype=torch.uint8, device=dev)
+    po = torch.zeros(nd + 1, dtype=torch.int64, device=dev)
+    pos = torch.zeros(max(total, 1), dtype=torch.int64, device=dev)
+    idx = idx[:total] if total else None
+    torch.cuda.synchronize()  # (torch filled the buffers on its own stream)
+    nf.tx_pack(frames, slot, lens, idx, off, None, po)  # the total, to size data
+    torch.cuda.synchronize()
+    payload = int(po.cpu().numpy().view(np.uint64)[nd])
+    data = torch.zeros(max(payload, 16), dtype=torch.uint8, device=dev)[:payload]
+    src = torch.randint(0, 256, (max(payload, 16),), dtype=torch.uint8, device=dev)[:payload]
+    dst = torch.empty_like(src)
+    s = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()
+    ms = timed(s, reps, lambda: nf.tx_pack(frames, slot, lens, idx, off, data, po,
+                                           pos[:total] if total else None, stream=s))
+    ms_np = timed(s, reps, lambda: nf.tx_pack(frames, slot, lens, idx, off, data, po, None,
+                                              stream=s))
+    ms_cp = timed(s, reps, lambda: dst.copy_(src))
+    # the first entries against a gather made with torch (a sanity check of the
+    # run, not the test: tests/test_txpack_gpu.py)
+    k = min(total, 4096)
+    if k:
+        i = idx[:k].long()
+        want = frames.view(n, slot)[i].clone()
+        cl = lens[i].long().clamp(max=slot)
+        want[torch.arange(slot, device=dev)[None, :] >= cl[:, None]] = 0
+        p = pos[:k]
+        assert bool((p == torch.cumsum((cl + 15) // 16 * 16, 0) - (cl + 15) // 16 * 16).all())
+        if bool((cl > 48).all()):  # every frame fills its four units
+            assert bool((data[:k * slot].view(k, slot) == want).all())
+    alg = 12 * total + 2 * payload + 8 * total
+    med = ms[len(ms) // 2]
+    med_cp = ms_cp[len(ms_cp) // 2]
+    return {"payload_bytes": payload, "pack_ms_median": round(med, 4),
+            "pack_ms_min": round(ms[0], 4), "pack_ms_max": round(ms[-1], 4),
+            "pack_no_pos_ms_median": round(ms_np[len(ms_np) // 2], 4),
+            "copy_ms_median": round(med_cp, 4), "copy_ms_min": round(ms_cp[0], 4),
+            "copy_ms_max": round(ms_cp[-1], 4),
+            "pack_over_copy": round(med / med_cp, 3) if med_cp else None,
+            "pack_alg_bytes": alg, "pack_alg_gb_per_s": round(alg / (med * 1e-3) / 1e9, 1),
+            "copy_gb_per_s": round(2 * payload / (med_cp * 1e-3) / 1e9, 1) if med_cp else None}
 
 
 def main():
@@ -95,6 +164,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--step-ms", type=float, default=None,
                     help="the headline step of the same session (bench.py ms_per_step)")
+    ap.add_argument("--pack", action="store_true",
+                    help="also time vp_tx_pack over each case's lists, beside a plain copy")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     n = args.packets
@@ -110,11 +181,22 @@ def main():
              ("two-port-drop16", nat, 2, out2, 0, lens),
              ("four-port-flood", br4, 4) + bridge_flood_outputs(n, dev)]
     for name, nf, nd, out, in_dev, ln in cases:
-        r = {"case": name, **measure(nf, nd, out, in_dev, ln, args.reps, dev)}
+        r, lists = measure(nf, nd, out, in_dev, ln, args.reps, dev)
+        r = {"case": name, **r}
         if args.step_ms:
             r["headline_step_ms"] = args.step_ms
             r["fraction_of_step"] = round(r["ms_median"] / args.step_ms, 4)
         print(json.dumps(r), flush=True)
+        if args.pack:
+            idx, off, total = lists
+            p = {"case": name + "-pack", "packets": n, "n_devices": nd, "entries": total,
+                 "reps": args.reps, **measure_pack(nf, nd, ln, idx, off, total, args.reps, dev)}
+            if args.step_ms:
+                p["headline_step_ms"] = args.step_ms
+                p["fraction_of_step"] = round(p["pack_ms_median"] / args.step_ms, 4)
+            print(json.dumps(p), flush=True)
+        del lists
+        torch.cuda.empty_cache()
 
 
 if __name__ == "__main__":

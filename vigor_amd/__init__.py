@@ -66,6 +66,12 @@ class TxListsC(C.Structure):
                 ("stats", C.c_void_p)]
 
 
+class TxFramesC(C.Structure):
+    """vp_tx_frames (include/vigpath.h): device pointers."""
+    _fields_ = [("data", C.c_void_p), ("cap_bytes", C.c_uint64), ("port_off", C.c_void_p),
+                ("pos", C.c_void_p)]
+
+
 # packets per block of vp_tx_build's kernels (vp_tx.hip kTxBlockPackets)
 TX_BLOCK_PACKETS = 2048
 
@@ -158,7 +164,7 @@ EXPORTS = ["vp_nat_create", "vp_bridge_create", "vp_lb_create", "vp_fw_create",
            "vp_last_error", "vp_register_host", "vp_unregister_host", "vp_process_mbufs",
            "vp_last_stage_ms", "vp_stage_ms", "vp_comm_abort", "vp_probe_slots",
            "vp_probe_slots_w", "vp_process_one", "vp_last_kernel", "vp_serve_stats_get",
-           "vp_serve_expiry_stats_get", "vp_tx_build"]
+           "vp_serve_expiry_stats_get", "vp_tx_build", "vp_tx_pack"]
 
 _libs = {}
 
@@ -262,6 +268,9 @@ def lib(path: str | None = None):
     L.vp_tx_build.argtypes = [C.c_void_p, C.POINTER(DevBatchC), C.POINTER(TxListsC),
                               C.c_void_p]
     L.vp_tx_build.restype = C.c_int
+    L.vp_tx_pack.argtypes = [C.c_void_p, C.POINTER(DevBatchC), C.POINTER(TxListsC),
+                             C.POINTER(TxFramesC), C.c_void_p]
+    L.vp_tx_pack.restype = C.c_int
     L.vp_last_error.argtypes = []
     L.vp_last_error.restype = C.c_char_p
     _libs[path] = L

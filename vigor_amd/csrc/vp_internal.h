@@ -99,6 +99,7 @@ hipError_t preload_pol(hipStream_t s);
 hipError_t preload_comm(hipStream_t s);
 hipError_t preload_mbuf(hipStream_t s);
 hipError_t preload_tx(hipStream_t s);
+hipError_t preload_txpack(hipStream_t s);
 
 // Owner-mode phase A stages (vp_last_stage_ms).
 constexpr int kStages = 8;
@@ -246,6 +247,13 @@ struct Workspace {
   hipEvent_t tx_ev = nullptr;
   hipStream_t tx_last = nullptr;
   bool tx_used = false;
+  // vp_tx_pack (vp_txpack.hip): the blocks' padded bytes, scanned in place
+  // into their first positions; the last call's end and its stream
+  uint64_t *txp_sum = nullptr;
+  size_t txp_sum_n = 0;
+  hipEvent_t txp_ev = nullptr;
+  hipStream_t txp_last = nullptr;
+  bool txp_used = false;
   // tbl_new_keys_unsorted: the tagged key set (3 x u64 per slot, never
   // reset: a slot of an older tag is empty), its tag, first-sighting bits
   // per position and their scan, the first sightings' miss ordinals and

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import (BridgeConfigC, DevBatchC, FwConfigC, LbConfigC, MbufBatchC,
                NatConfigC, PolConfigC, ServeExpiryStatsC, ServeStatsC, TableStatsC,
-               TxListsC, TxStatsC, _check, lib)
+               TxFramesC, TxListsC, TxStatsC, _check, lib)
 
 
 def _dptr(t):
@@ -148,6 +148,37 @@ class NfBase:
                          offset=offset.data_ptr(), stats=_dptr(stats))
         s = C.c_void_p(stream.cuda_stream) if stream is not None else None
         self._ck(self.L.vp_tx_build(self.h, C.byref(b), C.byref(lists), s), "vp_tx_build")
+
+    def tx_pack(self, frames, slot, lens, idx, offset, data, port_off, pos=None, stream=None):
+        """vp_tx_pack: the frames that tx_build's lists name, packed into one
+        byte stream per port (each frame at min(len, slot) bytes, zero-padded
+        to 16). frames: uint8 CUDA tensor of n * slot bytes (only read); lens:
+        16-bit CUDA tensor of n; idx / offset: as tx_build wrote them (idx
+        None: capacity 0); data: uint8 CUDA tensor whose size is the capacity
+        in bytes (None: 0); port_off: 64-bit CUDA tensor of n_devices + 1;
+        pos: None or a 64-bit CUDA tensor of at least idx's length. Enqueued
+        on `stream` (the context's own for None) and not waited for."""
+        n = lens.numel()
+        assert frames.numel() == n * slot
+        b = DevBatchC(frames=_dptr(frames) if n else None, slot=slot, n=n,
+                      len=_dptr(lens) if n else None)
+        cap = idx.numel() if idx is not None else 0
+        if idx is not None:
+            assert idx.is_cuda and idx.element_size() == 4
+        assert offset.is_cuda and offset.element_size() == 4
+        assert port_off.is_cuda and port_off.element_size() == 8
+        if data is not None:
+            assert data.is_cuda and data.element_size() == 1
+        if pos is not None:
+            assert pos.is_cuda and pos.element_size() == 8 and pos.numel() >= cap
+        cap_bytes = data.numel() if data is not None else 0
+        lists = TxListsC(idx=_dptr(idx) if cap else None, cap=cap, offset=offset.data_ptr(),
+                         stats=None)
+        out = TxFramesC(data=_dptr(data) if cap_bytes else None, cap_bytes=cap_bytes,
+                        port_off=port_off.data_ptr(), pos=_dptr(pos) if cap else None)
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._ck(self.L.vp_tx_pack(self.h, C.byref(b), C.byref(lists), C.byref(out), s),
+                 "vp_tx_pack")
 
     def sync_state(self):
         """Multi-GPU: merge the ranks' timestamps (collective)."""
