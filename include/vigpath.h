@@ -271,6 +271,66 @@ typedef struct vp_tx_frames {
 int vp_tx_pack(vp_ctx *ctx, const vp_dev_batch *batch, const vp_tx_lists *lists,
                const vp_tx_frames *out, void *stream);
 
+typedef struct vp_tx_next {
+  uint8_t  *frames; /* device, 16-byte aligned, cap * slot bytes; may be NULL iff cap == 0 */
+  uint32_t  slot;   /* multiple of 16, >= 64; need not equal the source batch's slot */
+  uint32_t  cap;    /* packets the buffers below hold */
+  uint16_t *len;    /* device, cap entries */
+  int64_t  *now;    /* device, cap entries, or NULL */
+  uint32_t *src;    /* device, cap entries, or NULL: index in the source batch */
+  uint32_t *count;  /* device, one word: entries of the port's list (may exceed cap) */
+} vp_tx_next;
+
+/* Hand one port's list to the next NF as a device batch: the frames that list
+ * `port` of vp_tx_build names, gathered into consecutive slots with their
+ * len[], their time and their index of origin -- the cable between two of the
+ * reference's boxes (one NF per binary, nf.c:150-176 on each side), for two
+ * contexts on one GPU. Reads batch->frames, slot, n, len and now (or now0 and
+ * now_step), and the lists' idx, cap and offset (device memory); writes nothing
+ * but out's buffers, and never the source batch or the lists. With
+ *   E  = min(offset[n_devices], cap)          the entries idx really holds
+ *   lo = min(offset[port], E), hi = min(offset[port + 1], E)
+ *   C  = hi - lo                              what idx holds of that list
+ *   i  = idx[lo + k] for k < C
+ *   w  = min(batch->slot, out->slot)
+ * the call writes *count = C, always the true count, also when C > out->cap,
+ * and for k < min(C, out->cap) with i < n:
+ *   frames[k*slot .. k*slot + w)         the first w bytes of source slot i,
+ *                                        verbatim: the slot image, the bytes
+ *                                        past len[i] included, as an mbuf
+ *                                        passed on by pointer keeps them
+ *   frames[k*slot + w .. (k+1)*slot)     zero (bytes past a frame's slot read
+ *                                        as 0)
+ *   len[k] = len[i]                      unchanged, not clipped to a slot
+ *   now[k] = batch->now[i], or now0 + i * now_step (64 bits) when batch->now
+ *                                        is NULL
+ *   src[k] = i
+ * and with i >= n (vp_tx_build writes no such entry; a garbage list cannot
+ * make the call read outside the batch) nothing is read through i: the slot is
+ * zero, len[k] = 0, now[k] = 0, src[k] = i. Nothing at or beyond entry
+ * min(C, out->cap) of any buffer is written. The result is deterministic: the
+ * same inputs give the same bytes. The order inside the output is the list's,
+ * packet order, so a batch whose times do not go back gives times that do not
+ * go back; the output is a valid vp_dev_batch for any context, with in_dev
+ * NULL and an in_port of the caller's choosing.
+ * The work (one kernel launch, the grid sized from out->cap, at least one
+ * block so that count is written when cap == 0) is enqueued on `stream` (NULL:
+ * the context's own), after the work already there, and the call MAY RETURN
+ * BEFORE IT RAN. It makes no host round trip: offset[] is read on the device
+ * only. Ordering against the vp_tx_build that filled the lists is the
+ * caller's (the same stream, or an event). It needs no workspace. Like
+ * vp_tx_build it ends the NF's resident kernel, and after a multi-GPU attach
+ * it is local to the rank.
+ * VP_EINVAL: a NULL ctx, batch, lists, out, offset or count; a NULL idx with
+ * lists->cap > 0; port >= n_devices; a context with more than VP_MAX_DEVICES
+ * devices; either slot below 64 or not a multiple of 16; either frames not
+ * 16-byte aligned; a NULL out->frames or out->len with out->cap > 0; a NULL
+ * batch->frames or batch->len with n > 0, lists->cap > 0 and out->cap > 0; the
+ * byte ranges [batch->frames, + n * slot) and [out->frames, + cap * slot)
+ * overlapping. */
+int vp_tx_rebatch(vp_ctx *ctx, const vp_dev_batch *batch, const vp_tx_lists *lists,
+                  uint32_t port, const vp_tx_next *out, void *stream);
+
 /* Host memory the GPU may read and write frames in directly: a DPDK mbuf
  * pool's memory (the hugepages rte_pktmbuf_pool_create, nf.c:235-242, lays
  * the mbufs out in), registered once after the pool is created. Page-locked

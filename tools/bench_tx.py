@@ -2,6 +2,7 @@
 beside the bytes the algorithm has to move. Run by hand; not part of bench.py.
 
   python3 tools/bench_tx.py [--packets 16777216] [--reps 20] [--step-ms MS] [--pack]
+                             [--rebatch]
 
 Three cases:
   two-port         vignat's headline outputs: every packet from port 0 (one
@@ -23,6 +24,12 @@ stream a plain device-to-device copy (torch's copy_, one hipMemcpyAsync) of
 the streams' total bytes. The frames are 64-byte slots of random bytes.
 Algorithmic bytes of a pack: idx and len read in two passes (12 B per entry),
 the payload read and written, and 8 B per entry of pos[].
+--rebatch: after a case's lists are built, vp_tx_rebatch of one port's list
+(port 1, the fullest in every case) into 64-byte slots with
+len[], now[] and src[] is timed the same way, beside a plain device-to-device
+copy of the same number of slot bytes on the same stream. Algorithmic bytes of
+a rebatch: each listed slot read and written, 14 B per entry read (idx, len,
+now) and 14 B written (len, now, src).
 --step-ms: the headline step (bench.py's ms_per_step of the same session);
 every time is then also given as a fraction of it.
 """
@@ -158,6 +165,55 @@ def measure_pack(nf, nd, lens, idx, off, total, reps, dev):
             "copy_gb_per_s": round(2 * payload / (med_cp * 1e-3) / 1e9, 1) if med_cp else None}
 
 
+def measure_rebatch(nf, nd, lens, idx, off, total, port, reps, dev):
+    """vp_tx_rebatch of list `port` over built lists and 64-byte slots, and a
+    plain copy of the same slot bytes on the same stream."""
+    n, slot = lens.numel(), 64
+    frames = torch.randint(0, 256, (n * slot,), dtype=torch.uint8, device=dev)
+    now = torch.arange(n, dtype=torch.int64, device=dev) + T.NOW0
+    bounds = off.cpu().numpy().view(np.uint32)
+    lo, count = int(bounds[port]), int(bounds[port + 1] - bounds[port])
+    idx = idx[:total] if total else None
+    cap = max(count, 1)
+    o_f = torch.zeros(cap * slot, dtype=torch.uint8, device=dev)
+    o_l = torch.zeros(cap, dtype=torch.int16, device=dev)
+    o_n = torch.zeros(cap, dtype=torch.int64, device=dev)
+    o_s = torch.zeros(cap, dtype=torch.int32, device=dev)
+    cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+    src = torch.randint(0, 256, (cap * slot,), dtype=torch.uint8, device=dev)
+    dst = torch.empty_like(src)
+    s = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()  # (torch filled the buffers on its own stream)
+
+    def call():
+        nf.tx_rebatch(frames, slot, lens, idx, off, port, o_f, slot, o_l, cnt, out_now=o_n,
+                      out_src=o_s, now=now, stream=s)
+
+    ms = timed(s, reps, call)
+    ms_cp = timed(s, reps, lambda: dst.copy_(src))
+    # the first entries against a gather made with torch (a sanity check of the
+    # run, not the test: tests/test_txbatch_gpu.py)
+    assert int(cnt.cpu()[0]) == count
+    k = min(count, 4096)
+    if k:
+        i = idx[lo:lo + k].long()
+        assert bool((o_f[:k * slot].view(k, slot) == frames.view(n, slot)[i]).all())
+        assert bool((o_l[:k] == lens[i]).all()) and bool((o_n[:k] == now[i]).all())
+        assert bool((o_s[:k].long() == i).all())
+    alg = 2 * count * slot + 28 * count
+    med, med_cp = ms[len(ms) // 2], ms_cp[len(ms_cp) // 2]
+    return {"port": port, "list_entries": count, "slot_bytes": count * slot,
+            "rebatch_ms_median": round(med, 4), "rebatch_ms_min": round(ms[0], 4),
+            "rebatch_ms_max": round(ms[-1], 4), "copy_ms_median": round(med_cp, 4),
+            "copy_ms_min": round(ms_cp[0], 4), "copy_ms_max": round(ms_cp[-1], 4),
+            "rebatch_over_copy": round(med / med_cp, 3) if med_cp else None,
+            "bytes_over_copy_bytes": round(alg / (2 * count * slot), 3) if count else None,
+            "rebatch_alg_bytes": alg,
+            "rebatch_alg_gb_per_s": round(alg / (med * 1e-3) / 1e9, 1),
+            "copy_gb_per_s": round(2 * count * slot / (med_cp * 1e-3) / 1e9, 1)
+            if med_cp else None}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--packets", type=int, default=1 << 24)
@@ -166,6 +222,8 @@ def main():
                     help="the headline step of the same session (bench.py ms_per_step)")
     ap.add_argument("--pack", action="store_true",
                     help="also time vp_tx_pack over each case's lists, beside a plain copy")
+    ap.add_argument("--rebatch", action="store_true",
+                    help="also time vp_tx_rebatch of port 1's list, beside a plain copy")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     n = args.packets
@@ -194,6 +252,15 @@ def main():
             if args.step_ms:
                 p["headline_step_ms"] = args.step_ms
                 p["fraction_of_step"] = round(p["pack_ms_median"] / args.step_ms, 4)
+            print(json.dumps(p), flush=True)
+        if args.rebatch:
+            idx, off, total = lists
+            p = {"case": name + "-rebatch", "packets": n, "n_devices": nd, "entries": total,
+                 "reps": args.reps,
+                 **measure_rebatch(nf, nd, ln, idx, off, total, 1, args.reps, dev)}
+            if args.step_ms:
+                p["headline_step_ms"] = args.step_ms
+                p["fraction_of_step"] = round(p["rebatch_ms_median"] / args.step_ms, 4)
             print(json.dumps(p), flush=True)
         del lists
         torch.cuda.empty_cache()

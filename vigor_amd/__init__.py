@@ -72,6 +72,13 @@ class TxFramesC(C.Structure):
                 ("pos", C.c_void_p)]
 
 
+class TxNextC(C.Structure):
+    """vp_tx_next (include/vigpath.h): device pointers."""
+    _fields_ = [("frames", C.c_void_p), ("slot", C.c_uint32), ("cap", C.c_uint32),
+                ("len", C.c_void_p), ("now", C.c_void_p), ("src", C.c_void_p),
+                ("count", C.c_void_p)]
+
+
 # packets per block of vp_tx_build's kernels (vp_tx.hip kTxBlockPackets)
 TX_BLOCK_PACKETS = 2048
 
@@ -164,7 +171,7 @@ EXPORTS = ["vp_nat_create", "vp_bridge_create", "vp_lb_create", "vp_fw_create",
            "vp_last_error", "vp_register_host", "vp_unregister_host", "vp_process_mbufs",
            "vp_last_stage_ms", "vp_stage_ms", "vp_comm_abort", "vp_probe_slots",
            "vp_probe_slots_w", "vp_process_one", "vp_last_kernel", "vp_serve_stats_get",
-           "vp_serve_expiry_stats_get", "vp_tx_build", "vp_tx_pack"]
+           "vp_serve_expiry_stats_get", "vp_tx_build", "vp_tx_pack", "vp_tx_rebatch"]
 
 _libs = {}
 
@@ -271,6 +278,9 @@ def lib(path: str | None = None):
     L.vp_tx_pack.argtypes = [C.c_void_p, C.POINTER(DevBatchC), C.POINTER(TxListsC),
                              C.POINTER(TxFramesC), C.c_void_p]
     L.vp_tx_pack.restype = C.c_int
+    L.vp_tx_rebatch.argtypes = [C.c_void_p, C.POINTER(DevBatchC), C.POINTER(TxListsC),
+                                C.c_uint32, C.POINTER(TxNextC), C.c_void_p]
+    L.vp_tx_rebatch.restype = C.c_int
     L.vp_last_error.argtypes = []
     L.vp_last_error.restype = C.c_char_p
     _libs[path] = L
@@ -296,6 +306,7 @@ def _check(rc: int, what: str, L=None):
 
 
 from .nf import Bridge, Fw, Lb, Nat, NfBase, Pol  # noqa: E402,F401
+from .chain import Chain  # noqa: E402,F401
 from .config import (bridge_config_from_args, fw_config_from_args,  # noqa
                      lb_config_from_args, nat_config_from_args,
                      pol_config_from_args)

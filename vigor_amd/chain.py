@@ -1,0 +1,154 @@
+"""NF chains on one GPU: what the reference runs as one box per NF with a
+cable between each pair (firewall -> NAT, bridge -> policer, ...), as contexts
+whose batches stay in device memory. A link hands one port's transmit list of
+a stage to a later stage as that stage's input batch: vp_tx_build, then
+vp_tx_rebatch, then vp_process_device. No frame byte crosses
+to the host.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+
+class Chain:
+    """`stages`: NF objects (vigor_amd.Nat, Fw, ...) on one GPU. `links`:
+    (s, out_port, t, in_port) tuples with t > s: what stage s sends to its
+    port out_port arrives at stage t on port in_port. Every stage but 0 has
+    exactly one inbound link (merging two lists into one stage is not
+    supported); anything else raises ValueError. Packets a stage sends to a
+    port without a link stay in that stage's result with their out port: they
+    have left the chain."""
+
+    def __init__(self, stages, links):
+        self.stages = list(stages)
+        if not self.stages:
+            raise ValueError("a chain needs a stage")
+        k = len(self.stages)
+        self.inbound = [None] * k
+        self.outbound = [[] for _ in range(k)]
+        for link in links:
+            s, out_port, t, in_port = (int(x) for x in link)
+            if not (0 <= s < k and 0 <= t < k):
+                raise ValueError("link %r names a stage outside the chain" % (link,))
+            if t <= s:
+                raise ValueError("link %r goes backward" % (link,))
+            if not 0 <= out_port < self.stages[s].cfg.n_devices:
+                raise ValueError("link %r leaves from a port stage %d does not have" % (link, s))
+            if not 0 <= in_port <= 0xFFFF:
+                raise ValueError("link %r arrives on a port beyond 16 bits" % (link,))
+            if self.inbound[t] is not None:
+                raise ValueError("stage %d has two inbound links" % t)
+            self.inbound[t] = (s, out_port, in_port)
+            self.outbound[s].append((out_port, t))
+        for t in range(1, k):
+            if self.inbound[t] is None:
+                raise ValueError("stage %d has no inbound link" % t)
+        self.stream = None
+        self._lists = [None] * k  # per stage: (idx, offset)
+        self._bufs = [None] * k   # per stage >= 1: its input batch's buffers
+
+    def _grown(self, t, n, slot, dev):
+        """Stage t's input buffers for n packets: kept from call to call,
+        replaced by larger ones on demand."""
+        b = self._bufs[t]
+        if b is None or b["cap"] < n or b["slot"] != slot:
+            cap = max(n, 2 * b["cap"] if b and b["slot"] == slot else 0, 64)
+            b = {"cap": cap, "slot": slot,
+                 "frames": torch.empty(cap * slot, dtype=torch.uint8, device=dev),
+                 "lens": torch.empty(cap, dtype=torch.int16, device=dev),
+                 "now": torch.empty(cap, dtype=torch.int64, device=dev),
+                 "src": torch.empty(cap, dtype=torch.int32, device=dev),
+                 "out": torch.empty(cap, dtype=torch.int16, device=dev),
+                 "count": torch.zeros(1, dtype=torch.int32, device=dev)}
+            self._bufs[t] = b
+        return b
+
+    def run(self, frames, lens, in_dev, slot: int, now=None, now0: int = 0, now_step: int = 0):
+        """One batch through the chain. frames / lens / in_dev / now / now0 /
+        now_step: stage 0's batch, as for process_device (frames are rewritten
+        in place). Stage 0 processes the caller's batch; then, for every stage
+        in order that has a link: tx_build over its out ports, one small
+        device-to-host read of offset[] to size the next batches (the one host
+        synchronisation per stage), tx_rebatch of each linked port into buffers
+        the chain owns, and process_device of the target stage with every
+        packet on the link's in_port and the gathered per-packet times. All of
+        it is enqueued on one stream of the chain's, which is waited for once
+        more before the call returns.
+
+        Returns one dict per stage: n (packets the stage received), frames
+        (n * slot bytes, as the stage left them), lens, out (its out ports)
+        and origin (int64: each packet's index in the caller's batch, composed
+        from the links' src arrays). The tensors of the stages after 0 are the
+        chain's own buffers: valid until the next run. State persists across
+        calls in the stages' contexts."""
+        dev = frames.device
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(device=dev)
+        S = self.stream
+        S.wait_stream(torch.cuda.current_stream(dev))
+        k = len(self.stages)
+        n0 = lens.numel()
+        res = [None] * k
+        with torch.cuda.stream(S):
+            out0 = torch.zeros(n0, dtype=torch.int16, device=dev)
+            if n0:
+                self.stages[0].process_device(frames, lens, in_dev, out0, slot, now=now,
+                                              now0=now0, now_step=now_step, stream=S)
+            res[0] = {"n": n0, "frames": frames, "lens": lens, "out": out0,
+                      "origin": torch.arange(n0, dtype=torch.int64, device=dev)}
+            time = [(now, now0, now_step)] + [None] * (k - 1)
+            ports = [in_dev] + [None] * (k - 1)
+            for s in range(k):
+                r = res[s]
+                if not self.outbound[s] or r["n"] == 0:
+                    for _, t in self.outbound[s]:
+                        res[t] = self._empty(slot, dev)
+                    continue
+                nf = self.stages[s]
+                nd = nf.cfg.n_devices
+                offset = self._build(s, nf, nd, r, ports[s], dev)
+                idx = self._lists[s][0]
+                t_now, t_now0, t_step = time[s]
+                for out_port, t in self.outbound[s]:
+                    cnt = int(offset[out_port + 1]) - int(offset[out_port])
+                    if cnt == 0:
+                        res[t] = self._empty(slot, dev)
+                        continue
+                    b = self._grown(t, cnt, slot, dev)
+                    nf.tx_rebatch(r["frames"], slot, r["lens"], idx, self._lists[s][1], out_port,
+                                  b["frames"][:cnt * slot], slot, b["lens"][:cnt], b["count"],
+                                  out_now=b["now"][:cnt], out_src=b["src"][:cnt], now=t_now,
+                                  now0=t_now0, now_step=t_step, stream=S)
+                    in_port = self.inbound[t][2]
+                    self.stages[t].process_device(b["frames"][:cnt * slot], b["lens"][:cnt],
+                                                  in_port, b["out"][:cnt], slot,
+                                                  now=b["now"][:cnt], stream=S)
+                    time[t] = (b["now"][:cnt], 0, 0)
+                    ports[t] = in_port
+                    res[t] = {"n": cnt, "frames": b["frames"][:cnt * slot],
+                              "lens": b["lens"][:cnt], "out": b["out"][:cnt],
+                              "origin": r["origin"][b["src"][:cnt].long()]}
+        S.synchronize()
+        return res
+
+    @staticmethod
+    def _empty(slot, dev):
+        z16 = torch.zeros(0, dtype=torch.int16, device=dev)
+        return {"n": 0, "frames": torch.zeros(0, dtype=torch.uint8, device=dev), "lens": z16,
+                "out": z16.clone(), "origin": torch.zeros(0, dtype=torch.int64, device=dev)}
+
+    def _build(self, s, nf, nd, r, in_dev, dev):
+        """Stage s's transmit lists over its result; returns offset[] on the
+        host. A list that outgrew idx (floods) is built again with room."""
+        n = r["n"]
+        if self._lists[s] is None or self._lists[s][0].numel() < n:
+            self._lists[s] = (torch.empty(n, dtype=torch.int32, device=dev),
+                              torch.zeros(nd + 1, dtype=torch.int32, device=dev))
+        while True:
+            idx, off_t = self._lists[s]
+            nf.tx_build(r["out"], in_dev, r["lens"], idx, off_t, None, stream=self.stream)
+            offset = off_t.cpu().numpy().view(np.uint32)  # (waits for the stream)
+            if int(offset[nd]) <= idx.numel():
+                return offset
+            self._lists[s] = (torch.empty(int(offset[nd]), dtype=torch.int32, device=dev), off_t)

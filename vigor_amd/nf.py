@@ -14,7 +14,7 @@ import numpy as np
 
 from . import (BridgeConfigC, DevBatchC, FwConfigC, LbConfigC, MbufBatchC,
                NatConfigC, PolConfigC, ServeExpiryStatsC, ServeStatsC, TableStatsC,
-               TxFramesC, TxListsC, TxStatsC, _check, lib)
+               TxFramesC, TxListsC, TxNextC, TxStatsC, _check, lib)
 
 
 def _dptr(t):
@@ -179,6 +179,53 @@ class NfBase:
         s = C.c_void_p(stream.cuda_stream) if stream is not None else None
         self._ck(self.L.vp_tx_pack(self.h, C.byref(b), C.byref(lists), C.byref(out), s),
                  "vp_tx_pack")
+
+    def tx_rebatch(self, frames, slot, lens, idx, offset, port, out_frames, out_slot, out_lens,
+                   count, out_now=None, out_src=None, now=None, now0: int = 0,
+                   now_step: int = 0, stream=None):
+        """vp_tx_rebatch: list `port` of tx_build's lists as the next NF's
+        device batch -- the listed slots gathered into consecutive slots of
+        out_frames (out_slot bytes each, zero-filled past the narrower slot),
+        with len[], the per-packet time and the index of origin carried along.
+        frames: uint8 CUDA tensor of n * slot bytes (only read); lens: 16-bit
+        CUDA tensor of n; now: None (now0 + i * now_step) or a 64-bit CUDA
+        tensor of n; idx / offset: as tx_build wrote them (idx None: capacity
+        0). out_lens: 16-bit CUDA tensor whose length is the capacity in
+        packets (None: 0); out_frames: uint8 CUDA tensor of capacity *
+        out_slot bytes; out_now: None or a 64-bit tensor, out_src: None or a
+        32-bit tensor, each of at least the capacity; count: 32-bit CUDA
+        tensor of one word, the list's true length afterwards. Enqueued on
+        `stream` (the context's own for None) and not waited for."""
+        n = lens.numel()
+        assert frames.numel() == n * slot
+        cap = out_lens.numel() if out_lens is not None else 0
+        if idx is not None:
+            assert idx.is_cuda and idx.element_size() == 4
+        assert offset.is_cuda and offset.element_size() == 4
+        assert count.is_cuda and count.element_size() == 4 and count.numel() >= 1
+        if cap:
+            assert out_lens.is_cuda and out_lens.element_size() == 2
+            assert out_frames.is_cuda and out_frames.element_size() == 1
+            assert out_frames.numel() == cap * out_slot
+        if out_now is not None:
+            assert out_now.is_cuda and out_now.element_size() == 8 and out_now.numel() >= cap
+        if out_src is not None:
+            assert out_src.is_cuda and out_src.element_size() == 4 and out_src.numel() >= cap
+        if now is not None:
+            assert now.is_cuda and now.element_size() == 8 and now.numel() == n
+        b = DevBatchC(frames=_dptr(frames) if n else None, slot=slot, n=n,
+                      len=_dptr(lens) if n else None,
+                      now=_dptr(now) if n else None, now0=now0, now_step=now_step)
+        lcap = idx.numel() if idx is not None else 0
+        lists = TxListsC(idx=_dptr(idx) if lcap else None, cap=lcap, offset=offset.data_ptr(),
+                         stats=None)
+        out = TxNextC(frames=_dptr(out_frames) if cap else None, slot=out_slot, cap=cap,
+                      len=_dptr(out_lens) if cap else None,
+                      now=_dptr(out_now) if cap else None,
+                      src=_dptr(out_src) if cap else None, count=count.data_ptr())
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._ck(self.L.vp_tx_rebatch(self.h, C.byref(b), C.byref(lists), port, C.byref(out), s),
+                 "vp_tx_rebatch")
 
     def sync_state(self):
         """Multi-GPU: merge the ranks' timestamps (collective)."""
