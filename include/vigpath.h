@@ -331,6 +331,97 @@ typedef struct vp_tx_next {
 int vp_tx_rebatch(vp_ctx *ctx, const vp_dev_batch *batch, const vp_tx_lists *lists,
                   uint32_t port, const vp_tx_next *out, void *stream);
 
+#define VP_TX_MERGE_MAX 8
+
+typedef struct vp_tx_source {
+  vp_ctx *ctx;               /* the context whose n_devices shaped `lists` */
+  const vp_dev_batch *batch; /* frames, slot, n, len, now | now0, now_step */
+  const vp_tx_lists *lists;  /* as vp_tx_build wrote them */
+  uint32_t port;             /* which list */
+  uint32_t in_port;          /* port these packets arrive on (<= 0xFFFF) */
+  const uint32_t *key;       /* device, batch->n entries, or NULL: key(i) = i */
+} vp_tx_source;
+
+typedef struct vp_tx_merged {
+  uint8_t  *frames; /* device, 16-byte aligned, cap * slot bytes; may be NULL iff cap == 0 */
+  uint32_t  slot;   /* multiple of 16, >= 64; need not equal any source's slot */
+  uint32_t  cap;    /* packets the buffers below hold */
+  uint16_t *len;    /* device, cap entries */
+  int64_t  *now;    /* device, cap entries, or NULL */
+  uint16_t *in_dev; /* device, cap entries, or NULL: srcs[j].in_port of each packet's source */
+  uint32_t *key;    /* device, cap entries, or NULL: the packet's merge key */
+  uint32_t *src;    /* device, cap entries, required with cap > 0: index in its source batch */
+  uint8_t  *which;  /* device, cap entries, required with cap > 0: its source number j */
+  uint32_t *count;  /* device, one word: total entries of all sources (may exceed cap) */
+} vp_tx_merged;
+
+/* Merge several lists into one NF's device batch: where the cables of several
+ * boxes (or of several ports of one) lead into one box, that box sees their
+ * packets interleaved by the time they entered the first box. What
+ * vp_tx_rebatch does for one list, for n_srcs of them, ordered by a 32-bit key
+ * per packet: the caller passes each packet's position in the chain's input.
+ * Reads, of every source, batch->frames, slot, n, len and now (or now0 and
+ * now_step), the lists' idx, cap and offset, and key (device memory); writes
+ * nothing but out's buffers, and never a source batch, a list or a key array.
+ * Per source j, with n_devices that of srcs[j].ctx,
+ *   E_j  = min(offset[n_devices], cap)        the entries idx really holds
+ *   lo_j = min(offset[port], E_j), hi_j = min(offset[port + 1], E_j)
+ *   C_j  = hi_j - lo_j                        what idx holds of that list
+ * and total = the sum of all C_j. Entry (j, m), m < C_j, is packet
+ *   i = idx_j[lo_j + m]   with   key(j, m) = key_j[i], or i when key is NULL;
+ *                                with i >= n_j the key is i, and nothing is
+ *                                read through i
+ * The output holds all entries ordered by key, ascending; among equal keys by
+ * source number j, ascending; within one source in list order m. Equivalently
+ * entry (j, m) with key x stands at position
+ *   p = m + sum over j' < j of #{m' : key(j', m') <= x}
+ *         + sum over j' > j of #{m' : key(j', m') <  x}
+ * which is that stable merge provided every source's keys do not decrease
+ * along its list -- true of key == NULL (vp_tx_build's lists ascend) and of the
+ * composed origins of a batch in packet order. The precondition is the
+ * caller's. Where keys do decrease the order is unspecified, but the call
+ * still reads nothing outside the batches, lists and key arrays and writes
+ * nothing at or beyond min(total, cap) of any output buffer.
+ * The call writes *count = total, always the true value, also when total >
+ * out->cap (0xFFFFFFFF where the sum passes 32 bits), and for every position
+ * p < min(total, out->cap), with (j, m) the entry that stands there, i its
+ * packet and w = min(srcs[j].batch->slot, out->slot):
+ *   frames[p*slot .. p*slot + w)        the first w bytes of source j's slot
+ *                                       i, verbatim, as vp_tx_rebatch; source
+ *                                       slots may differ from each other
+ *   frames[p*slot + w .. (p+1)*slot)    zero
+ *   len[p] = len_j[i]                   unchanged, not clipped to a slot
+ *   now[p] = now_j[i], or that source's now0 + i * now_step (64 bits)
+ *   in_dev[p] = srcs[j].in_port
+ *   key[p] = key(j, m),  src[p] = i,  which[p] = j
+ * and with i >= n_j the slot is zero, len[p] = 0 and now[p] = 0. Nothing at or
+ * beyond entry min(total, out->cap) of any buffer is written. The result is
+ * deterministic. Times that do not go back inside every source and agree with
+ * the key order give times that do not go back; the output is a valid
+ * vp_dev_batch for `ctx` with in_dev = out->in_dev. With n_srcs == 1 and
+ * key == NULL, frames, len, now and src hold exactly vp_tx_rebatch's bytes.
+ * `ctx` is the receiving NF's context; it supplies the default stream. Every
+ * source context must be on ctx's GPU (a source may be ctx itself). The work
+ * (two kernel launches, the grids sized from out->cap, at least one block so
+ * that count is written when cap == 0) is enqueued on `stream` (NULL: ctx's
+ * own), after the work already there, and the call MAY RETURN BEFORE IT RAN. It
+ * makes no host round trip: every offset[] is read on the device only.
+ * Ordering against the vp_tx_build calls that filled the lists is the
+ * caller's (the same stream, or events). It needs no workspace. It ends the
+ * resident kernel of ctx and of every source context, and after a multi-GPU
+ * attach it is local to the rank.
+ * VP_EINVAL: a NULL ctx, srcs, out or count; n_srcs == 0 or above
+ * VP_TX_MERGE_MAX; per source everything vp_tx_rebatch rejects (a NULL batch,
+ * lists or offset; a NULL idx with lists->cap > 0; port >= n_devices; a
+ * context with more than VP_MAX_DEVICES devices; a slot below 64 or not a
+ * multiple of 16; frames not 16-byte aligned; a NULL batch->frames or
+ * batch->len with n > 0, lists->cap > 0 and out->cap > 0; its slot array
+ * overlapping out->frames); in_port > 0xFFFF; a source context that is NULL or
+ * on another GPU; out->slot below 64 or not a multiple of 16; out->frames not
+ * 16-byte aligned; a NULL out->frames, len, src or which with out->cap > 0. */
+int vp_tx_merge(vp_ctx *ctx, const vp_tx_source *srcs, uint32_t n_srcs,
+                const vp_tx_merged *out, void *stream);
+
 /* Host memory the GPU may read and write frames in directly: a DPDK mbuf
  * pool's memory (the hugepages rte_pktmbuf_pool_create, nf.c:235-242, lays
  * the mbufs out in), registered once after the pool is created. Page-locked

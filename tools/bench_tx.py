@@ -2,7 +2,7 @@
 beside the bytes the algorithm has to move. Run by hand; not part of bench.py.
 
   python3 tools/bench_tx.py [--packets 16777216] [--reps 20] [--step-ms MS] [--pack]
-                             [--rebatch]
+                             [--rebatch] [--merge]
 
 Three cases:
   two-port         vignat's headline outputs: every packet from port 0 (one
@@ -30,6 +30,16 @@ len[], now[] and src[] is timed the same way, beside a plain device-to-device
 copy of the same number of slot bytes on the same stream. Algorithmic bytes of
 a rebatch: each listed slot read and written, 14 B per entry read (idx, len,
 now) and 14 B written (len, now, src).
+--merge: vp_tx_merge of (a) the two lists of the two-port
+case and (b) three lists (ports 1 to 3) of the four-port flood pattern, keyed
+by packet index (key NULL), into 64-byte slots with len[], now[], in_dev[],
+key[], src[] and which[]; beside it, in the same run and on the same stream,
+vp_tx_rebatch of a single list holding the same number of entries (the same
+stretch of idx[] read as one list) and a plain device-to-device copy of the
+same slot bytes. Algorithmic bytes of a merge: each listed slot read and
+written; per entry idx read (4), in_dev, key, src and which written (11),
+which and src read back (5), len and now read and written (20): 40 B; the
+binary searches' reads come on top and are not counted.
 --step-ms: the headline step (bench.py's ms_per_step of the same session);
 every time is then also given as a fraction of it.
 """
@@ -214,6 +224,66 @@ def measure_rebatch(nf, nd, lens, idx, off, total, port, reps, dev):
             if med_cp else None}
 
 
+def measure_merge(nf, nd, lens, idx, off, total, ports, reps, dev):
+    """vp_tx_merge of the lists `ports` of one batch (64-byte slots, keyed by
+    packet index), vp_tx_rebatch of the same stretch of idx[] as one list, and
+    a plain copy of the same slot bytes, all on one stream."""
+    n, slot = lens.numel(), 64
+    frames = torch.randint(0, 256, (n * slot,), dtype=torch.uint8, device=dev)
+    now = torch.arange(n, dtype=torch.int64, device=dev) + T.NOW0
+    bounds = off.cpu().numpy().view(np.uint32)
+    assert list(ports) == list(range(ports[0], ports[-1] + 1))
+    lo, hi = int(bounds[ports[0]]), int(bounds[ports[-1] + 1])
+    count = hi - lo
+    cap = max(count, 1)
+    o_f = torch.zeros(cap * slot, dtype=torch.uint8, device=dev)
+    o_l = torch.zeros(cap, dtype=torch.int16, device=dev)
+    o_n = torch.zeros(cap, dtype=torch.int64, device=dev)
+    o_i = torch.zeros(cap, dtype=torch.int16, device=dev)
+    o_k = torch.zeros(cap, dtype=torch.int32, device=dev)
+    o_s = torch.zeros(cap, dtype=torch.int32, device=dev)
+    o_w = torch.zeros(cap, dtype=torch.uint8, device=dev)
+    cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+    # the same entries as one list: the stretch of idx[] the ports' lists fill
+    one = idx[lo:hi] if count else None
+    one_off = torch.tensor([0] + [count] * nd, dtype=torch.int32, device=dev)
+    src = torch.randint(0, 256, (cap * slot,), dtype=torch.uint8, device=dev)
+    dst = torch.empty_like(src)
+    s = torch.cuda.Stream(device=dev)
+    lists = idx[:total] if total else None
+    sources = [(nf, frames, slot, lens, lists, off, p, k, None, now, 0, 0)
+               for k, p in enumerate(ports)]
+    torch.cuda.synchronize()  # (torch filled the buffers on its own stream)
+    ms = timed(s, reps, lambda: nf.tx_merge(sources, o_f, slot, o_l, cnt, o_s, o_w, out_now=o_n,
+                                            out_in_dev=o_i, out_key=o_k, stream=s))
+    assert int(cnt.cpu()[0]) == count
+    # a sanity check of the run, not the test (tests/test_txmerge_gpu.py): the
+    # keys ascend, and the first entries hold the slots src[] names
+    k = min(count, 4096)
+    if k:
+        assert bool((o_k[1:count] >= o_k[:count - 1]).all())
+        i = o_s[:k].long()
+        assert bool((o_k[:k].long() == i).all())
+        assert bool((o_f[:k * slot].view(k, slot) == frames.view(n, slot)[i]).all())
+        assert bool((o_l[:k] == lens[i]).all()) and bool((o_n[:k] == now[i]).all())
+    ms_rb = timed(s, reps, lambda: nf.tx_rebatch(frames, slot, lens, one, one_off, 0, o_f, slot,
+                                                 o_l, cnt, out_now=o_n, out_src=o_s, now=now,
+                                                 stream=s))
+    ms_cp = timed(s, reps, lambda: dst.copy_(src))
+    alg = 2 * count * slot + 40 * count
+    med, med_rb, med_cp = (x[len(x) // 2] for x in (ms, ms_rb, ms_cp))
+    return {"ports": list(ports), "entries_merged": count, "slot_bytes": count * slot,
+            "merge_ms_median": round(med, 4), "merge_ms_min": round(ms[0], 4),
+            "merge_ms_max": round(ms[-1], 4), "rebatch_ms_median": round(med_rb, 4),
+            "rebatch_ms_min": round(ms_rb[0], 4), "rebatch_ms_max": round(ms_rb[-1], 4),
+            "copy_ms_median": round(med_cp, 4), "copy_ms_min": round(ms_cp[0], 4),
+            "copy_ms_max": round(ms_cp[-1], 4),
+            "merge_over_rebatch": round(med / med_rb, 3) if med_rb else None,
+            "merge_over_copy": round(med / med_cp, 3) if med_cp else None,
+            "merge_alg_bytes": alg,
+            "bytes_over_copy_bytes": round(alg / (2 * count * slot), 3) if count else None}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--packets", type=int, default=1 << 24)
@@ -224,6 +294,9 @@ def main():
                     help="also time vp_tx_pack over each case's lists, beside a plain copy")
     ap.add_argument("--rebatch", action="store_true",
                     help="also time vp_tx_rebatch of port 1's list, beside a plain copy")
+    ap.add_argument("--merge", action="store_true",
+                    help="also time vp_tx_merge of the two-port case's two lists and of three "
+                         "lists of the flood pattern, beside vp_tx_rebatch and a plain copy")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     n = args.packets
@@ -261,6 +334,16 @@ def main():
             if args.step_ms:
                 p["headline_step_ms"] = args.step_ms
                 p["fraction_of_step"] = round(p["rebatch_ms_median"] / args.step_ms, 4)
+            print(json.dumps(p), flush=True)
+        if args.merge and name != "two-port-drop16":
+            idx, off, total = lists
+            ports = [0, 1] if nd == 2 else [1, 2, 3]
+            p = {"case": name + "-merge", "packets": n, "n_devices": nd, "entries": total,
+                 "reps": args.reps,
+                 **measure_merge(nf, nd, ln, idx, off, total, ports, args.reps, dev)}
+            if args.step_ms:
+                p["headline_step_ms"] = args.step_ms
+                p["fraction_of_step"] = round(p["merge_ms_median"] / args.step_ms, 4)
             print(json.dumps(p), flush=True)
         del lists
         torch.cuda.empty_cache()

@@ -79,6 +79,23 @@ class TxNextC(C.Structure):
                 ("count", C.c_void_p)]
 
 
+TX_MERGE_MAX = 8  # VP_TX_MERGE_MAX
+
+
+class TxSourceC(C.Structure):
+    """vp_tx_source (include/vigpath.h): one list of a vp_tx_merge call."""
+    _fields_ = [("ctx", C.c_void_p), ("batch", C.c_void_p), ("lists", C.c_void_p),
+                ("port", C.c_uint32), ("in_port", C.c_uint32), ("key", C.c_void_p)]
+
+
+class TxMergedC(C.Structure):
+    """vp_tx_merged (include/vigpath.h): device pointers."""
+    _fields_ = [("frames", C.c_void_p), ("slot", C.c_uint32), ("cap", C.c_uint32),
+                ("len", C.c_void_p), ("now", C.c_void_p), ("in_dev", C.c_void_p),
+                ("key", C.c_void_p), ("src", C.c_void_p), ("which", C.c_void_p),
+                ("count", C.c_void_p)]
+
+
 # packets per block of vp_tx_build's kernels (vp_tx.hip kTxBlockPackets)
 TX_BLOCK_PACKETS = 2048
 
@@ -171,7 +188,8 @@ EXPORTS = ["vp_nat_create", "vp_bridge_create", "vp_lb_create", "vp_fw_create",
            "vp_last_error", "vp_register_host", "vp_unregister_host", "vp_process_mbufs",
            "vp_last_stage_ms", "vp_stage_ms", "vp_comm_abort", "vp_probe_slots",
            "vp_probe_slots_w", "vp_process_one", "vp_last_kernel", "vp_serve_stats_get",
-           "vp_serve_expiry_stats_get", "vp_tx_build", "vp_tx_pack", "vp_tx_rebatch"]
+           "vp_serve_expiry_stats_get", "vp_tx_build", "vp_tx_pack", "vp_tx_rebatch",
+           "vp_tx_merge"]
 
 _libs = {}
 
@@ -281,6 +299,9 @@ def lib(path: str | None = None):
     L.vp_tx_rebatch.argtypes = [C.c_void_p, C.POINTER(DevBatchC), C.POINTER(TxListsC),
                                 C.c_uint32, C.POINTER(TxNextC), C.c_void_p]
     L.vp_tx_rebatch.restype = C.c_int
+    L.vp_tx_merge.argtypes = [C.c_void_p, C.POINTER(TxSourceC), C.c_uint32,
+                              C.POINTER(TxMergedC), C.c_void_p]
+    L.vp_tx_merge.restype = C.c_int
     L.vp_last_error.argtypes = []
     L.vp_last_error.restype = C.c_char_p
     _libs[path] = L

@@ -2,23 +2,42 @@
 cable between each pair (firewall -> NAT, bridge -> policer, ...), as contexts
 whose batches stay in device memory. A link hands one port's transmit list of
 a stage to a later stage as that stage's input batch: vp_tx_build, then
-vp_tx_rebatch, then vp_process_device. No frame byte crosses
-to the host.
+vp_tx_rebatch, then vp_process_device. Several links into one
+stage are merged by the packets' positions in the chain's input: vp_tx_merge
+(DESIGN.md §5.8). No frame byte crosses to the host.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
+from . import TX_MERGE_MAX
+
 
 class Chain:
     """`stages`: NF objects (vigor_amd.Nat, Fw, ...) on one GPU. `links`:
     (s, out_port, t, in_port) tuples with t > s: what stage s sends to its
     port out_port arrives at stage t on port in_port. Every stage but 0 has
-    exactly one inbound link (merging two lists into one stage is not
-    supported); anything else raises ValueError. Packets a stage sends to a
-    port without a link stay in that stage's result with their out port: they
-    have left the chain."""
+    one to TX_MERGE_MAX inbound links; anything else raises ValueError.
+    Packets a stage sends to a port without a link stay in that stage's
+    result with their out port: they have left the chain.
+
+    A stage with several inbound links sees their packets merged by origin
+    (each packet's index in the chain's input), as cables into one box would
+    deliver them: an NF's state depends on the order and the times of its
+    packets. The tie rule: copies of one input packet (floods, or a packet
+    that reaches the stage through two branches) arrive in the order of the
+    stage's inbound links in `links`. That is the order in which boxes pushing
+    each packet through all its cables before the next would deliver them
+    whenever `links` is written in depth-first order -- every link of a
+    stage's subtree before the stage's next link -- and only then: the limit
+    of the rule. An out port that feeds a stage with several inbound links
+    carries that one link: a port named by another link as well raises
+    ValueError.
+
+    inbound[t]: the (s, out_port, in_port) of stage t's first inbound link in
+    `links` order (None for stage 0); inbounds[t]: all of them, in `links`
+    order."""
 
     def __init__(self, stages, links):
         self.stages = list(stages)
@@ -26,6 +45,7 @@ class Chain:
             raise ValueError("a chain needs a stage")
         k = len(self.stages)
         self.inbound = [None] * k
+        self.inbounds = [[] for _ in range(k)]
         self.outbound = [[] for _ in range(k)]
         for link in links:
             s, out_port, t, in_port = (int(x) for x in link)
@@ -37,20 +57,28 @@ class Chain:
                 raise ValueError("link %r leaves from a port stage %d does not have" % (link, s))
             if not 0 <= in_port <= 0xFFFF:
                 raise ValueError("link %r arrives on a port beyond 16 bits" % (link,))
-            if self.inbound[t] is not None:
-                raise ValueError("stage %d has two inbound links" % t)
-            self.inbound[t] = (s, out_port, in_port)
+            if len(self.inbounds[t]) == TX_MERGE_MAX:
+                raise ValueError("stage %d has more than %d inbound links" % (t, TX_MERGE_MAX))
+            if self.inbound[t] is None:
+                self.inbound[t] = (s, out_port, in_port)
+            self.inbounds[t].append((s, out_port, in_port))
             self.outbound[s].append((out_port, t))
         for t in range(1, k):
             if self.inbound[t] is None:
                 raise ValueError("stage %d has no inbound link" % t)
+            if len(self.inbounds[t]) > 1:
+                for s, out_port, _ in self.inbounds[t]:
+                    if [p for p, _ in self.outbound[s]].count(out_port) > 1:
+                        raise ValueError("port %d of stage %d feeds stage %d, which merges, and "
+                                         "has another link" % (out_port, s, t))
         self.stream = None
         self._lists = [None] * k  # per stage: (idx, offset)
         self._bufs = [None] * k   # per stage >= 1: its input batch's buffers
 
-    def _grown(self, t, n, slot, dev):
+    def _grown(self, t, n, slot, dev, merged=False):
         """Stage t's input buffers for n packets: kept from call to call,
-        replaced by larger ones on demand."""
+        replaced by larger ones on demand. merged: with the per-packet port,
+        key and source number of vp_tx_merge."""
         b = self._bufs[t]
         if b is None or b["cap"] < n or b["slot"] != slot:
             cap = max(n, 2 * b["cap"] if b and b["slot"] == slot else 0, 64)
@@ -61,6 +89,10 @@ class Chain:
                  "src": torch.empty(cap, dtype=torch.int32, device=dev),
                  "out": torch.empty(cap, dtype=torch.int16, device=dev),
                  "count": torch.zeros(1, dtype=torch.int32, device=dev)}
+            if merged:
+                b["in"] = torch.empty(cap, dtype=torch.int16, device=dev)
+                b["key"] = torch.empty(cap, dtype=torch.int32, device=dev)
+                b["which"] = torch.empty(cap, dtype=torch.uint8, device=dev)
             self._bufs[t] = b
         return b
 
@@ -72,16 +104,21 @@ class Chain:
         device-to-host read of offset[] to size the next batches (the one host
         synchronisation per stage), tx_rebatch of each linked port into buffers
         the chain owns, and process_device of the target stage with every
-        packet on the link's in_port and the gathered per-packet times. All of
-        it is enqueued on one stream of the chain's, which is waited for once
-        more before the call returns.
+        packet on the link's in_port and the gathered per-packet times. A
+        stage with several inbound links gets its input when it is reached,
+        after every earlier stage ran: one tx_merge over its links' lists (in
+        `links` order, each keyed by its source stage's origins), sized from
+        the offset[] reads already made, then process_device with the merged
+        per-packet ports and times. All of it is enqueued on one stream of the
+        chain's, which is waited for once more before the call returns.
 
         Returns one dict per stage: n (packets the stage received), frames
         (n * slot bytes, as the stage left them), lens, out (its out ports)
         and origin (int64: each packet's index in the caller's batch, composed
-        from the links' src arrays). The tensors of the stages after 0 are the
-        chain's own buffers: valid until the next run. State persists across
-        calls in the stages' contexts."""
+        from the links' src arrays; at a merged stage the merged keys), and at
+        a merged stage in_dev (the per-packet in port). The tensors of the
+        stages after 0 are the chain's own buffers: valid until the next run.
+        State persists across calls in the stages' contexts."""
         dev = frames.device
         if self.stream is None:
             self.stream = torch.cuda.Stream(device=dev)
@@ -99,18 +136,25 @@ class Chain:
                       "origin": torch.arange(n0, dtype=torch.int64, device=dev)}
             time = [(now, now0, now_step)] + [None] * (k - 1)
             ports = [in_dev] + [None] * (k - 1)
+            offsets = [None] * k  # per stage with built lists: offset[] on the host
+            merges = [len(x) > 1 for x in self.inbounds]
             for s in range(k):
+                if merges[s]:
+                    res[s] = self._merge(s, res, offsets, time, ports, slot, dev)
                 r = res[s]
                 if not self.outbound[s] or r["n"] == 0:
                     for _, t in self.outbound[s]:
-                        res[t] = self._empty(slot, dev)
+                        if not merges[t]:
+                            res[t] = self._empty(slot, dev)
                     continue
                 nf = self.stages[s]
                 nd = nf.cfg.n_devices
-                offset = self._build(s, nf, nd, r, ports[s], dev)
+                offset = offsets[s] = self._build(s, nf, nd, r, ports[s], dev)
                 idx = self._lists[s][0]
                 t_now, t_now0, t_step = time[s]
                 for out_port, t in self.outbound[s]:
+                    if merges[t]:
+                        continue  # (assembled when stage t is reached)
                     cnt = int(offset[out_port + 1]) - int(offset[out_port])
                     if cnt == 0:
                         res[t] = self._empty(slot, dev)
@@ -131,6 +175,43 @@ class Chain:
                               "origin": r["origin"][b["src"][:cnt].long()]}
         S.synchronize()
         return res
+
+    def _merge(self, t, res, offsets, time, ports, slot, dev):
+        """Stage t's input from its several inbound links, and its run: one
+        tx_merge over the links' lists in `links` order, each source keyed by
+        its stage's origins (stage 0's are the packet indices: no key array),
+        then process_device with the merged per-packet ports and times."""
+        sources, cnt = [], 0
+        for s, out_port, in_port in self.inbounds[t]:
+            r = res[s]
+            if r["n"] == 0 or offsets[s] is None:
+                continue
+            c = int(offsets[s][out_port + 1]) - int(offsets[s][out_port])
+            if c == 0:
+                continue
+            cnt += c
+            if s and "key" not in r:
+                r["key"] = r["origin"].to(torch.int32)
+            idx, off_t = self._lists[s]
+            sources.append((self.stages[s], r["frames"], slot, r["lens"], idx, off_t, out_port,
+                            in_port, r["key"] if s else None) + tuple(time[s]))
+        if cnt == 0:
+            res_t = self._empty(slot, dev)
+            res_t["in_dev"] = res_t["lens"].clone()
+            return res_t
+        b = self._grown(t, cnt, slot, dev, merged=True)
+        S = self.stream
+        self.stages[t].tx_merge(sources, b["frames"][:cnt * slot], slot, b["lens"][:cnt],
+                                b["count"], b["src"][:cnt], b["which"][:cnt],
+                                out_now=b["now"][:cnt], out_in_dev=b["in"][:cnt],
+                                out_key=b["key"][:cnt], stream=S)
+        self.stages[t].process_device(b["frames"][:cnt * slot], b["lens"][:cnt], b["in"][:cnt],
+                                      b["out"][:cnt], slot, now=b["now"][:cnt], stream=S)
+        time[t] = (b["now"][:cnt], 0, 0)
+        ports[t] = b["in"][:cnt]
+        return {"n": cnt, "frames": b["frames"][:cnt * slot], "lens": b["lens"][:cnt],
+                "out": b["out"][:cnt], "origin": b["key"][:cnt].long(),
+                "in_dev": b["in"][:cnt], "key": b["key"][:cnt]}
 
     @staticmethod
     def _empty(slot, dev):

@@ -101,6 +101,7 @@ hipError_t preload_mbuf(hipStream_t s);
 hipError_t preload_tx(hipStream_t s);
 hipError_t preload_txpack(hipStream_t s);
 hipError_t preload_txbatch(hipStream_t s);
+hipError_t preload_txmerge(hipStream_t s);
 
 // Owner-mode phase A stages (vp_last_stage_ms).
 constexpr int kStages = 8;

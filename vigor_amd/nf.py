@@ -14,7 +14,8 @@ import numpy as np
 
 from . import (BridgeConfigC, DevBatchC, FwConfigC, LbConfigC, MbufBatchC,
                NatConfigC, PolConfigC, ServeExpiryStatsC, ServeStatsC, TableStatsC,
-               TxFramesC, TxListsC, TxNextC, TxStatsC, _check, lib)
+               TX_MERGE_MAX, TxFramesC, TxListsC, TxMergedC, TxNextC, TxSourceC, TxStatsC,
+               _check, lib)
 
 
 def _dptr(t):
@@ -226,6 +227,71 @@ class NfBase:
         s = C.c_void_p(stream.cuda_stream) if stream is not None else None
         self._ck(self.L.vp_tx_rebatch(self.h, C.byref(b), C.byref(lists), port, C.byref(out), s),
                  "vp_tx_rebatch")
+
+    def tx_merge(self, sources, out_frames, out_slot, out_lens, count, out_src, out_which,
+                 out_now=None, out_in_dev=None, out_key=None, stream=None):
+        """vp_tx_merge: several lists of tx_build's as this NF's device batch,
+        merged by a 32-bit key per packet (stable: equal keys in the order of
+        `sources`, inside a source in list order). sources: 1 to TX_MERGE_MAX
+        tuples (nf, frames, slot, lens, idx, offset, port, in_port, key, now,
+        now0, now_step), the tail from `key` on optional (None, None, 0, 0):
+        nf the NF whose tx_build wrote idx / offset over that batch, frames /
+        slot / lens / now / now0 / now_step the batch as for tx_rebatch, port
+        the list, in_port the port its packets arrive on here, key None (the
+        packet's index) or a 32-bit CUDA tensor of n that does not decrease
+        along the list. out_lens: 16-bit CUDA tensor whose length is the
+        capacity in packets (None: 0); out_frames: uint8 CUDA tensor of
+        capacity * out_slot bytes; out_src (32-bit) and out_which (8-bit) are
+        needed with a capacity; out_now (64-bit), out_in_dev (16-bit) and
+        out_key (32-bit) may be None; count: 32-bit CUDA tensor of one word,
+        the lists' true total afterwards. Enqueued on `stream` (this
+        context's own for None) and not waited for."""
+        sources = [tuple(s) + (None, None, 0, 0)[len(tuple(s)) - 8:] for s in sources]
+        assert 1 <= len(sources) <= TX_MERGE_MAX
+        cap = out_lens.numel() if out_lens is not None else 0
+        assert count.is_cuda and count.element_size() == 4 and count.numel() >= 1
+        if cap:
+            assert out_lens.is_cuda and out_lens.element_size() == 2
+            assert out_frames.is_cuda and out_frames.element_size() == 1
+            assert out_frames.numel() == cap * out_slot
+            assert out_src.is_cuda and out_src.element_size() == 4 and out_src.numel() >= cap
+            assert out_which.is_cuda and out_which.element_size() == 1
+            assert out_which.numel() >= cap
+        for t, width in ((out_now, 8), (out_in_dev, 2), (out_key, 4)):
+            if t is not None:
+                assert t.is_cuda and t.element_size() == width and t.numel() >= cap
+        arr = (TxSourceC * len(sources))()
+        keep = []  # (the structs the array points to)
+        for a, (nf, frames, slot, lens, idx, offset, port, in_port, key, now, now0,
+                now_step) in zip(arr, sources):
+            n = lens.numel()
+            assert frames.numel() == n * slot
+            if idx is not None:
+                assert idx.is_cuda and idx.element_size() == 4
+            assert offset.is_cuda and offset.element_size() == 4
+            if now is not None:
+                assert now.is_cuda and now.element_size() == 8 and now.numel() == n
+            if key is not None:
+                assert key.is_cuda and key.element_size() == 4 and key.numel() == n
+            b = DevBatchC(frames=_dptr(frames) if n else None, slot=slot, n=n,
+                          len=_dptr(lens) if n else None,
+                          now=_dptr(now) if n else None, now0=now0, now_step=now_step)
+            lcap = idx.numel() if idx is not None else 0
+            lists = TxListsC(idx=_dptr(idx) if lcap else None, cap=lcap,
+                             offset=offset.data_ptr(), stats=None)
+            keep += [b, lists]
+            a.ctx, a.batch, a.lists = nf.h, C.addressof(b), C.addressof(lists)
+            a.port, a.in_port = port, in_port
+            a.key = _dptr(key) if n else None
+        out = TxMergedC(frames=_dptr(out_frames) if cap else None, slot=out_slot, cap=cap,
+                        len=_dptr(out_lens) if cap else None,
+                        now=_dptr(out_now) if cap else None,
+                        in_dev=_dptr(out_in_dev) if cap else None,
+                        key=_dptr(out_key) if cap else None,
+                        src=_dptr(out_src) if cap else None,
+                        which=_dptr(out_which) if cap else None, count=count.data_ptr())
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._ck(self.L.vp_tx_merge(self.h, arr, len(sources), C.byref(out), s), "vp_tx_merge")
 
     def sync_state(self):
         """Multi-GPU: merge the ranks' timestamps (collective)."""
