@@ -422,6 +422,78 @@ typedef struct vp_tx_merged {
 int vp_tx_merge(vp_ctx *ctx, const vp_tx_source *srcs, uint32_t n_srcs,
                 const vp_tx_merged *out, void *stream);
 
+/* ------------------------------------------------------------ receive --
+ * The way back in: frames that arrive as one packed run of bytes -- a capture,
+ * a buffer a NIC or another GPU wrote, the stream the pack call above made on
+ * another device -- as a device batch in equal slots. */
+
+typedef struct vp_rx_stream {
+  const uint8_t  *data;    /* device, 16-byte aligned; may be NULL iff bytes == 0 */
+  uint64_t        bytes;   /* bytes of data that may be read */
+  uint32_t        n;       /* entries (frames) in the stream */
+  const uint64_t *pos;     /* device, n entries, or NULL: byte offset of entry e's frame */
+  const uint32_t *sel;     /* device, n entries, or NULL: m(e) = sel[e]; NULL: m(e) = e */
+  uint32_t        meta_n;  /* entries of len[] and now[] */
+  const uint16_t *len;     /* device, meta_n entries */
+  const int64_t  *now;     /* device, meta_n entries, or NULL */
+  int64_t         now0, now_step;
+} vp_rx_stream;
+
+/* Unpack a stream of frames into consecutive slots: the inverse of the pack
+ * call above, filling the struct the rebatch call fills, so whatever consumes
+ * a rebatched batch consumes an unpacked one. Reads data, pos, sel, len and
+ * now (device memory); writes nothing but out's buffers. For entry e < n, with
+ *   m      = sel[e], or e when sel is NULL     its index into len[] and now[]
+ *   L      = len[m] when m < meta_n, else 0    (nothing is read through an
+ *                                              m >= meta_n)
+ *   ext(e) = (L + 15) & ~15
+ *   p(e)   = pos[e], or, when pos is NULL, the sum of ext(k) over k < e (64
+ *            bits): a self-describing stream, the frames back to back at
+ *            their own padded lengths
+ *   r      = min(L, out->slot)
+ * entry e is readable iff m < meta_n, p(e) % 16 == 0 and
+ * p(e) + ((r + 15) & ~15) <= bytes, the sum taken without wrapping (a p near
+ * 2^64 is not readable). The call writes *count = n, also when n > out->cap,
+ * and for k = e < min(n, out->cap), readable:
+ *   frames[k*slot .. k*slot + r)         data[p .. p + r)
+ *   frames[k*slot + r .. (k+1)*slot)     zero; the bytes of the last 16-byte
+ *                                        unit past L are cleared, never
+ *                                        trusted from the stream
+ *   len[k] = L                           unchanged, not clipped to a slot
+ *   now[k] = now[m], or now0 + m * now_step (64 bits) when now is NULL
+ *   src[k] = m
+ * and not readable: the slot is zero, len[k] = 0, now[k] = 0, src[k] = m, and
+ * nothing is read from data for it. Nothing at or beyond entry min(n,
+ * out->cap) of any buffer is written. The result is deterministic: the same
+ * inputs give the same bytes. The output is a valid vp_dev_batch for any
+ * context, with in_dev NULL and an in_port of the caller's choosing.
+ * Port d of a packed batch comes back with, lo = offset[d], hi = offset[d + 1]
+ * of its lists: pos = the packed pos + lo, sel = the lists' idx + lo, n = hi -
+ * lo, meta_n = the batch's n, len and the time the batch's, data and bytes the
+ * packed stream. Without pos the entries' lengths must be their own (sel, or
+ * a len[] already in stream order) and data must start at the first frame
+ * (the packed data + port_off[d]); that form matches a packed stream only
+ * where every len is <= the source slot: pack pads min(len, slot), a
+ * self-describing stream pads len. For the same reason, with pos, a len beyond
+ * the source slot unpacked into a wider slot takes the bytes behind its frame
+ * (the next frames') for its own up to min(len, out->slot): the stream does
+ * not say where a clipped frame ends.
+ * The work is enqueued on `stream` (NULL: the context's own), after the work
+ * already there, and the call MAY RETURN BEFORE IT RAN: one kernel launch with
+ * pos, three without (the padded lengths summed per wave, scanned by one
+ * block, then the scatter), the grids sized from min(n, out->cap), at least
+ * one block so that count is written. It makes no host round trip. The
+ * library orders its own workspace (the sums) between streams. Like
+ * vp_tx_build it ends the NF's resident kernel, and after a multi-GPU attach
+ * it is local to the rank. The context supplies only the GPU and the default
+ * stream: its n_devices plays no part.
+ * VP_EINVAL: a NULL ctx, in, out or count; a NULL data with bytes > 0; data or
+ * out->frames not 16-byte aligned; a NULL len with meta_n > 0; out->slot below
+ * 64 or not a multiple of 16; a NULL out->frames or out->len with out->cap >
+ * 0; the byte ranges [data, + bytes) and [out->frames, + cap * slot)
+ * overlapping. n == 0: count 0, nothing else written. */
+int vp_rx_unpack(vp_ctx *ctx, const vp_rx_stream *in, const vp_tx_next *out, void *stream);
+
 /* Host memory the GPU may read and write frames in directly: a DPDK mbuf
  * pool's memory (the hugepages rte_pktmbuf_pool_create, nf.c:235-242, lays
  * the mbufs out in), registered once after the pool is created. Page-locked

@@ -2,7 +2,7 @@
 beside the bytes the algorithm has to move. Run by hand; not part of bench.py.
 
   python3 tools/bench_tx.py [--packets 16777216] [--reps 20] [--step-ms MS] [--pack]
-                             [--rebatch] [--merge]
+                             [--rebatch] [--merge] [--unpack]
 
 Three cases:
   two-port         vignat's headline outputs: every packet from port 0 (one
@@ -40,6 +40,15 @@ same slot bytes. Algorithmic bytes of a merge: each listed slot read and
 written; per entry idx read (4), in_dev, key, src and which written (11),
 which and src read back (5), len and now read and written (20): 40 B; the
 binary searches' reads come on top and are not counted.
+--unpack: after a case's lists are built and packed (vp_tx_pack with pos, 64-
+byte slots of random bytes), vp_rx_unpack of port 1's stream
+into 64-byte slots with len[], now[] and src[] is timed the same way, once with
+pos and sel and once without pos from the port's first byte (sizes and scan
+launches included); beside them, in the same run and on the same stream,
+vp_tx_rebatch of the same entries and a plain device-to-device copy of the
+same slot bytes. Algorithmic bytes of an unpack: the port's stream read, each
+slot written, 22 B per entry read (sel, len, now, pos) and 14 B written (len,
+now, src); without pos the sizes pass reads sel and len once more.
 --step-ms: the headline step (bench.py's ms_per_step of the same session);
 every time is then also given as a fraction of it.
 """
@@ -284,6 +293,90 @@ def measure_merge(nf, nd, lens, idx, off, total, ports, reps, dev):
             "bytes_over_copy_bytes": round(alg / (2 * count * slot), 3) if count else None}
 
 
+def measure_unpack(nf, nd, lens, idx, off, total, port, reps, dev):
+    """vp_rx_unpack of list `port`'s packed stream (vp_tx_pack with pos over
+    64-byte slots) into 64-byte slots with len[], now[] and src[]: with pos and
+    sel, and without pos from the port's first byte; beside them, on the same
+    stream, vp_tx_rebatch of the same entries and a plain copy of the same slot
+    bytes."""
+    n, slot = lens.numel(), 64
+    frames = torch.randint(0, 256, (n * slot,), dtype=torch.uint8, device=dev)
+    now = torch.arange(n, dtype=torch.int64, device=dev) + T.NOW0
+    bounds = off.cpu().numpy().view(np.uint32)
+    lo, count = int(bounds[port]), int(bounds[port + 1] - bounds[port])
+    idx = idx[:total] if total else None
+    po = torch.zeros(nd + 1, dtype=torch.int64, device=dev)
+    pos = torch.zeros(max(total, 1), dtype=torch.int64, device=dev)
+    data = torch.zeros(max(total, 1) * slot, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()  # (torch filled the buffers on its own stream)
+    nf.tx_pack(frames, slot, lens, idx, off, data, po, pos[:total] if total else None)
+    torch.cuda.synchronize()
+    p_off = po.cpu().numpy().view(np.uint64)
+    payload, a, b = int(p_off[nd]), int(p_off[port]), int(p_off[port + 1])
+    assert payload <= data.numel() and int(lens.max()) <= slot
+    cap = max(count, 1)
+    o_f = torch.zeros(cap * slot, dtype=torch.uint8, device=dev)
+    o_l = torch.zeros(cap, dtype=torch.int16, device=dev)
+    o_n = torch.zeros(cap, dtype=torch.int64, device=dev)
+    o_s = torch.zeros(cap, dtype=torch.int32, device=dev)
+    cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+    src = torch.randint(0, 256, (cap * slot,), dtype=torch.uint8, device=dev)
+    dst = torch.empty_like(src)
+    sel = idx[lo:lo + count] if count else None
+    s = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()
+
+    def verify():
+        # the first entries against a gather made with torch (a sanity check
+        # of the run, not the test: tests/test_rxunpack_gpu.py)
+        assert int(cnt.cpu()[0]) == count
+        k = min(count, 4096)
+        if k:
+            i = sel[:k].long()
+            want = frames.view(n, slot)[i].clone()
+            want[torch.arange(slot, device=dev)[None, :] >= lens[i].long()[:, None]] = 0
+            assert bool((o_f[:k * slot].view(k, slot) == want).all())
+            assert bool((o_l[:k] == lens[i]).all()) and bool((o_n[:k] == now[i]).all())
+            assert bool((o_s[:k].long() == i).all())
+        o_f.zero_()
+        torch.cuda.synchronize()
+
+    d_all, d_port = data[:payload], data[a:b]
+    p_port = pos[lo:lo + count] if count else None
+    ms = timed(s, reps, lambda: nf.rx_unpack(
+        d_all, lens, o_f, slot, o_l, cnt, pos=p_port, sel=sel, out_now=o_n, out_src=o_s,
+        now=now, n=count, stream=s))
+    verify()
+    ms_np = timed(s, reps, lambda: nf.rx_unpack(
+        d_port, lens, o_f, slot, o_l, cnt, sel=sel, out_now=o_n, out_src=o_s, now=now,
+        n=count, stream=s))
+    verify()
+    ms_rb = timed(s, reps, lambda: nf.tx_rebatch(frames, slot, lens, idx, off, port, o_f, slot,
+                                                 o_l, cnt, out_now=o_n, out_src=o_s, now=now,
+                                                 stream=s))
+    ms_cp = timed(s, reps, lambda: dst.copy_(src))
+    # per entry: sel, len, now and pos read (22 B), len, now and src written (14 B)
+    alg = (b - a) + count * slot + 36 * count
+    med, med_np, med_rb, med_cp = (x[len(x) // 2] for x in (ms, ms_np, ms_rb, ms_cp))
+    return {"port": port, "list_entries": count, "slot_bytes": count * slot,
+            "stream_bytes": b - a,
+            "unpack_ms_median": round(med, 4), "unpack_ms_min": round(ms[0], 4),
+            "unpack_ms_max": round(ms[-1], 4),
+            "unpack_no_pos_ms_median": round(med_np, 4), "unpack_no_pos_ms_min": round(ms_np[0], 4),
+            "unpack_no_pos_ms_max": round(ms_np[-1], 4),
+            "rebatch_ms_median": round(med_rb, 4), "rebatch_ms_min": round(ms_rb[0], 4),
+            "rebatch_ms_max": round(ms_rb[-1], 4),
+            "copy_ms_median": round(med_cp, 4), "copy_ms_min": round(ms_cp[0], 4),
+            "copy_ms_max": round(ms_cp[-1], 4),
+            "unpack_over_copy": round(med / med_cp, 3) if med_cp else None,
+            "unpack_no_pos_over_copy": round(med_np / med_cp, 3) if med_cp else None,
+            "unpack_over_rebatch": round(med / med_rb, 3) if med_rb else None,
+            "unpack_no_pos_over_rebatch": round(med_np / med_rb, 3) if med_rb else None,
+            "rebatch_over_copy": round(med_rb / med_cp, 3) if med_cp else None,
+            "unpack_alg_bytes": alg,
+            "bytes_over_copy_bytes": round(alg / (2 * count * slot), 3) if count else None}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--packets", type=int, default=1 << 24)
@@ -297,6 +390,9 @@ def main():
     ap.add_argument("--merge", action="store_true",
                     help="also time vp_tx_merge of the two-port case's two lists and of three "
                          "lists of the flood pattern, beside vp_tx_rebatch and a plain copy")
+    ap.add_argument("--unpack", action="store_true",
+                    help="also time vp_rx_unpack of port 1's packed stream, with and without "
+                         "pos, beside vp_tx_rebatch and a plain copy")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     n = args.packets
@@ -344,6 +440,15 @@ def main():
             if args.step_ms:
                 p["headline_step_ms"] = args.step_ms
                 p["fraction_of_step"] = round(p["merge_ms_median"] / args.step_ms, 4)
+            print(json.dumps(p), flush=True)
+        if args.unpack:
+            idx, off, total = lists
+            p = {"case": name + "-unpack", "packets": n, "n_devices": nd, "entries": total,
+                 "reps": args.reps,
+                 **measure_unpack(nf, nd, ln, idx, off, total, 1, args.reps, dev)}
+            if args.step_ms:
+                p["headline_step_ms"] = args.step_ms
+                p["fraction_of_step"] = round(p["unpack_ms_median"] / args.step_ms, 4)
             print(json.dumps(p), flush=True)
         del lists
         torch.cuda.empty_cache()

@@ -79,6 +79,14 @@ class TxNextC(C.Structure):
                 ("count", C.c_void_p)]
 
 
+class RxStreamC(C.Structure):
+    """vp_rx_stream (include/vigpath.h): device pointers."""
+    _fields_ = [("data", C.c_void_p), ("bytes", C.c_uint64), ("n", C.c_uint32),
+                ("pos", C.c_void_p), ("sel", C.c_void_p), ("meta_n", C.c_uint32),
+                ("len", C.c_void_p), ("now", C.c_void_p), ("now0", C.c_int64),
+                ("now_step", C.c_int64)]
+
+
 TX_MERGE_MAX = 8  # VP_TX_MERGE_MAX
 
 
@@ -189,7 +197,7 @@ EXPORTS = ["vp_nat_create", "vp_bridge_create", "vp_lb_create", "vp_fw_create",
            "vp_last_stage_ms", "vp_stage_ms", "vp_comm_abort", "vp_probe_slots",
            "vp_probe_slots_w", "vp_process_one", "vp_last_kernel", "vp_serve_stats_get",
            "vp_serve_expiry_stats_get", "vp_tx_build", "vp_tx_pack", "vp_tx_rebatch",
-           "vp_tx_merge"]
+           "vp_tx_merge", "vp_rx_unpack"]
 
 _libs = {}
 
@@ -302,6 +310,9 @@ def lib(path: str | None = None):
     L.vp_tx_merge.argtypes = [C.c_void_p, C.POINTER(TxSourceC), C.c_uint32,
                               C.POINTER(TxMergedC), C.c_void_p]
     L.vp_tx_merge.restype = C.c_int
+    L.vp_rx_unpack.argtypes = [C.c_void_p, C.POINTER(RxStreamC), C.POINTER(TxNextC),
+                               C.c_void_p]
+    L.vp_rx_unpack.restype = C.c_int
     L.vp_last_error.argtypes = []
     L.vp_last_error.restype = C.c_char_p
     _libs[path] = L

@@ -5,6 +5,10 @@ a stage to a later stage as that stage's input batch: vp_tx_build, then
 vp_tx_rebatch, then vp_process_device. Several links into one
 stage are merged by the packets' positions in the chain's input: vp_tx_merge
 (DESIGN.md §5.8). No frame byte crosses to the host.
+
+With cable="stream" a link into a stage with one inbound link is rehearsed as a
+byte stream that could cross a device boundary: vp_tx_pack of the source
+stage's lists, then vp_rx_unpack of each linked port.
 """
 from __future__ import annotations
 
@@ -37,9 +41,20 @@ class Chain:
 
     inbound[t]: the (s, out_port, in_port) of stage t's first inbound link in
     `links` order (None for stage 0); inbounds[t]: all of them, in `links`
-    order."""
+    order.
 
-    def __init__(self, stages, links):
+    cable: "slots" (the default) hands a port's list over with tx_rebatch;
+    "stream" feeds every stage that has one inbound link through a packed
+    stream instead: one tx_pack of the source stage's lists, with pos, into a
+    buffer the chain owns, then one rx_unpack per linked port. The stream
+    carries min(len, slot) bytes of a frame, so the target sees zeros where the
+    source slot held bytes past the frame's length. Stages with several
+    inbound links keep tx_merge. Any other value raises ValueError."""
+
+    def __init__(self, stages, links, cable="slots"):
+        if cable not in ("slots", "stream"):
+            raise ValueError("cable %r is neither 'slots' nor 'stream'" % (cable,))
+        self.cable = cable
         self.stages = list(stages)
         if not self.stages:
             raise ValueError("a chain needs a stage")
@@ -74,6 +89,7 @@ class Chain:
         self.stream = None
         self._lists = [None] * k  # per stage: (idx, offset)
         self._bufs = [None] * k   # per stage >= 1: its input batch's buffers
+        self._packs = [None] * k  # per stage, cable "stream": (data, pos, port_off)
 
     def _grown(self, t, n, slot, dev, merged=False):
         """Stage t's input buffers for n packets: kept from call to call,
@@ -103,7 +119,8 @@ class Chain:
         in order that has a link: tx_build over its out ports, one small
         device-to-host read of offset[] to size the next batches (the one host
         synchronisation per stage), tx_rebatch of each linked port into buffers
-        the chain owns, and process_device of the target stage with every
+        the chain owns (cable "stream": one tx_pack of all the lists, then
+        rx_unpack of each linked port), and process_device of the target stage with every
         packet on the link's in_port and the gathered per-packet times. A
         stage with several inbound links gets its input when it is reached,
         after every earlier stage ran: one tx_merge over its links' lists (in
@@ -152,6 +169,7 @@ class Chain:
                 offset = offsets[s] = self._build(s, nf, nd, r, ports[s], dev)
                 idx = self._lists[s][0]
                 t_now, t_now0, t_step = time[s]
+                packed = None  # cable "stream": this stage's lists, packed once
                 for out_port, t in self.outbound[s]:
                     if merges[t]:
                         continue  # (assembled when stage t is reached)
@@ -160,10 +178,20 @@ class Chain:
                         res[t] = self._empty(slot, dev)
                         continue
                     b = self._grown(t, cnt, slot, dev)
-                    nf.tx_rebatch(r["frames"], slot, r["lens"], idx, self._lists[s][1], out_port,
-                                  b["frames"][:cnt * slot], slot, b["lens"][:cnt], b["count"],
-                                  out_now=b["now"][:cnt], out_src=b["src"][:cnt], now=t_now,
-                                  now0=t_now0, now_step=t_step, stream=S)
+                    if self.cable == "stream":
+                        if packed is None:
+                            packed = self._pack(s, nf, nd, r, int(offset[nd]), slot, dev)
+                        lo = int(offset[out_port])
+                        nf.rx_unpack(packed[0], r["lens"], b["frames"][:cnt * slot], slot,
+                                     b["lens"][:cnt], b["count"], pos=packed[1][lo:lo + cnt],
+                                     sel=idx[lo:lo + cnt], out_now=b["now"][:cnt],
+                                     out_src=b["src"][:cnt], now=t_now, now0=t_now0,
+                                     now_step=t_step, stream=S)
+                    else:
+                        nf.tx_rebatch(r["frames"], slot, r["lens"], idx, self._lists[s][1],
+                                      out_port, b["frames"][:cnt * slot], slot, b["lens"][:cnt],
+                                      b["count"], out_now=b["now"][:cnt], out_src=b["src"][:cnt],
+                                      now=t_now, now0=t_now0, now_step=t_step, stream=S)
                     in_port = self.inbound[t][2]
                     self.stages[t].process_device(b["frames"][:cnt * slot], b["lens"][:cnt],
                                                   in_port, b["out"][:cnt], slot,
@@ -212,6 +240,22 @@ class Chain:
         return {"n": cnt, "frames": b["frames"][:cnt * slot], "lens": b["lens"][:cnt],
                 "out": b["out"][:cnt], "origin": b["key"][:cnt].long(),
                 "in_dev": b["in"][:cnt], "key": b["key"][:cnt]}
+
+    def _pack(self, s, nf, nd, r, total, slot, dev):
+        """Stage s's lists as one packed stream (cable "stream"): tx_pack with
+        pos into a buffer of total * slot bytes, which holds every listed frame
+        at its padded length. Returns (data, pos); the buffers are kept from
+        call to call and replaced by larger ones on demand."""
+        idx, off_t = self._lists[s]
+        p = self._packs[s]
+        if p is None or p[0].numel() < total * slot or p[1].numel() < idx.numel():
+            p = self._packs[s] = (torch.empty(total * slot, dtype=torch.uint8, device=dev),
+                                  torch.empty(idx.numel(), dtype=torch.int64, device=dev),
+                                  torch.zeros(nd + 1, dtype=torch.int64, device=dev))
+        data = p[0][:total * slot]
+        nf.tx_pack(r["frames"], slot, r["lens"], idx, off_t, data, p[2], pos=p[1],
+                   stream=self.stream)
+        return data, p[1]
 
     @staticmethod
     def _empty(slot, dev):

@@ -102,6 +102,12 @@ hipError_t preload_tx(hipStream_t s);
 hipError_t preload_txpack(hipStream_t s);
 hipError_t preload_txbatch(hipStream_t s);
 hipError_t preload_txmerge(hipStream_t s);
+hipError_t preload_rxunpack(hipStream_t s);
+
+// vp_txpack.hip's one-block exclusive scan of m 64-bit sums in place, also
+// launched by vp_rx_unpack (vp_rxunpack.hip): <<<1, kTxpScanThreads>>>
+constexpr uint32_t kTxpScanThreads = 1024;
+__global__ void txp_scan(uint64_t *sums, uint32_t m);
 
 // Owner-mode phase A stages (vp_last_stage_ms).
 constexpr int kStages = 8;
@@ -256,6 +262,14 @@ struct Workspace {
   hipEvent_t txp_ev = nullptr;
   hipStream_t txp_last = nullptr;
   bool txp_used = false;
+  // vp_rx_unpack without pos[] (vp_rxunpack.hip): the waves' padded bytes,
+  // scanned in place into their first positions; the last call's end and its
+  // stream
+  uint64_t *rxu_sum = nullptr;
+  size_t rxu_sum_n = 0;
+  hipEvent_t rxu_ev = nullptr;
+  hipStream_t rxu_last = nullptr;
+  bool rxu_used = false;
   // tbl_new_keys_unsorted: the tagged key set (3 x u64 per slot, never
   // reset: a slot of an older tag is empty), its tag, first-sighting bits
   // per position and their scan, the first sightings' miss ordinals and

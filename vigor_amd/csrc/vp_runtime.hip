@@ -179,7 +179,7 @@ static int preload_units(int gpu, hipStream_t s) {
   if (std::find(done.begin(), done.end(), gpu) != done.end()) return 0;
   for (auto f : {preload_runtime, preload_table, preload_nat, preload_bridge, preload_lb,
                  preload_fw, preload_pol, preload_comm, preload_mbuf, preload_tx,
-                 preload_txpack, preload_txbatch, preload_txmerge})
+                 preload_txpack, preload_txbatch, preload_txmerge, preload_rxunpack})
     VP_HIP(f(s));
   VP_HIP(hipStreamSynchronize(s));
   done.push_back(gpu);
@@ -233,10 +233,11 @@ static void free_all(vp_ctx *c) {
                   w.route,   w.sendk,    w.recvk,  w.reply,  w.rreply,
                   w.cnt_t,   w.rcnt_t,   w.dneed,  w.xsend, w.sendk2, w.recvk2,
                   w.reply2,  w.rreply2,  w.lcnt, w.nkset, w.nkbits, w.nkpre,
-                  w.nkfirst, w.nkcnt, w.in_fill, w.tx_cnt, w.txp_sum};
+                  w.nkfirst, w.nkcnt, w.in_fill, w.tx_cnt, w.txp_sum, w.rxu_sum};
   for (void *p : ptrs) hipFree(p);
   if (w.tx_ev) hipEventDestroy(w.tx_ev);
   if (w.txp_ev) hipEventDestroy(w.txp_ev);
+  if (w.rxu_ev) hipEventDestroy(w.rxu_ev);
   for (int i = 0; i < 2; i++) {
     if (w.ev_p1[i]) hipEventDestroy(w.ev_p1[i]);
     if (w.ev_ans[i]) hipEventDestroy(w.ev_ans[i]);

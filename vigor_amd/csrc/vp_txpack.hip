@@ -31,8 +31,9 @@ constexpr uint32_t kTxpTurns = kTxpPerWave / 64;  // 64 entries, one per lane, p
 // a frame's copy is at most 65535 bytes (len is 16 bits) rounded up to 16
 static_assert((uint64_t)kTxpBlockEntries * 65536u < (1ull << 32), "a block's sum in 32 bits");
 static_assert(kTxpBlockEntries % (64 * kTxpWaves) == 0, "whole waves");
-// txp_scan: one block, kTxpScanItems consecutive sums per thread and tile
-constexpr uint32_t kTxpScanThreads = 1024, kTxpScanItems = 8;
+// txp_scan: one block (kTxpScanThreads, vp_internal.h), kTxpScanItems
+// consecutive sums per thread and tile
+constexpr uint32_t kTxpScanItems = 8;
 constexpr uint32_t kTxpScanTile = kTxpScanThreads * kTxpScanItems;
 constexpr uint32_t kTxpLean = 64;  // the widest padded frame of the four-lane path
 

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import (BridgeConfigC, DevBatchC, FwConfigC, LbConfigC, MbufBatchC,
-               NatConfigC, PolConfigC, ServeExpiryStatsC, ServeStatsC, TableStatsC,
+               NatConfigC, PolConfigC, RxStreamC, ServeExpiryStatsC, ServeStatsC, TableStatsC,
                TX_MERGE_MAX, TxFramesC, TxListsC, TxMergedC, TxNextC, TxSourceC, TxStatsC,
                _check, lib)
 
@@ -292,6 +292,61 @@ class NfBase:
                         which=_dptr(out_which) if cap else None, count=count.data_ptr())
         s = C.c_void_p(stream.cuda_stream) if stream is not None else None
         self._ck(self.L.vp_tx_merge(self.h, arr, len(sources), C.byref(out), s), "vp_tx_merge")
+
+    def rx_unpack(self, data, lens, out_frames, out_slot, out_lens, count, pos=None, sel=None,
+                  out_now=None, out_src=None, now=None, now0: int = 0, now_step: int = 0,
+                  n=None, stream=None):
+        """vp_rx_unpack: a packed stream of frames (tx_pack's, a capture, a
+        buffer another device wrote) as a device batch -- entry e's frame,
+        r = min(len, out_slot) bytes at a 16-byte aligned position of `data`,
+        into slot e of out_frames, zero-filled behind, with len[], the time and
+        the index m(e) into lens / now carried along. data: uint8 CUDA tensor
+        whose size is the readable bytes (None: 0); lens: 16-bit CUDA tensor of
+        meta_n entries (None: 0); now: None (now0 + m * now_step) or a 64-bit
+        CUDA tensor of meta_n; pos: None (the frames lie back to back at their
+        lengths rounded up to 16) or a 64-bit CUDA tensor of byte offsets; sel:
+        None (m(e) = e) or a 32-bit CUDA tensor. n: the entries, by default
+        sel's length, else pos's, else meta_n; pos and sel hold at least n.
+        out_lens: 16-bit CUDA tensor whose length is the capacity in packets
+        (None: 0); out_frames: uint8 CUDA tensor of capacity * out_slot bytes;
+        out_now: None or a 64-bit tensor, out_src: None or a 32-bit tensor,
+        each of at least the capacity; count: 32-bit CUDA tensor of one word,
+        n afterwards. Enqueued on `stream` (the context's own for None) and
+        not waited for."""
+        meta_n = lens.numel() if lens is not None else 0
+        nbytes = data.numel() if data is not None else 0
+        cap = out_lens.numel() if out_lens is not None else 0
+        if n is None:
+            n = sel.numel() if sel is not None else pos.numel() if pos is not None else meta_n
+        if nbytes:
+            assert data.is_cuda and data.element_size() == 1
+        if meta_n:
+            assert lens.is_cuda and lens.element_size() == 2
+        if pos is not None:
+            assert pos.is_cuda and pos.element_size() == 8 and pos.numel() >= n
+        if sel is not None:
+            assert sel.is_cuda and sel.element_size() == 4 and sel.numel() >= n
+        if now is not None:
+            assert now.is_cuda and now.element_size() == 8 and now.numel() == meta_n
+        assert count.is_cuda and count.element_size() == 4 and count.numel() >= 1
+        if cap:
+            assert out_lens.is_cuda and out_lens.element_size() == 2
+            assert out_frames.is_cuda and out_frames.element_size() == 1
+            assert out_frames.numel() == cap * out_slot
+        if out_now is not None:
+            assert out_now.is_cuda and out_now.element_size() == 8 and out_now.numel() >= cap
+        if out_src is not None:
+            assert out_src.is_cuda and out_src.element_size() == 4 and out_src.numel() >= cap
+        rx = RxStreamC(data=_dptr(data) if nbytes else None, bytes=nbytes, n=n,
+                       pos=_dptr(pos) if n else None, sel=_dptr(sel) if n else None,
+                       meta_n=meta_n, len=_dptr(lens) if meta_n else None,
+                       now=_dptr(now) if meta_n else None, now0=now0, now_step=now_step)
+        out = TxNextC(frames=_dptr(out_frames) if cap else None, slot=out_slot, cap=cap,
+                      len=_dptr(out_lens) if cap else None,
+                      now=_dptr(out_now) if cap else None,
+                      src=_dptr(out_src) if cap else None, count=count.data_ptr())
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._ck(self.L.vp_rx_unpack(self.h, C.byref(rx), C.byref(out), s), "vp_rx_unpack")
 
     def sync_state(self):
         """Multi-GPU: merge the ranks' timestamps (collective)."""
