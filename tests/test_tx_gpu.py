@@ -263,6 +263,43 @@ def test_non_default_stream_after_process_device():
     end_to_end(nat, o, 2, fr, ln, dv, now, stream=torch.cuda.Stream())
 
 
+def test_workspace_growth_and_reuse_across_two_streams():
+    """The context's one workspace of counts is ordered between streams by the
+    library: one block's worth on the context's stream, three blocks and a
+    remainder with floods on a second stream (the workspace grows), then the
+    small batch again on the first (it waits for the second's launches),
+    nothing waited for in between; every call gives the reference's offsets,
+    lists and stats."""
+    rng = np.random.default_rng(24)
+    nd = 4
+    nf = vigor_amd.Bridge(vigor_amd.bridge_config_from_args([], nd), gpu=0)  # a fresh workspace
+    small = mix(rng, T, 2, p_bad=0.0)  # ports 0 and 1 only
+    large = mix(rng, 3 * T + 5, nd, p_flood=0.3)
+    s2 = torch.cuda.Stream()
+    d = torch.device("cuda:0")
+    jobs = []
+    for (out, ins, lens), stream in ((small, None), (large, s2), (small, None)):
+        want = tx_reference(out, ins, lens, nd, 1 << 32)
+        total = want[0].size
+        assert total == int(want[1][nd]) and total > 0
+        jobs.append((want, total, stream, dev16(out), dev16(ins), dev16(lens),
+                     torch.full((total + TAIL,), MARK, dtype=torch.int32, device=d),
+                     torch.full((nd + 1,), MARK, dtype=torch.int32, device=d),
+                     torch.full((8 * STATS_WORDS,), 0xFF, dtype=torch.uint8, device=d)))
+    assert jobs[1][1] > jobs[1][3].numel()  # (floods: more entries than packets)
+    torch.cuda.synchronize()
+    for want, total, stream, o_t, i_t, l_t, buf, off, st in jobs:
+        nf.tx_build(o_t, i_t, l_t, buf[:total], off, st, stream=stream)
+    torch.cuda.synchronize()
+    for (full, r_off, r_st), total, stream, o_t, i_t, l_t, buf, off, st in jobs:
+        got = buf.cpu().numpy().view(np.uint32)
+        assert off.cpu().numpy().view(np.uint32).tobytes() == r_off.tobytes()
+        assert st.cpu().numpy().view(np.uint64).tobytes() == r_st.tobytes()
+        assert got[:total].tobytes() == full.tobytes()
+        assert (got[total:] == MARK).all()
+    nf.close()
+
+
 def test_einval_cases():
     nf = bridge(32)
     L = nf.L

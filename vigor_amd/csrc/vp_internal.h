@@ -109,6 +109,25 @@ hipError_t preload_rxunpack(hipStream_t s);
 constexpr uint32_t kTxpScanThreads = 1024;
 __global__ void txp_scan(uint64_t *sums, uint32_t m);
 
+// Host checks of the transmit / receive calls. An NF's n_devices; a slot
+// array's slot and alignment; a destination (vp_tx_next, vp_tx_merged); two
+// byte ranges, neither NULL nor empty, that share a byte; what vp_tx_rebatch
+// rejects of one source (vp_txbatch.hip): 0 and *nd, or VP_EINVAL.
+uint32_t ctx_devices(const vp_ctx *c);
+inline bool slots_ok(const void *frames, uint32_t slot) {
+  return slot >= 64 && slot % 16 == 0 && ((uintptr_t)frames & 15) == 0;
+}
+template <class O>
+bool slot_dest_ok(const O *o) {
+  return slots_ok(o->frames, o->slot) && !((!o->frames || !o->len) && o->cap);
+}
+inline bool bytes_overlap(const void *a, uint64_t an, const void *b, uint64_t bn) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 && b0 && an && bn && a0 < b0 + bn && b0 < a0 + an;
+}
+int tx_source_check(const vp_ctx *c, const vp_dev_batch *b, const vp_tx_lists *l, uint32_t port,
+                    const uint8_t *oframes, uint32_t oslot, uint32_t ocap, uint32_t *nd);
+
 // Owner-mode phase A stages (vp_last_stage_ms).
 constexpr int kStages = 8;
 inline constexpr const char *kStageNames[kStages] = {
@@ -236,6 +255,24 @@ struct FlowTable {
   uint32_t own_n = 0, own_r = 0;  // ranks, this rank (own_n == 0: off)
 };
 
+// A device buffer one entry point keeps for its largest call so far. Before a
+// call's launches on `s`, callbuf_reserve: growing waits for the last call on
+// the host, another stream than the last call's waits for it; after them, _done.
+struct CallBuf {
+  void *p = nullptr;
+  size_t bytes = 0;
+  hipEvent_t ev = nullptr;
+  hipStream_t last = nullptr;
+  bool used = false;
+};
+int callbuf_reserve(CallBuf &w, size_t bytes, hipStream_t s);
+inline int callbuf_done(CallBuf &w, hipStream_t s) {
+  VP_HIP(hipEventRecord(w.ev, s));
+  w.used = true;
+  w.last = s;
+  return 0;
+}
+
 struct Workspace {
   uint32_t cap_n = 0;  // batch capacity these buffers hold
   uint32_t *miss = nullptr;
@@ -248,28 +285,10 @@ struct Workspace {
   uint32_t *pairs = nullptr;  // tbl_touch_reduce's scattered (position, index) words
   uint16_t *in_fill = nullptr;  // a batch's one port as an array (vp_dev_batch.in_port)
   size_t in_fill_n = 0;
-  // vp_tx_build (vp_tx.hip): entries per block and port, scanned in place into
-  // write positions; the last call's end and the stream it ran on
-  uint32_t *tx_cnt = nullptr;
-  size_t tx_cnt_n = 0;
-  hipEvent_t tx_ev = nullptr;
-  hipStream_t tx_last = nullptr;
-  bool tx_used = false;
-  // vp_tx_pack (vp_txpack.hip): the blocks' padded bytes, scanned in place
-  // into their first positions; the last call's end and its stream
-  uint64_t *txp_sum = nullptr;
-  size_t txp_sum_n = 0;
-  hipEvent_t txp_ev = nullptr;
-  hipStream_t txp_last = nullptr;
-  bool txp_used = false;
-  // vp_rx_unpack without pos[] (vp_rxunpack.hip): the waves' padded bytes,
-  // scanned in place into their first positions; the last call's end and its
-  // stream
-  uint64_t *rxu_sum = nullptr;
-  size_t rxu_sum_n = 0;
-  hipEvent_t rxu_ev = nullptr;
-  hipStream_t rxu_last = nullptr;
-  bool rxu_used = false;
+  // vp_tx_build's entries per block and port (u32), vp_tx_pack's padded bytes
+  // per block, vp_rx_unpack's per wave (u64): one buffer per call, which may
+  // be in flight on different streams together
+  CallBuf tx_cnt, txp_sum, rxu_sum;
   // tbl_new_keys_unsorted: the tagged key set (3 x u64 per slot, never
   // reset: a slot of an older tag is empty), its tag, first-sighting bits
   // per position and their scan, the first sightings' miss ordinals and

@@ -19,7 +19,6 @@ namespace vp {
 
 VP_PRELOAD_UNIT(runtime)
 
-
 // vp_last_error(): the calling thread's last failure
 static thread_local char g_last_error[256];
 
@@ -161,6 +160,30 @@ int ws_reserve(vp_ctx *c, uint32_t n) {
   return 0;
 }
 
+int callbuf_reserve(CallBuf &w, size_t bytes, hipStream_t s) {
+  if (!w.ev) VP_HIP(hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
+  if (bytes > w.bytes) {
+    if (w.used) VP_HIP(hipEventSynchronize(w.ev));
+    hipFree(w.p);
+    w.p = nullptr;
+    w.bytes = 0;
+    VP_HIP(hipMalloc(&w.p, bytes));
+    w.bytes = bytes;
+  } else if (w.used && w.last != s) {
+    VP_HIP(hipStreamWaitEvent(s, w.ev, 0));
+  }
+  return 0;
+}
+
+uint32_t ctx_devices(const vp_ctx *c) {
+  return c->kind == KIND_NAT      ? c->nat.n_devices
+         : c->kind == KIND_BRIDGE ? c->brg.n_devices
+         : c->kind == KIND_LB     ? c->lb.n_devices
+         : c->kind == KIND_FW     ? c->fw.n_devices
+         : c->kind == KIND_POL    ? c->pol.n_devices
+                                  : 0;
+}
+
 static void mac_words(const uint8_t d[6], const uint8_t s[6], uint32_t w[3]) {
   uint8_t b[12];
   memcpy(b, d, 6);
@@ -233,11 +256,12 @@ static void free_all(vp_ctx *c) {
                   w.route,   w.sendk,    w.recvk,  w.reply,  w.rreply,
                   w.cnt_t,   w.rcnt_t,   w.dneed,  w.xsend, w.sendk2, w.recvk2,
                   w.reply2,  w.rreply2,  w.lcnt, w.nkset, w.nkbits, w.nkpre,
-                  w.nkfirst, w.nkcnt, w.in_fill, w.tx_cnt, w.txp_sum, w.rxu_sum};
+                  w.nkfirst, w.nkcnt, w.in_fill};
   for (void *p : ptrs) hipFree(p);
-  if (w.tx_ev) hipEventDestroy(w.tx_ev);
-  if (w.txp_ev) hipEventDestroy(w.txp_ev);
-  if (w.rxu_ev) hipEventDestroy(w.rxu_ev);
+  for (CallBuf *b : {&w.tx_cnt, &w.txp_sum, &w.rxu_sum}) {
+    hipFree(b->p);
+    if (b->ev) hipEventDestroy(b->ev);
+  }
   for (int i = 0; i < 2; i++) {
     if (w.ev_p1[i]) hipEventDestroy(w.ev_p1[i]);
     if (w.ev_ans[i]) hipEventDestroy(w.ev_ans[i]);

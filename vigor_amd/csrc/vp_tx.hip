@@ -24,15 +24,15 @@
 #include <cstdint>
 
 #include "vp_internal.h"
+#include "vp_slots_dev.h"
 
 namespace vp {
 
 VP_PRELOAD_UNIT(tx)
 
-constexpr uint32_t kTxBlockPackets = 2048;  // vigor_amd.TX_BLOCK_PACKETS
-constexpr uint32_t kTxThreads = 256, kTxWaves = kTxThreads / 64;
+constexpr uint32_t kTxBlockPackets = kSlotBlockEntries;  // vigor_amd.TX_BLOCK_PACKETS
+constexpr uint32_t kTxThreads = kSlotThreads, kTxWaves = kSlotWaves, kTxPerWave = kSlotPerWave;
 constexpr uint32_t kTxPerThread = kTxBlockPackets / kTxThreads;
-constexpr uint32_t kTxPerWave = kTxBlockPackets / kTxWaves;
 // tx_count packs a thread's entries for one port as count << 20 | bytes
 static_assert(kTxPerThread * 65535u < (1u << 20) && kTxPerThread < (1u << 12), "packed sums");
 static_assert((uint64_t)kTxBlockPackets * 65535u < (1ull << 32), "a block's byte sum in 32 bits");
@@ -50,12 +50,6 @@ __device__ __forceinline__ uint32_t tx_class(uint32_t out, uint32_t in, uint32_t
   if (out == VP_FLOOD_FRAME) return kTxFlood << 16 | in;
   if (out < nd) return kTxUni << 16 | out;
   return kTxNone << 16;
-}
-
-__device__ __forceinline__ uint32_t tx_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 __global__ __launch_bounds__(kTxThreads) void tx_count(
@@ -100,17 +94,17 @@ __global__ __launch_bounds__(kTxThreads) void tx_count(
       c += v >> 20;
       b += v & 0xFFFFFu;
     }
-    c = tx_wave_sum(c);
-    b = tx_wave_sum(b);
+    c = wave_sum(c);
+    b = wave_sum(b);
     if (lane == 0) {
       cnt[(size_t)d * blocks + blockIdx.x] = c;
       if (stats && b) atomicAdd((unsigned long long *)&stats->bytes[d], (unsigned long long)b);
     }
   }
   if (!stats) return;
-  dropped = tx_wave_sum(dropped);
-  flooded = tx_wave_sum(flooded);
-  bad = tx_wave_sum(bad);
+  dropped = wave_sum(dropped);
+  flooded = wave_sum(flooded);
+  bad = wave_sum(bad);
   if (lane == 0) {
     if (dropped) atomicAdd(&misc[0], dropped);
     if (flooded) atomicAdd(&misc[1], flooded);
@@ -142,12 +136,7 @@ __global__ __launch_bounds__(kTxScanThreads) void tx_scan(uint32_t *cnt, uint32_
       v[k] = j0 + k < m ? cnt[j0 + k] : 0u;
       t += v[k];
     }
-    uint32_t x = t;  // inclusive scan of the threads' sums over the wave
-#pragma unroll
-    for (uint32_t o = 1; o < 64; o <<= 1) {
-      const uint32_t u = __shfl_up(x, o);
-      if (lane >= o) x += u;
-    }
+    const uint32_t x = wave_scan(t, lane);  // of the threads' sums
     if (lane == 63) wsum[wv] = x;
     __syncthreads();
     uint32_t before = 0, total = 0;
@@ -254,47 +243,16 @@ __global__ __launch_bounds__(kTxThreads) void tx_scatter(
   }
 }
 
-static uint32_t tx_devices(const vp_ctx *c) {
-  switch (c->kind) {
-    case KIND_NAT: return c->nat.n_devices;
-    case KIND_BRIDGE: return c->brg.n_devices;
-    case KIND_LB: return c->lb.n_devices;
-    case KIND_FW: return c->fw.n_devices;
-    case KIND_POL: return c->pol.n_devices;
-    default: return 0;
-  }
-}
-
-// The blocks x n_devices counts, for the largest call so far. One workspace
-// per context: a call on another stream than the last one's waits for that
-// one's launches first.
-static int tx_reserve(vp_ctx *c, size_t m, hipStream_t s) {
-  Workspace &w = c->ws;
-  if (!w.tx_ev) VP_HIP(hipEventCreateWithFlags(&w.tx_ev, hipEventDisableTiming));
-  if (m > w.tx_cnt_n) {
-    if (w.tx_used) VP_HIP(hipEventSynchronize(w.tx_ev));
-    hipFree(w.tx_cnt);
-    w.tx_cnt = nullptr;
-    w.tx_cnt_n = 0;
-    VP_HIP(hipMalloc((void **)&w.tx_cnt, 4 * m));
-    w.tx_cnt_n = m;
-  } else if (w.tx_used && w.tx_last != s) {
-    VP_HIP(hipStreamWaitEvent(s, w.tx_ev, 0));
-  }
-  return 0;
-}
-
 }  // namespace vp
 
 using namespace vp;
 
 extern "C" int vp_tx_build(vp_ctx *c, const vp_dev_batch *b, const vp_tx_lists *l,
                            void *stream) {
-  static_assert(kTxBlockPackets % (64 * kTxWaves) == 0, "whole waves");
   if (!c || !b || !l || !b->out_dev || !l->offset) return VP_EINVAL;
   if ((!l->idx && l->cap) || (l->stats && !b->len && b->n)) return VP_EINVAL;
   if (!b->in_dev && b->in_port > 0xFFFFu) return VP_EINVAL;
-  const uint32_t nd = tx_devices(c), n = b->n;
+  const uint32_t nd = ctx_devices(c), n = b->n;
   if (nd > VP_MAX_DEVICES) return VP_EINVAL;
   // every list position is a 32-bit number
   if ((uint64_t)n * std::max(1u, nd > 0 ? nd - 1 : 0u) > 0xFFFFFFFFull) return VP_EINVAL;
@@ -303,23 +261,21 @@ extern "C" int vp_tx_build(vp_ctx *c, const vp_dev_batch *b, const vp_tx_lists *
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   const uint32_t blocks = (uint32_t)(((uint64_t)n + kTxBlockPackets - 1) / kTxBlockPackets);
   const size_t m = (size_t)blocks * nd;
-  Workspace &w = c->ws;
-  VP_TRY(tx_reserve(c, m, s));
+  CallBuf &w = c->ws.tx_cnt;  // the blocks x n_devices counts
+  VP_TRY(callbuf_reserve(w, 4 * m, s));
+  uint32_t *cnt = (uint32_t *)w.p;
   if (l->stats) VP_HIP(hipMemsetAsync(l->stats, 0, sizeof(vp_tx_stats), s));
   if (blocks) {
     tx_count<<<blocks, kTxThreads, 4 * kTxThreads * std::max(1u, nd), s>>>(
-        b->out_dev, b->in_dev, b->in_port, b->len, n, nd, blocks, w.tx_cnt, l->stats);
+        b->out_dev, b->in_dev, b->in_port, b->len, n, nd, blocks, cnt, l->stats);
     VP_HIP(hipGetLastError());
   }
-  tx_scan<<<1, kTxScanThreads, 0, s>>>(w.tx_cnt, (uint32_t)m, blocks, nd, l->offset, l->stats);
+  tx_scan<<<1, kTxScanThreads, 0, s>>>(cnt, (uint32_t)m, blocks, nd, l->offset, l->stats);
   VP_HIP(hipGetLastError());
   if (m && l->cap) {
     tx_scatter<<<blocks, kTxThreads, 0, s>>>(b->out_dev, b->in_dev, b->in_port, n, nd, blocks,
-                                             w.tx_cnt, l->idx, l->cap);
+                                             cnt, l->idx, l->cap);
     VP_HIP(hipGetLastError());
   }
-  VP_HIP(hipEventRecord(w.tx_ev, s));
-  w.tx_used = true;
-  w.tx_last = s;
-  return 0;
+  return callbuf_done(w, s);
 }
