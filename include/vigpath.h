@@ -760,8 +760,14 @@ int vp_last_kernel_ms(vp_ctx *ctx, float *ms, int *launches);
 
 /* The name of the tile kernel the last vp_process_device call launched for
  * its 64-byte slots (vignat picks nat_classify64w or nat_classify64ws per
- * segment; viglb lb_classify64[w]); "" when none was. The
- * string is static. */
+ * segment; viglb lb_classify64[w]); "" when none was.
+ * vigpol names every segment, whatever the slot: its classify kernel plus the
+ * phase-T path that produced the segment's results --
+ * "pol_classify64+pol_runs" (run slots), "...+pol_scatter+pol_runs" (scan +
+ * scatter) or "...+pol_buckets" (the sorting path, a grouping attempt that fell
+ * back included), with pol_classify for slots other than 64 bytes. A call
+ * that was cut into several segments reports its last segment's. The string
+ * is static. */
 const char *vp_last_kernel(vp_ctx *ctx);
 
 /* Owner-sharded multi-GPU contexts (VP_SHARD_OWNER) with kernel timing on:

@@ -106,7 +106,8 @@ def test_steady_state_grouping_path():
     (per-index hit counts from phase A, scan + scatter, per-lane insertion
     sort); uniformly random order puts each run's packets out of order in
     the scatter. A hot address (run > 64) in the last batch sends that
-    segment to the radix-sort path instead. Both must equal the oracle."""
+    segment to the radix-sort path instead. Both must equal the oracle, and
+    vp_last_kernel must name the path each batch's last segment took."""
     rng = np.random.default_rng(21)
     n_dst, n = 5000, 60000
     d = np.concatenate([np.arange(n_dst), rng.integers(0, n_dst, n - n_dst)])
@@ -117,5 +118,12 @@ def test_steady_state_grouping_path():
     dv = np.zeros(n, np.uint16)
     now = (T.NOW0 + np.cumsum(rng.integers(0, 40, n))).astype(np.int64)
     pol, o = make_pair(cap=8192, rate=2_000_000, burst=2000)
-    check_batches(pol, o, f.copy(), ln, dv, now, 64, [n_dst, 25000, 45000])
+    fr = f.copy()
+    bounds = [0, n_dst, 25000, 45000, n]
+    want = ["pol_classify64+pol_buckets",  # the allocating batch: every packet a miss
+            "pol_classify64+pol_runs", "pol_classify64+pol_runs",  # steady
+            "pol_classify64+pol_buckets"]  # the hot address: a run above 64
+    for a, b, k in zip(bounds[:-1], bounds[1:], want):
+        check_batches(pol, o, fr[a * 64:b * 64], ln[a:b], dv[a:b], now[a:b], 64, [])
+        assert pol.last_kernel() == k, (a, b, pol.last_kernel())
     check_state(pol, o, 8192)

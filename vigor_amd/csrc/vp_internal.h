@@ -650,7 +650,8 @@ struct vp_ctx {
   uint32_t *pol_runs = nullptr;  // [kRunMax][index] hit positions (grouping;
                                  // allocated by the first grouping segment,
                                  // tables up to 4M indices, else pol_off)
-  bool pol_runs_tried = false;   // that allocation was attempted
+  bool pol_runs_tried = false;   // that allocation was attempted (or
+                                 // VIGPATH_POL_RUNS=0 said not to make it)
   uint4 *be_rec = nullptr;  // viglb backends[]: {ip, mac0-3, mac4-5|nic<<16, 0}
   uint32_t *cht = nullptr;  // viglb CHT, cht[bucket * backend_capacity + prio]
   uint32_t *dmacw = nullptr;  // per device: {s_addr[0..1] << 16, s_addr[2..5]}

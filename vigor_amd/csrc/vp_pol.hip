@@ -824,7 +824,12 @@ static int pol_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   const uint32_t epoch = ++t.pub_epoch;  // phase A's counts, published by pol_runs
   const PubArgs pub{t.d_pub, t.ctl, epoch, nullptr, nullptr, 0, 0};
   VP_HIP(ev_record(c->ktime, c->ev0, c->stream));
-  if (b->slot == 64 && c->coalesced_io) {
+  const bool tile64 = b->slot == 64 && c->coalesced_io;
+  // vp_last_kernel: the classify kernel plus the phase-T path that produced
+  // this segment's results (the sorting path until the grouping path is
+  // known to have run, below)
+  c->last_kernel = tile64 ? "pol_classify64+pol_buckets" : "pol_classify+pol_buckets";
+  if (tile64) {
     const uint32_t tiles = (p1 - (p0 & ~63u) + 63) / 64;
     pol_classify64<<<resident_grid((const void *)pol_classify64, (tiles + 3) / 4), 256, 0,
                      c->stream>>>(a, b->n);
@@ -891,6 +896,11 @@ static int pol_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   if (grouping && !nmiss && !ndefer && t.h_ctl.aux_count == 0) {
     t.ctl_clean = true;       // nothing counted
     c->pol_cnt_clean = true;  // pol_runs cleared every count it read
+    if (c->pol_runs)
+      c->last_kernel = tile64 ? "pol_classify64+pol_runs" : "pol_classify+pol_runs";
+    else
+      c->last_kernel = tile64 ? "pol_classify64+pol_scatter+pol_runs"
+                              : "pol_classify+pol_scatter+pol_runs";
     return 0;
   }
   // phase T, sorting path: (index, packet) pairs sorted by index; radix sort

@@ -670,6 +670,11 @@ int vp_pol_create(const vp_pol_config *cfg, int gpu, vp_ctx **out) {
     free_all(c);
     return rc;
   }
+  // VIGPATH_POL_RUNS=0 (diagnostics, read once per context): the run slots
+  // are never allocated, as after a failed allocation (pol_runs_reserve), so
+  // a table of any size groups by scan + scatter
+  const char *pr = getenv("VIGPATH_POL_RUNS");
+  if (pr && *pr && atoi(pr) == 0) c->pol_runs_tried = true;
   *out = c;
   return 0;
 }
