@@ -494,6 +494,92 @@ typedef struct vp_rx_stream {
  * overlapping. n == 0: count 0, nothing else written. */
 int vp_rx_unpack(vp_ctx *ctx, const vp_rx_stream *in, const vp_tx_next *out, void *stream);
 
+/* ----------------------------------------------------------- the way home --
+ * A chain of NFs standing where one NF stands: the packets a later stage
+ * received come back to the slots they started from in the caller's batch,
+ * with their out ports renamed to the ports of the composite box. */
+
+#define VP_RET_SKIP 0x10000u  /* leave the home packet alone (it travelled on over a link) */
+#define VP_RET_DROP 0x10001u  /* home out_dev = the home packet's own in port (nf.c:159) */
+/* any value <= 0xFFFF: written to home out_dev literally (VP_FLOOD_FRAME included) */
+
+typedef struct vp_tx_return_stats {
+  uint64_t returned;  /* entries written home (drops included) */
+  uint64_t dropped;   /* of those, written as VP_RET_DROP */
+  uint64_t skipped;   /* firsts whose action was VP_RET_SKIP */
+  uint64_t dup;       /* entries that were not the first of their run of equal home indices */
+  uint64_t bad_home;  /* firsts whose home index is >= home->n: nothing written */
+} vp_tx_return_stats;
+
+typedef struct vp_tx_way_home {
+  const uint32_t *home;              /* device, from->n entries, or NULL: home(k) = k */
+  uint32_t port[VP_MAX_DEVICES];     /* action for out == d, d < n_devices of ctx */
+  uint32_t on_drop, on_flood, on_bad;/* out == the entry's in port; VP_FLOOD_FRAME; any other */
+  vp_tx_return_stats *stats;         /* device, or NULL */
+} vp_tx_way_home;
+
+/* Return a stage's batch into the batch its packets came from: the inverse of
+ * vp_tx_rebatch. Where that call gathers the slots a list names into
+ * consecutive slots and records each one's index of origin, this one scatters
+ * consecutive slots back to such indices, and translates each packet's out
+ * port -- a port of the stage that produced `from` -- into a port of the box
+ * that holds the whole chain. Reads from->frames, slot, n, out_dev and in_dev
+ * (or in_port), home->slot, n and in_dev (or in_port), and way->home (device
+ * memory); writes slots and out_dev entries of `home`, and nothing else.
+ * `ctx` is the stage that produced `from`: it supplies n_devices, the GPU and
+ * the default stream. For entry k < from->n, with
+ *   h     = way->home[k], or k when way->home is NULL
+ *   first = k == 0 or h differs from entry k - 1's h   (the first of a run of
+ *           equal home indices: the copies one stage holds of one packet)
+ *   out   = from->out_dev[k],  in = from->in_dev[k] or from->in_port
+ * the action a is chosen in vp_tx_build's order:
+ *   out == in               a = way->on_drop                         (nf.c:159)
+ *   out == VP_FLOOD_FRAME   a = way->on_flood
+ *   out < n_devices         a = way->port[out]
+ *   otherwise               a = way->on_bad
+ * Entry k is written home iff it is a first, h < home->n and a != VP_RET_SKIP,
+ * and then, with slot_h = home->slot and w = min(from->slot, home->slot):
+ *   home->frames[h*slot_h .. h*slot_h + w)        the first w bytes of from's
+ *                                                 slot k, verbatim
+ *   home->frames[h*slot_h + w .. (h+1)*slot_h)    zero
+ *   home->out_dev[h] = a, or for a == VP_RET_DROP the home packet's own in
+ *                      port: home->in_dev[h], or home->in_port
+ * len is neither read nor written (no NF changes a length). Nothing else of
+ * `home` is written: a slot of `home` that no written entry names keeps every
+ * byte, and so does its out_dev entry.
+ * from->frames == home->frames with equal slots and way->home == NULL is the
+ * batch that is its own home: stage 0, which vp_process_device rewrote in
+ * place. No frame byte moves, only out_dev is translated, and from->out_dev
+ * and home->out_dev may then be the same array (only then). Any other overlap
+ * of the two slot ranges [frames, + n * slot) is VP_EINVAL.
+ * The result is deterministic whenever home[] does not decrease: the firsts
+ * then have distinct homes, and no two lanes write one slot. That holds for
+ * src[] of vp_tx_rebatch and vp_rx_unpack, key[] of vp_tx_merge, and origins
+ * composed from them along a chain. Where home[] does decrease, which of two
+ * firsts with one home wins is unspecified (bytes of both may mix in the
+ * slot), but the call still reads and writes nothing outside the two batches.
+ * *stats is written whole by every call (never accumulated) and always holds
+ * the true counts, which are sums and so deterministic in every case. A first
+ * whose action is VP_RET_SKIP and whose home index is >= home->n counts in
+ * both skipped and bad_home; from->n = returned + dup + (the firsts not
+ * written).
+ * The work is enqueued on `stream` (NULL: the context's own), after the work
+ * already there, and the call MAY RETURN BEFORE IT RAN: one kernel launch, the
+ * grid sized from from->n, in front of it a 40-byte clear of *stats on the same
+ * stream where stats is given (the waves add their counts to it); with
+ * from->n == 0 that clear is all there is. It makes no host round trip and
+ * needs no workspace. Like vp_tx_build it ends the NF's resident kernel, and
+ * after a multi-GPU attach it is local to the rank.
+ * VP_EINVAL: a NULL ctx, from, home or way; from->n > 0 with a NULL
+ * from->frames or from->out_dev; a NULL home->frames or home->out_dev with
+ * home->n > 0 and from->n > 0; either slot below 64 or not a multiple of 16;
+ * either frames not 16-byte aligned; in_dev NULL with in_port > 0xFFFF, on
+ * either batch; a port[d] with d < n_devices, or an on_* value, that is
+ * neither <= 0xFFFF nor one of the two sentinels; a context with more than
+ * VP_MAX_DEVICES devices; the overlap above. */
+int vp_tx_return(vp_ctx *ctx, const vp_dev_batch *from, const vp_dev_batch *home,
+                 const vp_tx_way_home *way, void *stream);
+
 /* Host memory the GPU may read and write frames in directly: a DPDK mbuf
  * pool's memory (the hugepages rte_pktmbuf_pool_create, nf.c:235-242, lays
  * the mbufs out in), registered once after the pool is created. Page-locked

@@ -2,7 +2,7 @@
 beside the bytes the algorithm has to move. Run by hand; not part of bench.py.
 
   python3 tools/bench_tx.py [--packets 16777216] [--reps 20] [--step-ms MS] [--pack]
-                             [--rebatch] [--merge] [--unpack]
+                             [--rebatch] [--merge] [--unpack] [--return]
 
 Three cases:
   two-port         vignat's headline outputs: every packet from port 0 (one
@@ -49,6 +49,15 @@ vp_tx_rebatch of the same entries and a plain device-to-device copy of the
 same slot bytes. Algorithmic bytes of an unpack: the port's stream read, each
 slot written, 22 B per entry read (sel, len, now, pos) and 14 B written (len,
 now, src); without pos the sizes pass reads sel and len once more.
+--return: after a case's lists are built and port 1's list is rebatched into
+64-byte slots with src[], vp_tx_return of that batch into the
+source batch's slots (home = src[], every packet sent on to an exit) is timed
+the same way, with stats and without; beside it, in the same run and on the
+same stream, vp_tx_rebatch of the same entries and a plain device-to-device
+copy of the same slot bytes. Algorithmic bytes of a return: each slot read and
+written, 6 B per entry read (home, out) and 2 B written (the home out port):
+the rebatch's slot bytes with the index on the write side, and 8 B of
+per-entry arrays where the rebatch has 28.
 --step-ms: the headline step (bench.py's ms_per_step of the same session);
 every time is then also given as a fraction of it.
 """
@@ -377,6 +386,82 @@ def measure_unpack(nf, nd, lens, idx, off, total, port, reps, dev):
             "bytes_over_copy_bytes": round(alg / (2 * count * slot), 3) if count else None}
 
 
+def measure_return(nf, nd, lens, idx, off, total, port, reps, dev):
+    """vp_tx_return of list `port`'s rebatched batch (64-byte slots) into the
+    source batch's slots, home = the rebatch's src[]; beside it, on the same
+    stream, vp_tx_rebatch of the same entries and a plain copy of the same slot
+    bytes."""
+    n, slot = lens.numel(), 64
+    frames = torch.randint(0, 256, (n * slot,), dtype=torch.uint8, device=dev)
+    now = torch.arange(n, dtype=torch.int64, device=dev) + T.NOW0
+    bounds = off.cpu().numpy().view(np.uint32)
+    lo, count = int(bounds[port]), int(bounds[port + 1] - bounds[port])
+    idx = idx[:total] if total else None
+    cap = max(count, 1)
+    o_f = torch.zeros(cap * slot, dtype=torch.uint8, device=dev)
+    o_l = torch.zeros(cap, dtype=torch.int16, device=dev)
+    o_n = torch.zeros(cap, dtype=torch.int64, device=dev)
+    o_s = torch.zeros(cap, dtype=torch.int32, device=dev)
+    cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+    # the stage behind the cable sent every packet on to its port 1, the
+    # composite's port 7
+    o_out = torch.ones(cap, dtype=torch.int16, device=dev)
+    h_out = torch.zeros(n, dtype=torch.int16, device=dev)
+    st = torch.zeros(C.sizeof(vigor_amd.TxReturnStatsC), dtype=torch.uint8, device=dev)
+    ports = [vigor_amd.RET_DROP] * nd
+    ports[1] = 7
+    src = torch.randint(0, 256, (cap * slot,), dtype=torch.uint8, device=dev)
+    dst = torch.empty_like(src)
+    s = torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()  # (torch filled the buffers on its own stream)
+
+    def rebatch():
+        nf.tx_rebatch(frames, slot, lens, idx, off, port, o_f, slot, o_l, cnt, out_now=o_n,
+                      out_src=o_s, now=now, stream=s)
+
+    with torch.cuda.stream(s):
+        rebatch()
+        o_f[:count * slot] ^= 0xFF  # (the stage rewrote its frames: the return shows)
+    s.synchronize()
+    ms = timed(s, reps, lambda: nf.tx_return(
+        o_f[:count * slot], slot, o_out[:count], 0, frames, slot, h_out, 0, ports,
+        vigor_amd.RET_DROP, vigor_amd.RET_DROP, vigor_amd.RET_DROP, home=o_s[:count], stats=st,
+        stream=s))
+    # the first entries against a scatter made with torch (a sanity check of
+    # the run, not the test: tests/test_txreturn_gpu.py)
+    words = st.cpu().numpy().view(np.uint64)
+    assert words.tolist() == [count, 0, 0, 0, 0]
+    k = min(count, 4096)
+    if k:
+        i = idx[lo:lo + k].long()
+        assert bool((frames.view(n, slot)[i] == o_f[:k * slot].view(k, slot)).all())
+        assert bool((h_out[i] == 7).all()) and int((h_out == 7).sum()) == count
+    ms_ns = timed(s, reps, lambda: nf.tx_return(
+        o_f[:count * slot], slot, o_out[:count], 0, frames, slot, h_out, 0, ports,
+        vigor_amd.RET_DROP, vigor_amd.RET_DROP, vigor_amd.RET_DROP, home=o_s[:count], stream=s))
+    ms_rb = timed(s, reps, rebatch)
+    ms_cp = timed(s, reps, lambda: dst.copy_(src))
+    # per entry: home (4) and out (2) read, home out (2) written
+    alg, alg_rb = 2 * count * slot + 8 * count, 2 * count * slot + 28 * count
+    med, med_rb, med_cp = (x[len(x) // 2] for x in (ms, ms_rb, ms_cp))
+    return {"port": port, "list_entries": count, "slot_bytes": count * slot,
+            "return_ms_median": round(med, 4), "return_ms_min": round(ms[0], 4),
+            "return_ms_max": round(ms[-1], 4),
+            "return_no_stats_ms_median": round(ms_ns[len(ms_ns) // 2], 4),
+            "return_no_stats_ms_min": round(ms_ns[0], 4),
+            "return_no_stats_ms_max": round(ms_ns[-1], 4),
+            "rebatch_ms_median": round(med_rb, 4), "rebatch_ms_min": round(ms_rb[0], 4),
+            "rebatch_ms_max": round(ms_rb[-1], 4),
+            "copy_ms_median": round(med_cp, 4), "copy_ms_min": round(ms_cp[0], 4),
+            "copy_ms_max": round(ms_cp[-1], 4),
+            "return_over_rebatch": round(med / med_rb, 3) if med_rb else None,
+            "return_over_copy": round(med / med_cp, 3) if med_cp else None,
+            "rebatch_over_copy": round(med_rb / med_cp, 3) if med_cp else None,
+            "return_alg_bytes": alg,
+            "bytes_over_rebatch_bytes": round(alg / alg_rb, 3) if count else None,
+            "bytes_over_copy_bytes": round(alg / (2 * count * slot), 3) if count else None}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--packets", type=int, default=1 << 24)
@@ -393,6 +478,9 @@ def main():
     ap.add_argument("--unpack", action="store_true",
                     help="also time vp_rx_unpack of port 1's packed stream, with and without "
                          "pos, beside vp_tx_rebatch and a plain copy")
+    ap.add_argument("--return", action="store_true",
+                    help="also time vp_tx_return of port 1's rebatched batch into the source "
+                         "batch's slots, beside vp_tx_rebatch and a plain copy")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     n = args.packets
@@ -449,6 +537,15 @@ def main():
             if args.step_ms:
                 p["headline_step_ms"] = args.step_ms
                 p["fraction_of_step"] = round(p["unpack_ms_median"] / args.step_ms, 4)
+            print(json.dumps(p), flush=True)
+        if getattr(args, "return"):
+            idx, off, total = lists
+            p = {"case": name + "-return", "packets": n, "n_devices": nd, "entries": total,
+                 "reps": args.reps,
+                 **measure_return(nf, nd, ln, idx, off, total, 1, args.reps, dev)}
+            if args.step_ms:
+                p["headline_step_ms"] = args.step_ms
+                p["fraction_of_step"] = round(p["return_ms_median"] / args.step_ms, 4)
             print(json.dumps(p), flush=True)
         del lists
         torch.cuda.empty_cache()

@@ -89,6 +89,21 @@ class RxStreamC(C.Structure):
 
 TX_MERGE_MAX = 8  # VP_TX_MERGE_MAX
 
+RET_SKIP, RET_DROP = 0x10000, 0x10001  # VP_RET_SKIP, VP_RET_DROP
+
+
+class TxReturnStatsC(C.Structure):
+    """vp_tx_return_stats (include/vigpath.h)."""
+    _fields_ = [("returned", C.c_uint64), ("dropped", C.c_uint64), ("skipped", C.c_uint64),
+                ("dup", C.c_uint64), ("bad_home", C.c_uint64)]
+
+
+class TxWayHomeC(C.Structure):
+    """vp_tx_way_home (include/vigpath.h): home and stats are device pointers."""
+    _fields_ = [("home", C.c_void_p), ("port", C.c_uint32 * MAX_DEV),
+                ("on_drop", C.c_uint32), ("on_flood", C.c_uint32), ("on_bad", C.c_uint32),
+                ("stats", C.c_void_p)]
+
 
 class TxSourceC(C.Structure):
     """vp_tx_source (include/vigpath.h): one list of a vp_tx_merge call."""
@@ -197,7 +212,7 @@ EXPORTS = ["vp_nat_create", "vp_bridge_create", "vp_lb_create", "vp_fw_create",
            "vp_last_stage_ms", "vp_stage_ms", "vp_comm_abort", "vp_probe_slots",
            "vp_probe_slots_w", "vp_process_one", "vp_last_kernel", "vp_serve_stats_get",
            "vp_serve_expiry_stats_get", "vp_tx_build", "vp_tx_pack", "vp_tx_rebatch",
-           "vp_tx_merge", "vp_rx_unpack"]
+           "vp_tx_merge", "vp_rx_unpack", "vp_tx_return"]
 
 _libs = {}
 
@@ -313,6 +328,9 @@ def lib(path: str | None = None):
     L.vp_rx_unpack.argtypes = [C.c_void_p, C.POINTER(RxStreamC), C.POINTER(TxNextC),
                                C.c_void_p]
     L.vp_rx_unpack.restype = C.c_int
+    L.vp_tx_return.argtypes = [C.c_void_p, C.POINTER(DevBatchC), C.POINTER(DevBatchC),
+                               C.POINTER(TxWayHomeC), C.c_void_p]
+    L.vp_tx_return.restype = C.c_int
     L.vp_last_error.argtypes = []
     L.vp_last_error.restype = C.c_char_p
     _libs[path] = L

@@ -15,7 +15,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import TX_MERGE_MAX
+from . import FLOOD_FRAME, RET_DROP, RET_SKIP, TX_MERGE_MAX, TxReturnStatsC
 
 
 class Chain:
@@ -49,9 +49,16 @@ class Chain:
     buffer the chain owns, then one rx_unpack per linked port. The stream
     carries min(len, slot) bytes of a frame, so the target sees zeros where the
     source slot held bytes past the frame's length. Stages with several
-    inbound links keep tx_merge. Any other value raises ValueError."""
+    inbound links keep tx_merge. Any other value raises ValueError.
 
-    def __init__(self, stages, links, cable="slots"):
+    exits: {(stage, port): external_port}, the ports of the composite box that
+    process_device reports: what stage `stage` sends to its unlinked port
+    `port` leaves the box on external_port. An unlinked port that is no exit
+    has no cable: its packets come home as drops. An exit that names a linked
+    port, a port its stage does not have, or a value above 0xFFFF raises
+    ValueError. `run` does not read it."""
+
+    def __init__(self, stages, links, cable="slots", exits=None):
         if cable not in ("slots", "stream"):
             raise ValueError("cable %r is neither 'slots' nor 'stream'" % (cable,))
         self.cable = cable
@@ -86,6 +93,17 @@ class Chain:
                     if [p for p, _ in self.outbound[s]].count(out_port) > 1:
                         raise ValueError("port %d of stage %d feeds stage %d, which merges, and "
                                          "has another link" % (out_port, s, t))
+        self.exits = {}
+        for key, ext in (exits or {}).items():
+            s, port = (int(x) for x in key)
+            if not 0 <= s < k or not 0 <= port < self.stages[s].cfg.n_devices:
+                raise ValueError("exit %r names a port its stage does not have" % (key,))
+            if port in [p for p, _ in self.outbound[s]]:
+                raise ValueError("exit %r names a linked port" % (key,))
+            if not 0 <= int(ext) <= 0xFFFF:
+                raise ValueError("exit %r: port %r is beyond 16 bits" % (key, ext))
+            self.exits[(s, port)] = int(ext)
+        self._home_stats = None  # process_device: one vp_tx_return_stats per stage
         self.stream = None
         self._lists = [None] * k  # per stage: (idx, offset)
         self._bufs = [None] * k   # per stage >= 1: its input batch's buffers
@@ -203,6 +221,66 @@ class Chain:
                               "origin": r["origin"][b["src"][:cnt].long()]}
         S.synchronize()
         return res
+
+    def way_home(self, s):
+        """Stage s's actions for tx_return, as (ports, on_drop, on_flood,
+        on_bad): a linked port is RET_SKIP (the packet travelled on; the stage
+        it reached has the later word), an exit its external number, any other
+        port RET_DROP (no cable); a drop and an out port the stage does not
+        have are RET_DROP. A flood's copies take different ways and a home
+        slot holds one out port, so: where every port of the stage is an exit
+        the flood is the composite's own (FLOOD_FRAME); otherwise stage 0
+        leaves the packet alone (RET_SKIP), for a stage that a copy reached to
+        decide, and a later stage drops it."""
+        nd = self.stages[s].cfg.n_devices
+        linked = {p for p, _ in self.outbound[s]}
+        ports = [RET_SKIP if d in linked else self.exits.get((s, d), RET_DROP) for d in range(nd)]
+        if all((s, d) in self.exits for d in range(nd)):
+            on_flood = FLOOD_FRAME
+        else:
+            on_flood = RET_SKIP if s == 0 else RET_DROP
+        return ports, RET_DROP, on_flood, RET_DROP
+
+    def process_device(self, frames, lens, in_dev, out, slot: int, now=None, now0: int = 0,
+                       now_step: int = 0):
+        """The chain where one NF stands: an NF's process_device signature, and
+        afterwards the caller's batch as one box holding the whole chain would
+        leave it -- frames rewritten in place, out[i] a port of the composite
+        box (`exits`) or, for a drop, packet i's own in port.
+
+        Calls run, then, for every stage in ascending order that received
+        packets, one tx_return into the caller's batch: home = the stage's
+        origins (stage 0: the in-place form), the actions way_home's. A later
+        stage's return overrides an earlier one's for the same packet; of the
+        copies one stage holds of a packet (floods merged back together) the
+        first counts. A packet that stage 0 flooded and no copy of which
+        reached a later stage is not written: out keeps the caller's value
+        there (way_home's rule). All returns go on the chain's stream, which is
+        waited for once at the end. Returns the stages' vp_tx_return_stats
+        summed, as a dict."""
+        res = self.run(frames, lens, in_dev, slot, now=now, now0=now0, now_step=now_step)
+        dev, S, k = frames.device, self.stream, len(self.stages)
+        names = [f for f, _ in TxReturnStatsC._fields_]
+        if self._home_stats is None or self._home_stats.device != dev:
+            self._home_stats = torch.zeros(k, len(names), dtype=torch.int64, device=dev)
+        stats = self._home_stats
+        with torch.cuda.stream(S):
+            stats.zero_()
+            for s, r in enumerate(res):
+                if r is None or r["n"] == 0:
+                    continue
+                ports, on_drop, on_flood, on_bad = self.way_home(s)
+                if s == 0:
+                    s_in, home = in_dev, None
+                else:
+                    s_in = r["in_dev"] if "in_dev" in r else self.inbound[s][2]
+                    home = r["key"] if "key" in r else r["origin"].to(torch.int32)
+                self.stages[s].tx_return(r["frames"], slot, r["out"], s_in, frames, slot, out,
+                                         in_dev, ports, on_drop, on_flood, on_bad, home=home,
+                                         stats=stats[s], stream=S)
+        S.synchronize()
+        total = stats.sum(dim=0).cpu().tolist()
+        return dict(zip(names, total))
 
     def _merge(self, t, res, offsets, time, ports, slot, dev):
         """Stage t's input from its several inbound links, and its run: one

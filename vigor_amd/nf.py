@@ -12,10 +12,10 @@ import ctypes as C
 
 import numpy as np
 
-from . import (BridgeConfigC, DevBatchC, FwConfigC, LbConfigC, MbufBatchC,
+from . import (BridgeConfigC, DevBatchC, FwConfigC, LbConfigC, MAX_DEV, MbufBatchC,
                NatConfigC, PolConfigC, RxStreamC, ServeExpiryStatsC, ServeStatsC, TableStatsC,
-               TX_MERGE_MAX, TxFramesC, TxListsC, TxMergedC, TxNextC, TxSourceC, TxStatsC,
-               _check, lib)
+               TX_MERGE_MAX, TxFramesC, TxListsC, TxMergedC, TxNextC, TxReturnStatsC, TxSourceC,
+               TxStatsC, TxWayHomeC, _check, lib)
 
 
 def _dptr(t):
@@ -347,6 +347,52 @@ class NfBase:
                       src=_dptr(out_src) if cap else None, count=count.data_ptr())
         s = C.c_void_p(stream.cuda_stream) if stream is not None else None
         self._ck(self.L.vp_rx_unpack(self.h, C.byref(rx), C.byref(out), s), "vp_rx_unpack")
+
+    def tx_return(self, frames, slot, out, in_dev, home_frames, home_slot, home_out, home_in_dev,
+                  ports, on_drop, on_flood, on_bad, home=None, stats=None, stream=None):
+        """vp_tx_return: this NF's batch back in the slots its packets started
+        from -- the inverse of tx_rebatch. Entry k goes to slot home[k] of
+        home_frames (k itself for home None) if it is the first of its run of
+        equal homes, and its out port, translated, to home_out[home[k]]:
+        ports[d] for out == d, on_drop for out == the entry's in port, on_flood
+        for FLOOD_FRAME, on_bad for anything else; each a port number up to
+        0xFFFF, RET_SKIP (leave the home packet alone) or RET_DROP (the home
+        packet's own in port). frames: uint8 CUDA tensor of n * slot bytes
+        (only read); out: 16-bit CUDA tensor of n; in_dev: the same, or an int
+        (every packet on that port); home_frames / home_out / home_in_dev: the
+        same of the home batch, its n that of home_out; ports: n_devices
+        values; home: None or a 32-bit CUDA tensor of n that does not decrease;
+        stats: None or a CUDA tensor of at least sizeof(vigor_amd.
+        TxReturnStatsC) bytes. frames and home_frames the same memory with
+        equal slots and home None: the batch is its own home, only the out
+        ports are translated (out and home_out may then be one tensor).
+        Enqueued on `stream` (the context's own for None) and not waited for."""
+        n, hn = out.numel(), home_out.numel()
+        assert frames.numel() == n * slot and home_frames.numel() == hn * home_slot
+        assert len(ports) <= MAX_DEV
+        port, hport = isinstance(in_dev, int), isinstance(home_in_dev, int)
+        for t, width, count in ((frames, 1, n * slot), (out, 2, n), (None if port else in_dev, 2, n),
+                                (home_frames, 1, hn * home_slot), (home_out, 2, hn),
+                                (None if hport else home_in_dev, 2, hn), (home, 4, n)):
+            if t is not None and count:
+                assert t.is_cuda and t.element_size() == width and t.numel() >= count
+        if stats is not None:
+            assert stats.is_cuda
+            assert stats.numel() * stats.element_size() >= C.sizeof(TxReturnStatsC)
+        b = DevBatchC(frames=_dptr(frames) if n else None, slot=slot, n=n,
+                      in_dev=None if port or not n else in_dev.data_ptr(),
+                      out_dev=_dptr(out) if n else None, in_port=in_dev if port else 0)
+        hb = DevBatchC(frames=_dptr(home_frames) if hn else None, slot=home_slot, n=hn,
+                       in_dev=None if hport or not hn else home_in_dev.data_ptr(),
+                       out_dev=_dptr(home_out) if hn else None,
+                       in_port=home_in_dev if hport else 0)
+        way = TxWayHomeC(home=_dptr(home) if n else None, on_drop=on_drop, on_flood=on_flood,
+                         on_bad=on_bad, stats=_dptr(stats))
+        for d, a in enumerate(ports):
+            way.port[d] = a
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._ck(self.L.vp_tx_return(self.h, C.byref(b), C.byref(hb), C.byref(way), s),
+                 "vp_tx_return")
 
     def sync_state(self):
         """Multi-GPU: merge the ranks' timestamps (collective)."""
