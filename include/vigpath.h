@@ -580,6 +580,159 @@ typedef struct vp_tx_way_home {
 int vp_tx_return(vp_ctx *ctx, const vp_dev_batch *from, const vp_dev_batch *home,
                  const vp_tx_way_home *way, void *stream);
 
+/* -------------------------------------------------------------- the chain --
+ * The calls above joined into one object: several contexts on one GPU with
+ * cables between them (firewall -> NAT, bridge -> policer, ...), what the
+ * reference runs as one box per NF, standing where one NF stands. The chain
+ * owns the lists, the batches between the stages and the origins; the stages'
+ * contexts, and their table state, stay the caller's. */
+
+#define VP_CHAIN_MAX_STAGES 16
+#define VP_CABLE_SLOTS  0  /* a link hands a list over with vp_tx_rebatch */
+#define VP_CABLE_STREAM 1  /* ... as a packed stream: vp_tx_pack, then vp_rx_unpack */
+
+typedef struct vp_chain vp_chain;
+
+/* What stage `from` sends to its port out_port arrives at stage `to` on port
+ * in_port. */
+typedef struct vp_chain_link {
+  uint32_t from, out_port, to, in_port;
+} vp_chain_link;
+
+/* What stage `stage` sends to its unlinked port `port` leaves the composite
+ * box on ext_port (vp_chain_process_device). */
+typedef struct vp_chain_exit {
+  uint32_t stage, port, ext_port;
+} vp_chain_exit;
+
+typedef struct vp_chain_config {
+  vp_ctx *const *stages;      /* n_stages contexts on one GPU, in chain order */
+  uint32_t n_stages;
+  const vp_chain_link *links; /* n_links entries; may be NULL iff n_links == 0 */
+  uint32_t n_links;
+  const vp_chain_exit *exits; /* n_exits entries; may be NULL iff n_exits == 0 */
+  uint32_t n_exits;
+  uint32_t cable;             /* VP_CABLE_SLOTS or VP_CABLE_STREAM */
+} vp_chain_config;
+
+/* One stage's batch as the last run left it; every pointer a device pointer. */
+typedef struct vp_chain_view {
+  uint32_t n, slot;        /* packets the stage received (0: nothing reached it) */
+  uint8_t *frames;         /* n * slot bytes, as the stage left them */
+  const uint16_t *len;
+  const uint16_t *out_dev; /* the stage's own out ports */
+  const uint16_t *in_dev;  /* per-packet in port (stage 0 with a port array, a stage
+                              with several inbound links), or NULL: every packet
+                              arrived on in_port */
+  uint32_t in_port;
+  const int64_t *now;      /* per-packet time; NULL at stage 0 with affine time */
+  const uint32_t *origin;  /* each packet's index in the caller's batch; NULL at
+                              stage 0: origin(k) = k */
+} vp_chain_view;
+
+/* Make a chain of cfg->n_stages contexts. Nothing of cfg is kept: the arrays
+ * may be freed when the call returns; the contexts must outlive the chain.
+ * Every stage but 0 has one to VP_TX_MERGE_MAX inbound links. A stage with
+ * several sees their packets merged by origin (each packet's index in the
+ * chain's input), as cables into one box would deliver them; copies of one
+ * input packet (floods, or a packet that arrives through two branches) arrive
+ * in the order of the stage's inbound links in `links`. That is the order of
+ * boxes that push each packet through all their cables before the next
+ * whenever `links` is written in depth-first order, and only then. Packets a
+ * stage sends to a port without a link have left the chain: they stay in that
+ * stage's view with their out port.
+ * With VP_CABLE_STREAM every stage that has one inbound link is fed through a
+ * packed stream: the stream carries min(len, slot) bytes of a frame, so the
+ * target sees zeros where the source slot held bytes past the frame's length.
+ * Stages with several inbound links keep vp_tx_merge.
+ * VP_EINVAL, in this order, the first five before any context is read: a NULL
+ * cfg or out; n_stages == 0 or above VP_CHAIN_MAX_STAGES; a NULL stages, a
+ * NULL links with n_links > 0 or a NULL exits with n_exits > 0; a NULL stage;
+ * an unknown cable; stages on different GPUs, or one with more than
+ * VP_MAX_DEVICES devices; a link that names a stage outside the chain, goes
+ * backward (to <= from), leaves from a port its stage does not have, or
+ * arrives on a port above 0xFFFF; a stage with more than VP_TX_MERGE_MAX
+ * inbound links; a stage after 0 without one; an out port that feeds a stage
+ * with several inbound links and is named by another link as well; an exit
+ * that names a stage or a port the chain does not have, a linked port, or an
+ * ext_port above 0xFFFF. From the GPU check on, vp_last_error() names the
+ * offending stage, link or exit. VP_ENOTSUP: a stage attached to a multi-GPU
+ * communicator (vp_attach_*). VP_ENOMEM: no host or device memory for the
+ * chain's own bookkeeping. */
+int vp_chain_create(const vp_chain_config *cfg, vp_chain **out);
+
+/* Frees what the chain owns. The stages' contexts stay the caller's. A run
+ * that succeeded ended drained, so the stream it was given plays no part
+ * here and may be gone; only after a run that failed part-way, which may have
+ * left work queued, is that run's stream waited for first: it must then still
+ * exist at the next run and here. NULL: nothing. */
+void vp_chain_destroy(vp_chain *ch);
+
+/* One batch through the chain. Reads batch->frames, slot, n, len, in_dev (or
+ * in_port) and the time; batch->out_dev is neither read nor written. Stage 0
+ * processes the caller's batch in place (vp_process_device); its out ports go
+ * into a buffer of the chain's own, cleared first. Then, for every stage in
+ * order that has a link and received packets: vp_tx_build over its out ports;
+ * one read of offset[] to the host, the one host synchronisation per stage (a
+ * list that outgrew idx -- floods -- is built again with room); per linked
+ * port vp_tx_rebatch into buffers the chain owns (VP_CABLE_STREAM: one
+ * vp_tx_pack of all the lists with pos, then vp_rx_unpack per linked port);
+ * vp_process_device of the target with every packet on the link's in_port and
+ * the gathered per-packet times. A stage with several inbound links gets its
+ * input when it is reached, after every earlier stage ran: one vp_tx_merge
+ * over its links' lists in `links` order, each source keyed by its stage's
+ * origins (stage 0: NULL), then vp_process_device with the merged per-packet
+ * ports and times. Origins are 32 bits: behind stage 0 a link's src[], at a
+ * merged stage the merge's key[], elsewhere origin_s[src[k]] composed by one
+ * kernel (0xFFFFFFFF for a src outside the source batch, which vp_tx_return
+ * counts as bad_home and never writes through).
+ * Everything is enqueued on `stream` (NULL: stage 0's own), and the call
+ * returns after the results are in device memory. State persists across calls
+ * in the stages' contexts. The chain keeps its buffers from call to call and
+ * replaces them by larger ones on demand; it waits for the stream before it
+ * frees one, and a run that follows one that failed part-way first waits for
+ * the failed run's stream. n == 0: returns 0, nothing is written, every view is empty.
+ * VP_EINVAL: a NULL ch or batch; with n > 0 a NULL frames or len, a slot below
+ * 64 or not a multiple of 16, frames not 16-byte aligned; in_dev NULL and
+ * in_port > 0xFFFF. A failing stage's code is returned as it is; the views
+ * are then undefined until the next run that succeeds. */
+int vp_chain_run(vp_chain *ch, const vp_dev_batch *batch, void *stream);
+
+/* Stage `stage`'s batch as the last vp_chain_run or vp_chain_process_device
+ * left it. Stage 0's frames, len, in_dev and now are the caller's; everything
+ * else is the chain's own memory: valid until the next run or until
+ * vp_chain_destroy. n == 0 (and every pointer NULL) for a stage nothing
+ * reached, and before the first run. VP_EINVAL: a NULL ch or out; a stage the
+ * chain does not have. */
+int vp_chain_view_get(vp_chain *ch, uint32_t stage, vp_chain_view *out);
+
+/* The chain where one NF stands: vp_process_device's batch, and afterwards the
+ * caller's batch as one box holding the whole chain would leave it -- frames
+ * rewritten in place, out_dev[i] a port of the composite box (the exits) or,
+ * for a drop, packet i's own in port. Does vp_chain_run, then one vp_tx_return
+ * per stage that received packets, in ascending order, into the caller's
+ * batch: home = the stage's origins (stage 0: the in-place form), the actions
+ *   a linked port            VP_RET_SKIP (the packet travelled on; the stage
+ *                            it reached has the later word)
+ *   an exit                  its ext_port
+ *   any other port, a drop,
+ *   a port the stage lacks   VP_RET_DROP
+ *   VP_FLOOD_FRAME           VP_FLOOD_FRAME where every port of the stage is
+ *                            an exit; otherwise VP_RET_SKIP at stage 0 (a
+ *                            stage that a copy reached decides) and
+ *                            VP_RET_DROP later
+ * A later stage's return overrides an earlier one's for the same packet; of
+ * the copies one stage holds of a packet the first counts. Writes
+ * batch->out_dev, which the caller owns. The known limit: a packet that stage
+ * 0 flooded and no copy of which reached a later stage is not written: its
+ * out_dev keeps the caller's value. *stats (host memory, or NULL) receives the
+ * stages' vp_tx_return_stats summed: one device-to-host copy of all stages'
+ * 40 bytes at the end, no kernel. Returns after the results are in device
+ * memory. n == 0: returns 0, nothing is written, *stats zero.
+ * VP_EINVAL: what vp_chain_run rejects; a NULL out_dev with n > 0. */
+int vp_chain_process_device(vp_chain *ch, const vp_dev_batch *batch,
+                            vp_tx_return_stats *stats, void *stream);
+
 /* Host memory the GPU may read and write frames in directly: a DPDK mbuf
  * pool's memory (the hugepages rte_pktmbuf_pool_create, nf.c:235-242, lays
  * the mbufs out in), registered once after the pool is created. Page-locked
@@ -829,8 +982,10 @@ typedef struct vp_serve_expiry_stats {
 int vp_serve_expiry_stats_get(vp_ctx *ctx, vp_serve_expiry_stats *out);
 
 /* Why the calling thread's last failing vp_* call failed: the HIP error and
- * the call site for VP_EIO / VP_ENOMEM, the broken invariant for VP_ESTATE
- * ("" if none was recorded). The text stays until the thread's next failure. */
+ * the call site for VP_EIO / VP_ENOMEM, the broken invariant for VP_ESTATE,
+ * the offending stage, link or exit for a configuration vp_chain_create
+ * refused ("" if none was recorded). The text stays until the thread's next
+ * failure that records one. */
 const char *vp_last_error(void);
 
 /* Per-context kernel timing (diagnostics, off by default): with on != 0,

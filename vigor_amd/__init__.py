@@ -119,6 +119,36 @@ class TxMergedC(C.Structure):
                 ("count", C.c_void_p)]
 
 
+CHAIN_MAX_STAGES = 16  # VP_CHAIN_MAX_STAGES
+CABLE_SLOTS, CABLE_STREAM = 0, 1  # VP_CABLE_SLOTS, VP_CABLE_STREAM
+
+
+class ChainLinkC(C.Structure):
+    """vp_chain_link (include/vigpath.h)."""
+    _fields_ = [("from", C.c_uint32), ("out_port", C.c_uint32), ("to", C.c_uint32),
+                ("in_port", C.c_uint32)]
+
+
+class ChainExitC(C.Structure):
+    """vp_chain_exit (include/vigpath.h)."""
+    _fields_ = [("stage", C.c_uint32), ("port", C.c_uint32), ("ext_port", C.c_uint32)]
+
+
+class ChainConfigC(C.Structure):
+    """vp_chain_config (include/vigpath.h): host pointers."""
+    _fields_ = [("stages", C.POINTER(C.c_void_p)), ("n_stages", C.c_uint32),
+                ("links", C.POINTER(ChainLinkC)), ("n_links", C.c_uint32),
+                ("exits", C.POINTER(ChainExitC)), ("n_exits", C.c_uint32),
+                ("cable", C.c_uint32)]
+
+
+class ChainViewC(C.Structure):
+    """vp_chain_view (include/vigpath.h): device pointers."""
+    _fields_ = [("n", C.c_uint32), ("slot", C.c_uint32), ("frames", C.c_void_p),
+                ("len", C.c_void_p), ("out_dev", C.c_void_p), ("in_dev", C.c_void_p),
+                ("in_port", C.c_uint32), ("now", C.c_void_p), ("origin", C.c_void_p)]
+
+
 # packets per block of vp_tx_build's kernels (vp_tx.hip kTxBlockPackets)
 TX_BLOCK_PACKETS = 2048
 
@@ -212,7 +242,8 @@ EXPORTS = ["vp_nat_create", "vp_bridge_create", "vp_lb_create", "vp_fw_create",
            "vp_last_stage_ms", "vp_stage_ms", "vp_comm_abort", "vp_probe_slots",
            "vp_probe_slots_w", "vp_process_one", "vp_last_kernel", "vp_serve_stats_get",
            "vp_serve_expiry_stats_get", "vp_tx_build", "vp_tx_pack", "vp_tx_rebatch",
-           "vp_tx_merge", "vp_rx_unpack", "vp_tx_return"]
+           "vp_tx_merge", "vp_rx_unpack", "vp_tx_return", "vp_chain_create", "vp_chain_destroy",
+           "vp_chain_run", "vp_chain_view_get", "vp_chain_process_device"]
 
 _libs = {}
 
@@ -331,6 +362,17 @@ def lib(path: str | None = None):
     L.vp_tx_return.argtypes = [C.c_void_p, C.POINTER(DevBatchC), C.POINTER(DevBatchC),
                                C.POINTER(TxWayHomeC), C.c_void_p]
     L.vp_tx_return.restype = C.c_int
+    L.vp_chain_create.argtypes = [C.POINTER(ChainConfigC), C.POINTER(C.c_void_p)]
+    L.vp_chain_create.restype = C.c_int
+    L.vp_chain_destroy.argtypes = [C.c_void_p]
+    L.vp_chain_destroy.restype = None
+    L.vp_chain_run.argtypes = [C.c_void_p, C.POINTER(DevBatchC), C.c_void_p]
+    L.vp_chain_run.restype = C.c_int
+    L.vp_chain_view_get.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(ChainViewC)]
+    L.vp_chain_view_get.restype = C.c_int
+    L.vp_chain_process_device.argtypes = [C.c_void_p, C.POINTER(DevBatchC),
+                                          C.POINTER(TxReturnStatsC), C.c_void_p]
+    L.vp_chain_process_device.restype = C.c_int
     L.vp_last_error.argtypes = []
     L.vp_last_error.restype = C.c_char_p
     _libs[path] = L
@@ -357,6 +399,7 @@ def _check(rc: int, what: str, L=None):
 
 from .nf import Bridge, Fw, Lb, Nat, NfBase, Pol  # noqa: E402,F401
 from .chain import Chain  # noqa: E402,F401
+from .cchain import CChain  # noqa: E402,F401
 from .config import (bridge_config_from_args, fw_config_from_args,  # noqa
                      lb_config_from_args, nat_config_from_args,
                      pol_config_from_args)
