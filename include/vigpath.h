@@ -494,6 +494,84 @@ typedef struct vp_rx_stream {
  * overlapping. n == 0: count 0, nothing else written. */
 int vp_rx_unpack(vp_ctx *ctx, const vp_rx_stream *in, const vp_tx_next *out, void *stream);
 
+#define VP_RX_MERGE_MAX 8
+
+typedef struct vp_rx_queue {
+  vp_rx_stream stream;  /* exactly vp_rx_unpack's input, every field with its meaning there */
+  uint32_t     in_port; /* port these frames arrived on (<= 0xFFFF) */
+} vp_rx_queue;
+
+/* Merge several receive queues by time into one NF's device batch: a box with
+ * several ports gets one packed stream per port, each with its own len[] and
+ * times, and the NF's result depends on how their packets interleave. nf.c
+ * polls its devices in turn and stamps each packet; this call gives the batch
+ * that loop would have handed the NF, for streams already in device memory.
+ * What vp_rx_unpack does for one stream, for n_queues of them, ordered by each
+ * frame's 64-bit time, with the port of each packet beside it. Reads, of every
+ * queue, data, pos, sel, len and now (device memory); writes nothing but out's
+ * buffers. The output struct is vp_tx_merged as vp_tx_merge fills it, except
+ * that out->key must be NULL: a time is 64 bits and comes out in out->now.
+ * Entry (j, e), e < n_j, of queue j has m, L, p(e), r and "readable" exactly as
+ * vp_rx_unpack defines them for queues[j].stream. Its key is the signed 64-bit
+ * time
+ *   t(j, e) = now_j[m], or now0_j + m * now_step_j (64 bits) when now_j is NULL
+ *   t(j, e) = INT64_MAX when m >= meta_n_j (nothing is read through such an m)
+ * and all 64 bits are compared, as signed values. The output holds every entry
+ * of every queue ordered by time, ascending; among equal times by queue number
+ * j, ascending (nf.c polls its devices in ascending order); within one queue in
+ * entry order e. Equivalently entry (j, e) with time t stands at position
+ *   p = e + sum over j' < j of #{e' : t(j', e') <= t}
+ *         + sum over j' > j of #{e' : t(j', e') <  t}
+ * which is that stable merge provided every queue's times do not decrease
+ * along its entries. The precondition is the caller's. Where times do decrease
+ * the order is unspecified, but the call still reads nothing outside the
+ * queues' arrays and writes nothing at or beyond min(total, cap) of any output
+ * buffer.
+ * The call writes *count = total = the sum of all n_j, always the true sum,
+ * also when it exceeds out->cap (0xFFFFFFFF where the sum passes 32 bits), and
+ * for every position p < min(total, out->cap), with (j, e) the entry that
+ * stands there:
+ *   frames[p*slot .. (p+1)*slot)   the slot as vp_rx_unpack writes it: readable,
+ *                                  data_j[p(e) .. p(e) + r) and zeros behind,
+ *                                  the bytes of the last 16-byte unit past L
+ *                                  cleared; not readable, a zero slot, and
+ *                                  nothing is read from data_j for it
+ *   len[p] = L                     unchanged, not clipped to a slot; 0 when not
+ *                                  readable
+ *   now[p] = t(j, e)               ALSO FOR AN ENTRY THAT IS NOT READABLE: the
+ *                                  one deliberate difference from vp_rx_unpack,
+ *                                  which stores 0 there. A broken frame must not
+ *                                  make the batch's clock go back (the process
+ *                                  call refuses such a batch); it is a packet of
+ *                                  length 0 at its own time
+ *   in_dev[p] = queues[j].in_port  when out->in_dev is not NULL
+ *   src[p] = m,  which[p] = j
+ * Nothing at or beyond entry min(total, out->cap) of any buffer is written. The
+ * result is deterministic. Times that do not go back inside every queue give
+ * times that do not go back; the output is a valid vp_dev_batch for `ctx` with
+ * in_dev = out->in_dev. With one queue whose entries are all readable, frames,
+ * len, now and src hold exactly vp_rx_unpack's bytes.
+ * `ctx` is the receiving NF's context; it supplies the GPU, the default stream
+ * and the workspace. The work is enqueued on `stream` (NULL: ctx's own), after
+ * the work already there, and the call MAY RETURN BEFORE IT RAN: two kernel
+ * launches (the ranks with the small records, then the frames), and before
+ * them two per queue without pos (its padded lengths summed per wave and
+ * scanned, as in vp_rx_unpack); the first grid is sized from the n_j, the second
+ * from min(total, out->cap), at least one block so that count is written. It
+ * makes no host round trip. The library orders its own workspace (each
+ * position's place in its stream, 8 bytes, and the sums) between streams. Like
+ * its neighbours it ends ctx's resident kernel, and after a multi-GPU attach it
+ * is local to the rank.
+ * VP_EINVAL (vp_last_error says which): a NULL ctx, queues, out or count;
+ * n_queues == 0 or above VP_RX_MERGE_MAX; per queue everything vp_rx_unpack
+ * rejects for its stream (a NULL data with bytes > 0; data not 16-byte aligned;
+ * a NULL len with meta_n > 0; [data, + bytes) overlapping [out->frames, + cap *
+ * slot)); in_port > 0xFFFF; out->key not NULL; out->slot below 64 or not a
+ * multiple of 16; out->frames not 16-byte aligned; a NULL out->frames, len, src
+ * or which with out->cap > 0. */
+int vp_rx_merge(vp_ctx *ctx, const vp_rx_queue *queues, uint32_t n_queues,
+                const vp_tx_merged *out, void *stream);
+
 /* ----------------------------------------------------------- the way home --
  * A chain of NFs standing where one NF stands: the packets a later stage
  * received come back to the slots they started from in the caller's batch,

@@ -2,7 +2,7 @@
 beside the bytes the algorithm has to move. Run by hand; not part of bench.py.
 
   python3 tools/bench_tx.py [--packets 16777216] [--reps 20] [--step-ms MS] [--pack]
-                             [--rebatch] [--merge] [--unpack] [--return]
+                             [--rebatch] [--merge] [--unpack] [--return] [--rxmerge]
 
 Three cases:
   two-port         vignat's headline outputs: every packet from port 0 (one
@@ -58,6 +58,19 @@ copy of the same slot bytes. Algorithmic bytes of a return: each slot read and
 written, 6 B per entry read (home, out) and 2 B written (the home out port):
 the rebatch's slot bytes with the index on the write side, and 8 B of
 per-entry arrays where the rebatch has 28.
+--rxmerge: after a case's lists are built and packed as for --unpack,
+vp_rx_merge of (a) the two port streams of the two-port case
+and (b) the streams of ports 1 to 3 of the four-port flood pattern, each with
+sel and the batch's time array (so the merge is by packet index, a flooded
+packet's three copies tying), into 64-byte slots with len[], now[], in_dev[],
+src[] and which[], once with pos and once without (every queue's sizes and
+scan launches included); beside them, in the same run and on the same stream,
+vp_rx_unpack of the same entries as one stream (with pos) and a plain
+device-to-device copy of the same slot bytes. Algorithmic bytes of a merge:
+the streams read, each slot written; per entry sel, now and pos read (20),
+which, src, in_dev, now and the position record written (23), which, src and
+the record read back (13), len read and written (4): 60 B; the binary
+searches' reads come on top and are not counted.
 --step-ms: the headline step (bench.py's ms_per_step of the same session);
 every time is then also given as a fraction of it.
 """
@@ -386,6 +399,102 @@ def measure_unpack(nf, nd, lens, idx, off, total, port, reps, dev):
             "bytes_over_copy_bytes": round(alg / (2 * count * slot), 3) if count else None}
 
 
+def measure_rxmerge(nf, nd, lens, idx, off, total, ports, reps, dev):
+    """vp_rx_merge of the packed streams of `ports` (vp_tx_pack with pos over
+    64-byte slots; sel and the batch's time array per queue) into 64-byte slots,
+    with pos and without; beside them, on the same stream, vp_rx_unpack of the
+    same entries as one stream and a plain copy of the same slot bytes."""
+    n, slot = lens.numel(), 64
+    frames = torch.randint(0, 256, (n * slot,), dtype=torch.uint8, device=dev)
+    now = torch.arange(n, dtype=torch.int64, device=dev) + T.NOW0
+    bounds = off.cpu().numpy().view(np.uint32)
+    assert list(ports) == list(range(ports[0], ports[-1] + 1))
+    lo, hi = int(bounds[ports[0]]), int(bounds[ports[-1] + 1])
+    count = hi - lo
+    idx = idx[:total] if total else None
+    po = torch.zeros(nd + 1, dtype=torch.int64, device=dev)
+    pos = torch.zeros(max(total, 1), dtype=torch.int64, device=dev)
+    data = torch.zeros(max(total, 1) * slot, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()  # (torch filled the buffers on its own stream)
+    nf.tx_pack(frames, slot, lens, idx, off, data, po, pos[:total] if total else None)
+    torch.cuda.synchronize()
+    p_off = po.cpu().numpy().view(np.uint64)
+    payload = int(p_off[nd])
+    assert payload <= data.numel() and int(lens.max()) <= slot
+    cap = max(count, 1)
+    o_f = torch.zeros(cap * slot, dtype=torch.uint8, device=dev)
+    o_l = torch.zeros(cap, dtype=torch.int16, device=dev)
+    o_n = torch.zeros(cap, dtype=torch.int64, device=dev)
+    o_i = torch.zeros(cap, dtype=torch.int16, device=dev)
+    o_s = torch.zeros(cap, dtype=torch.int32, device=dev)
+    o_w = torch.zeros(cap, dtype=torch.uint8, device=dev)
+    cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+    src = torch.randint(0, 256, (cap * slot,), dtype=torch.uint8, device=dev)
+    dst = torch.empty_like(src)
+
+    def queues(with_pos):
+        qs = []
+        for k, p in enumerate(ports):
+            a, b = int(bounds[p]), int(bounds[p + 1])
+            d = data[:payload] if with_pos else data[int(p_off[p]):int(p_off[p + 1])]
+            qs.append(dict(data=d, lens=lens, in_port=k, now=now, n=b - a,
+                           sel=idx[a:b] if b > a else None,
+                           pos=pos[a:b] if with_pos and b > a else None))
+        return qs
+
+    def verify():
+        # a sanity check of the run, not the test (tests/test_rxmerge_gpu.py):
+        # the times ascend, and the first entries hold the frames src[] names
+        assert int(cnt.cpu()[0]) == count
+        k = min(count, 4096)
+        if k:
+            assert bool((o_n[1:count] >= o_n[:count - 1]).all())
+            i = o_s[:k].long()
+            want = frames.view(n, slot)[i].clone()
+            want[torch.arange(slot, device=dev)[None, :] >= lens[i].long()[:, None]] = 0
+            assert bool((o_f[:k * slot].view(k, slot) == want).all())
+            assert bool((o_l[:k] == lens[i]).all()) and bool((o_n[:k] == now[i]).all())
+        o_f.zero_()
+        o_n.zero_()
+        torch.cuda.synchronize()
+
+    s = torch.cuda.Stream(device=dev)
+    q_pos, q_np = queues(True), queues(False)
+    torch.cuda.synchronize()
+    ms = timed(s, reps, lambda: nf.rx_merge(q_pos, o_f, slot, o_l, cnt, o_s, o_w, out_now=o_n,
+                                            out_in_dev=o_i, stream=s))
+    verify()
+    ms_np = timed(s, reps, lambda: nf.rx_merge(q_np, o_f, slot, o_l, cnt, o_s, o_w, out_now=o_n,
+                                               out_in_dev=o_i, stream=s))
+    verify()
+    # the same entries as one stream: the stretch of idx[] and pos[] the ports fill
+    ms_up = timed(s, reps, lambda: nf.rx_unpack(
+        data[:payload], lens, o_f, slot, o_l, cnt, pos=pos[lo:hi] if count else None,
+        sel=idx[lo:hi] if count else None, out_now=o_n, out_src=o_s, now=now, n=count, stream=s))
+    ms_cp = timed(s, reps, lambda: dst.copy_(src))
+    stream_bytes = int(p_off[ports[-1] + 1] - p_off[ports[0]])
+    alg = stream_bytes + count * slot + 60 * count
+    med, med_np, med_up, med_cp = (x[len(x) // 2] for x in (ms, ms_np, ms_up, ms_cp))
+    return {"ports": list(ports), "entries_merged": count, "slot_bytes": count * slot,
+            "stream_bytes": stream_bytes,
+            "rxmerge_ms_median": round(med, 4), "rxmerge_ms_min": round(ms[0], 4),
+            "rxmerge_ms_max": round(ms[-1], 4),
+            "rxmerge_no_pos_ms_median": round(med_np, 4),
+            "rxmerge_no_pos_ms_min": round(ms_np[0], 4),
+            "rxmerge_no_pos_ms_max": round(ms_np[-1], 4),
+            "unpack_ms_median": round(med_up, 4), "unpack_ms_min": round(ms_up[0], 4),
+            "unpack_ms_max": round(ms_up[-1], 4),
+            "copy_ms_median": round(med_cp, 4), "copy_ms_min": round(ms_cp[0], 4),
+            "copy_ms_max": round(ms_cp[-1], 4),
+            "rxmerge_over_unpack": round(med / med_up, 3) if med_up else None,
+            "rxmerge_no_pos_over_unpack": round(med_np / med_up, 3) if med_up else None,
+            "rxmerge_over_copy": round(med / med_cp, 3) if med_cp else None,
+            "rxmerge_no_pos_over_copy": round(med_np / med_cp, 3) if med_cp else None,
+            "unpack_over_copy": round(med_up / med_cp, 3) if med_cp else None,
+            "rxmerge_alg_bytes": alg,
+            "bytes_over_copy_bytes": round(alg / (2 * count * slot), 3) if count else None}
+
+
 def measure_return(nf, nd, lens, idx, off, total, port, reps, dev):
     """vp_tx_return of list `port`'s rebatched batch (64-byte slots) into the
     source batch's slots, home = the rebatch's src[]; beside it, on the same
@@ -481,6 +590,10 @@ def main():
     ap.add_argument("--return", action="store_true",
                     help="also time vp_tx_return of port 1's rebatched batch into the source "
                          "batch's slots, beside vp_tx_rebatch and a plain copy")
+    ap.add_argument("--rxmerge", action="store_true",
+                    help="also time vp_rx_merge of the two-port case's two packed streams and "
+                         "of three streams of the flood pattern, with and without pos, beside "
+                         "vp_rx_unpack of the same entries and a plain copy")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     n = args.packets
@@ -546,6 +659,16 @@ def main():
             if args.step_ms:
                 p["headline_step_ms"] = args.step_ms
                 p["fraction_of_step"] = round(p["return_ms_median"] / args.step_ms, 4)
+            print(json.dumps(p), flush=True)
+        if args.rxmerge and name != "two-port-drop16":
+            idx, off, total = lists
+            ports = [0, 1] if nd == 2 else [1, 2, 3]
+            p = {"case": name + "-rxmerge", "packets": n, "n_devices": nd, "entries": total,
+                 "reps": args.reps,
+                 **measure_rxmerge(nf, nd, ln, idx, off, total, ports, args.reps, dev)}
+            if args.step_ms:
+                p["headline_step_ms"] = args.step_ms
+                p["fraction_of_step"] = round(p["rxmerge_ms_median"] / args.step_ms, 4)
             print(json.dumps(p), flush=True)
         del lists
         torch.cuda.empty_cache()

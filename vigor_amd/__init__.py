@@ -88,6 +88,12 @@ class RxStreamC(C.Structure):
 
 
 TX_MERGE_MAX = 8  # VP_TX_MERGE_MAX
+RX_MERGE_MAX = 8  # VP_RX_MERGE_MAX
+
+
+class RxQueueC(C.Structure):
+    """vp_rx_queue (include/vigpath.h): one stream of a vp_rx_merge call."""
+    _fields_ = [("stream", RxStreamC), ("in_port", C.c_uint32)]
 
 RET_SKIP, RET_DROP = 0x10000, 0x10001  # VP_RET_SKIP, VP_RET_DROP
 
@@ -242,7 +248,7 @@ EXPORTS = ["vp_nat_create", "vp_bridge_create", "vp_lb_create", "vp_fw_create",
            "vp_last_stage_ms", "vp_stage_ms", "vp_comm_abort", "vp_probe_slots",
            "vp_probe_slots_w", "vp_process_one", "vp_last_kernel", "vp_serve_stats_get",
            "vp_serve_expiry_stats_get", "vp_tx_build", "vp_tx_pack", "vp_tx_rebatch",
-           "vp_tx_merge", "vp_rx_unpack", "vp_tx_return", "vp_chain_create", "vp_chain_destroy",
+           "vp_tx_merge", "vp_rx_unpack", "vp_rx_merge", "vp_tx_return", "vp_chain_create", "vp_chain_destroy",
            "vp_chain_run", "vp_chain_view_get", "vp_chain_process_device"]
 
 _libs = {}
@@ -359,6 +365,9 @@ def lib(path: str | None = None):
     L.vp_rx_unpack.argtypes = [C.c_void_p, C.POINTER(RxStreamC), C.POINTER(TxNextC),
                                C.c_void_p]
     L.vp_rx_unpack.restype = C.c_int
+    L.vp_rx_merge.argtypes = [C.c_void_p, C.POINTER(RxQueueC), C.c_uint32,
+                              C.POINTER(TxMergedC), C.c_void_p]
+    L.vp_rx_merge.restype = C.c_int
     L.vp_tx_return.argtypes = [C.c_void_p, C.POINTER(DevBatchC), C.POINTER(DevBatchC),
                                C.POINTER(TxWayHomeC), C.c_void_p]
     L.vp_tx_return.restype = C.c_int

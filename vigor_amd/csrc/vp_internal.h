@@ -103,6 +103,7 @@ hipError_t preload_txpack(hipStream_t s);
 hipError_t preload_txbatch(hipStream_t s);
 hipError_t preload_txmerge(hipStream_t s);
 hipError_t preload_rxunpack(hipStream_t s);
+hipError_t preload_rxmerge(hipStream_t s);
 hipError_t preload_txreturn(hipStream_t s);
 hipError_t preload_chain(hipStream_t s);
 
@@ -288,9 +289,10 @@ struct Workspace {
   uint16_t *in_fill = nullptr;  // a batch's one port as an array (vp_dev_batch.in_port)
   size_t in_fill_n = 0;
   // vp_tx_build's entries per block and port (u32), vp_tx_pack's padded bytes
-  // per block, vp_rx_unpack's per wave (u64): one buffer per call, which may
-  // be in flight on different streams together
-  CallBuf tx_cnt, txp_sum, rxu_sum;
+  // per block, vp_rx_unpack's per wave (u64), vp_rx_merge's frame position per
+  // output position and its queues' sums per wave (u64): one buffer per call,
+  // which may be in flight on different streams together
+  CallBuf tx_cnt, txp_sum, rxu_sum, rxm_rec;
   // tbl_new_keys_unsorted: the tagged key set (3 x u64 per slot, never
   // reset: a slot of an older tag is empty), its tag, first-sighting bits
   // per position and their scan, the first sightings' miss ordinals and

@@ -203,7 +203,7 @@ static int preload_units(int gpu, hipStream_t s) {
   for (auto f : {preload_runtime, preload_table, preload_nat, preload_bridge, preload_lb,
                  preload_fw, preload_pol, preload_comm, preload_mbuf, preload_tx,
                  preload_txpack, preload_txbatch, preload_txmerge, preload_rxunpack,
-                 preload_txreturn, preload_chain})
+                 preload_rxmerge, preload_txreturn, preload_chain})
     VP_HIP(f(s));
   VP_HIP(hipStreamSynchronize(s));
   done.push_back(gpu);
@@ -259,7 +259,7 @@ static void free_all(vp_ctx *c) {
                   w.reply2,  w.rreply2,  w.lcnt, w.nkset, w.nkbits, w.nkpre,
                   w.nkfirst, w.nkcnt, w.in_fill};
   for (void *p : ptrs) hipFree(p);
-  for (CallBuf *b : {&w.tx_cnt, &w.txp_sum, &w.rxu_sum}) {
+  for (CallBuf *b : {&w.tx_cnt, &w.txp_sum, &w.rxu_sum, &w.rxm_rec}) {
     hipFree(b->p);
     if (b->ev) hipEventDestroy(b->ev);
   }

@@ -38,36 +38,6 @@ VP_PRELOAD_UNIT(rxunpack)
 // a frame's padded length is at most 65536 (len is 16 bits)
 static_assert((uint64_t)kSlotPerWave * 65536u < (1ull << 32), "a wave's sum in 32 bits");
 
-struct RxuArgs {
-  const uint8_t *data;  // the stream
-  uint64_t bytes;
-  const uint64_t *pos;
-  const uint32_t *sel;
-  const uint16_t *len;
-  const int64_t *now;
-  int64_t now0, now_step;
-  uint32_t meta_n;
-  uint32_t m;            // min(n, cap): the entries that are written
-  uint32_t n;
-  const uint64_t *base;  // pos == NULL: every wave's first position (scanned sums)
-  uint8_t *oframes;      // the batch
-  uint32_t oslot;
-  uint16_t *olen;
-  int64_t *onow;
-  uint32_t *osrc;
-  uint32_t *count;
-};
-
-// Entry k's index into len[] / now[] and its length; the length is 0 where the
-// index is outside them, and nothing is read through such an index
-__device__ __forceinline__ void rxu_meta(const RxuArgs &a, uint64_t k, bool mine, uint32_t &mm,
-                                         bool &in, uint32_t &l) {
-  mm = (uint32_t)k;
-  if (mine && a.sel) mm = a.sel[k];
-  in = mine && mm < a.meta_n;
-  l = in ? a.len[mm] : 0u;
-}
-
 __global__ __launch_bounds__(kSlotThreads) void rxu_sizes(const RxuArgs a, uint64_t *sums) {
   const uint32_t tid = threadIdx.x, lane = tid & 63;
   const uint32_t wv = __builtin_amdgcn_readfirstlane(tid >> 6);

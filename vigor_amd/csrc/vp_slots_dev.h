@@ -1,6 +1,6 @@
 // Device code shared by the transmit / receive family (vp_tx.hip,
-// vp_txpack.hip, vp_txbatch.hip, vp_txmerge.hip, vp_rxunpack.hip; DESIGN.md
-// §5.5-§5.10): the block geometry, the small wave and list helpers, and the
+// vp_txpack.hip, vp_txbatch.hip, vp_txmerge.hip, vp_rxunpack.hip,
+// vp_rxmerge.hip): the block geometry, the small wave and list helpers, and the
 // slot mover that writes a turn's 64 entries into consecutive slots.
 #pragma once
 
@@ -167,5 +167,42 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t v, uint32_t e) {
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)e);
   return ((uint64_t)hi << 32) | lo;
 }
+
+// vp_rx_unpack's stream and destination as its kernels take them
+// (vp_rxunpack.hip); vp_rx_merge (vp_rxmerge.hip) fills one per queue without
+// pos[] for rxu_sizes, whose sums, scanned, are every wave's first position.
+struct RxuArgs {
+  const uint8_t *data;  // the stream
+  uint64_t bytes;
+  const uint64_t *pos;
+  const uint32_t *sel;
+  const uint16_t *len;
+  const int64_t *now;
+  int64_t now0, now_step;
+  uint32_t meta_n;
+  uint32_t m;            // min(n, cap): the entries that are written
+  uint32_t n;
+  const uint64_t *base;  // pos == NULL: every wave's first position (scanned sums)
+  uint8_t *oframes;      // the batch
+  uint32_t oslot;
+  uint16_t *olen;
+  int64_t *onow;
+  uint32_t *osrc;
+  uint32_t *count;
+};
+
+// Entry k's index into len[] / now[] and its length; the length is 0 where the
+// index is outside them, and nothing is read through such an index
+__device__ __forceinline__ void rxu_meta(const RxuArgs &a, uint64_t k, bool mine, uint32_t &mm,
+                                         bool &in, uint32_t &l) {
+  mm = (uint32_t)k;
+  if (mine && a.sel) mm = a.sel[k];
+  in = mine && mm < a.meta_n;
+  l = in ? a.len[mm] : 0u;
+}
+
+// Every wave of every block sums the padded lengths of the kSlotPerWave entries
+// below a.m it stands for into sums[block * kSlotWaves + wave]
+__global__ void rxu_sizes(const RxuArgs a, uint64_t *sums);
 
 }  // namespace vp

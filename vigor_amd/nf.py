@@ -13,13 +13,36 @@ import ctypes as C
 import numpy as np
 
 from . import (BridgeConfigC, DevBatchC, FwConfigC, LbConfigC, MAX_DEV, MbufBatchC,
-               NatConfigC, PolConfigC, RxStreamC, ServeExpiryStatsC, ServeStatsC, TableStatsC,
+               NatConfigC, PolConfigC, RX_MERGE_MAX, RxQueueC, RxStreamC, ServeExpiryStatsC, ServeStatsC, TableStatsC,
                TX_MERGE_MAX, TxFramesC, TxListsC, TxMergedC, TxNextC, TxReturnStatsC, TxSourceC,
                TxStatsC, TxWayHomeC, _check, lib)
 
 
 def _dptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _rx_stream(data, lens, pos, sel, now, now0, now_step, n):
+    """vp_rx_stream of rx_unpack's arguments of these names (one queue of
+    rx_merge's)."""
+    meta_n = lens.numel() if lens is not None else 0
+    nbytes = data.numel() if data is not None else 0
+    if n is None:
+        n = sel.numel() if sel is not None else pos.numel() if pos is not None else meta_n
+    if nbytes:
+        assert data.is_cuda and data.element_size() == 1
+    if meta_n:
+        assert lens.is_cuda and lens.element_size() == 2
+    if pos is not None:
+        assert pos.is_cuda and pos.element_size() == 8 and pos.numel() >= n
+    if sel is not None:
+        assert sel.is_cuda and sel.element_size() == 4 and sel.numel() >= n
+    if now is not None:
+        assert now.is_cuda and now.element_size() == 8 and now.numel() == meta_n
+    return RxStreamC(data=_dptr(data) if nbytes else None, bytes=nbytes, n=n,
+                     pos=_dptr(pos) if n else None, sel=_dptr(sel) if n else None,
+                     meta_n=meta_n, len=_dptr(lens) if meta_n else None,
+                     now=_dptr(now) if meta_n else None, now0=now0, now_step=now_step)
 
 
 class NfBase:
@@ -313,21 +336,8 @@ class NfBase:
         each of at least the capacity; count: 32-bit CUDA tensor of one word,
         n afterwards. Enqueued on `stream` (the context's own for None) and
         not waited for."""
-        meta_n = lens.numel() if lens is not None else 0
-        nbytes = data.numel() if data is not None else 0
         cap = out_lens.numel() if out_lens is not None else 0
-        if n is None:
-            n = sel.numel() if sel is not None else pos.numel() if pos is not None else meta_n
-        if nbytes:
-            assert data.is_cuda and data.element_size() == 1
-        if meta_n:
-            assert lens.is_cuda and lens.element_size() == 2
-        if pos is not None:
-            assert pos.is_cuda and pos.element_size() == 8 and pos.numel() >= n
-        if sel is not None:
-            assert sel.is_cuda and sel.element_size() == 4 and sel.numel() >= n
-        if now is not None:
-            assert now.is_cuda and now.element_size() == 8 and now.numel() == meta_n
+        rx = _rx_stream(data, lens, pos, sel, now, now0, now_step, n)
         assert count.is_cuda and count.element_size() == 4 and count.numel() >= 1
         if cap:
             assert out_lens.is_cuda and out_lens.element_size() == 2
@@ -337,16 +347,58 @@ class NfBase:
             assert out_now.is_cuda and out_now.element_size() == 8 and out_now.numel() >= cap
         if out_src is not None:
             assert out_src.is_cuda and out_src.element_size() == 4 and out_src.numel() >= cap
-        rx = RxStreamC(data=_dptr(data) if nbytes else None, bytes=nbytes, n=n,
-                       pos=_dptr(pos) if n else None, sel=_dptr(sel) if n else None,
-                       meta_n=meta_n, len=_dptr(lens) if meta_n else None,
-                       now=_dptr(now) if meta_n else None, now0=now0, now_step=now_step)
         out = TxNextC(frames=_dptr(out_frames) if cap else None, slot=out_slot, cap=cap,
                       len=_dptr(out_lens) if cap else None,
                       now=_dptr(out_now) if cap else None,
                       src=_dptr(out_src) if cap else None, count=count.data_ptr())
         s = C.c_void_p(stream.cuda_stream) if stream is not None else None
         self._ck(self.L.vp_rx_unpack(self.h, C.byref(rx), C.byref(out), s), "vp_rx_unpack")
+
+    def rx_merge(self, queues, out_frames, out_slot, out_lens, count, out_src, out_which,
+                 out_now=None, out_in_dev=None, stream=None):
+        """vp_rx_merge: several packed streams, one per port, as this NF's
+        device batch, merged by each frame's signed 64-bit time (stable: equal
+        times in the order of `queues`, inside a queue in entry order), every
+        slot, len and src as rx_unpack writes them; an entry that is not
+        readable keeps its time. queues: 1 to RX_MERGE_MAX dicts with the keys
+        data, lens, in_port and optionally pos, sel, now, now0, now_step, n --
+        rx_unpack's arguments of those names -- or tuples (data, lens, in_port,
+        pos, sel, now, now0, now_step, n), the tail from `pos` on optional.
+        Every queue's times must not decrease along its entries. out_lens:
+        16-bit CUDA tensor whose length is the capacity in packets (None: 0);
+        out_frames: uint8 CUDA tensor of capacity * out_slot bytes; out_src
+        (32-bit) and out_which (8-bit) are needed with a capacity; out_now
+        (64-bit) and out_in_dev (16-bit) may be None; count: 32-bit CUDA tensor
+        of one word, the queues' true total afterwards. Enqueued on `stream`
+        (this context's own for None) and not waited for."""
+        names = ("data", "lens", "in_port", "pos", "sel", "now", "now0", "now_step", "n")
+        queues = [q if isinstance(q, dict) else dict(zip(names, q)) for q in queues]
+        assert 1 <= len(queues) <= RX_MERGE_MAX
+        cap = out_lens.numel() if out_lens is not None else 0
+        assert count.is_cuda and count.element_size() == 4 and count.numel() >= 1
+        if cap:
+            assert out_lens.is_cuda and out_lens.element_size() == 2
+            assert out_frames.is_cuda and out_frames.element_size() == 1
+            assert out_frames.numel() == cap * out_slot
+            assert out_src.is_cuda and out_src.element_size() == 4 and out_src.numel() >= cap
+            assert out_which.is_cuda and out_which.element_size() == 1
+            assert out_which.numel() >= cap
+        for t, width in ((out_now, 8), (out_in_dev, 2)):
+            if t is not None:
+                assert t.is_cuda and t.element_size() == width and t.numel() >= cap
+        arr = (RxQueueC * len(queues))()
+        for a, q in zip(arr, queues):
+            a.stream = _rx_stream(q["data"], q["lens"], q.get("pos"), q.get("sel"), q.get("now"),
+                                  q.get("now0") or 0, q.get("now_step") or 0, q.get("n"))
+            a.in_port = q["in_port"]
+        out = TxMergedC(frames=_dptr(out_frames) if cap else None, slot=out_slot, cap=cap,
+                        len=_dptr(out_lens) if cap else None,
+                        now=_dptr(out_now) if cap else None,
+                        in_dev=_dptr(out_in_dev) if cap else None, key=None,
+                        src=_dptr(out_src) if cap else None,
+                        which=_dptr(out_which) if cap else None, count=count.data_ptr())
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._ck(self.L.vp_rx_merge(self.h, arr, len(queues), C.byref(out), s), "vp_rx_merge")
 
     def tx_return(self, frames, slot, out, in_dev, home_frames, home_slot, home_out, home_in_dev,
                   ports, on_drop, on_flood, on_bad, home=None, stats=None, stream=None):
