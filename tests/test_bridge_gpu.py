@@ -124,3 +124,24 @@ def test_rejects_bad_config():
         make_pair(cap=1000)
     with pytest.raises(vigor_amd.VigpathError):
         make_pair(statics=[(bytes(6), 0, 1)] * 4096)
+
+
+def test_rebuild_inside_learning_then_forward():
+    """One vp_process_device call that learns enough stations (600 of a
+    1024-entry table, MACs counting up) to switch the table to the
+    allocation-order layout: tbl_new_keys rebuilds the bucket array between
+    bridge_miss_keys and bridge_learn_finish. The second half of the call is
+    addressed to the MACs just learned (bridge_defer_finish reads the moved
+    buckets). The rebuild must happen in this call and the results equal the
+    oracle's."""
+    cap, n_new = 1024, 600  # > cap / 2 live: the linear layout is tried
+    br, o = make_pair(cap=cap)
+    fr, ln, dv, now = T.bridge_trace(2 * n_new, n_new)
+    before = br.table_stats()
+    check_batches(br, o, fr, ln, dv, now, 64, [])
+    after = br.table_stats()
+    assert after["rebuilds"] > before["rebuilds"], (before, after)
+    fr3, ln3, dv3, now3 = T.bridge_trace(3 * n_new, n_new, start=2 * n_new)
+    check_batches(br, o, fr3, ln3, dv3, now3, 64, [1000])
+    check_state(br, o, cap)
+    assert br.live_count() == n_new

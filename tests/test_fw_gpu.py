@@ -171,3 +171,29 @@ def test_multiplicative_home_buckets_reprobe(monkeypatch):
     fr, ln, dv, now = mixed_fw_trace(rng, 5000, 3500)
     check_batches(fw, o, fr, ln, dv, now + 10**8, 64, [2500])
     check_state(fw, o, 4096)
+
+
+def test_rebuild_inside_phase_b_then_phase_c():
+    """One vp_process_device call whose phase B opens enough flows (600 of a
+    1024-flow table, source ports counting up) to switch the table to the
+    allocation-order layout: tbl_new_keys rebuilds the bucket array between
+    fw_miss_keys and fw_miss_finish. The WAN replies to those flows follow in
+    the same call (phase C, fw_defer_finish), so both kernels read the moved
+    buckets. The rebuild must happen in this call and the results equal the
+    oracle's."""
+    cap, n_new = 1024, 600  # > cap / 2 live: the linear layout is tried
+    fw, o = make_pair(max_flows=cap)
+    fr, ln, dv, _ = T.fw_trace(n_new, n_new)
+    idx, z = np.arange(n_new), np.zeros(n_new, np.int64)
+    rep, rl = T.udp_frames(z, T.ip4(10, 0, 0, 0) + z, z, idx)  # flow i's reply
+    fr2 = np.concatenate([fr, rep])
+    ln2 = np.concatenate([ln, rl])
+    dv2 = np.concatenate([dv, np.ones(n_new, np.uint16)])
+    now2 = T.NOW0 + np.arange(2 * n_new, dtype=np.int64)
+    before = fw.table_stats()
+    check_batches(fw, o, fr2, ln2, dv2, now2, 64, [])
+    after = fw.table_stats()
+    assert after["rebuilds"] > before["rebuilds"], (before, after)
+    fr3, ln3, dv3, now3 = T.fw_trace(3 * n_new, n_new, start=2 * n_new, reply_every=3)
+    check_batches(fw, o, fr3, ln3, dv3, now3, 64, [1000])
+    check_state(fw, o, cap)

@@ -127,3 +127,24 @@ def test_steady_state_grouping_path():
         check_batches(pol, o, fr[a * 64:b * 64], ln[a:b], dv[a:b], now[a:b], 64, [])
         assert pol.last_kernel() == k, (a, b, pol.last_kernel())
     check_state(pol, o, 8192)
+
+
+def test_rebuild_inside_phase_b_then_more_packets():
+    """One vp_process_device call that starts policing enough addresses (600
+    of a 1024-entry table, addresses counting up) to switch the table to the
+    allocation-order layout: tbl_new_keys rebuilds the bucket array between
+    pol_miss_keys and pol_miss_finish. Further packets of the same addresses
+    follow in the same call (queued in phase A, finished by pol_defer_finish
+    against the moved buckets, then replayed by pol_buckets). The rebuild must
+    happen in this call and the results equal the oracle's."""
+    cap, n_new = 1024, 600  # > cap / 2 live: the linear layout is tried
+    pol, o = make_pair(cap=cap, burst=1000)
+    fr, ln, dv, now = T.pol_trace(2 * n_new, n_new)
+    ln = (60 + 7 * (np.arange(2 * n_new) % 90)).astype(np.uint16)  # some over the burst
+    before = pol.table_stats()
+    check_batches(pol, o, fr, ln, dv, now, 64, [])
+    after = pol.table_stats()
+    assert after["rebuilds"] > before["rebuilds"], (before, after)
+    fr3, ln3, dv3, now3 = T.pol_trace(3 * n_new, n_new, start=2 * n_new)
+    check_batches(pol, o, fr3, ln3, dv3, now3, 64, [1000])
+    check_state(pol, o, cap)

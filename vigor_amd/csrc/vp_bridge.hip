@@ -29,7 +29,6 @@
 // 0-1 identify the MAC; word 2 carries the DynamicValue (dyn_vals vector in
 // the reference) so one bucket read resolves a lookup.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <cstring>
 #include <vector>
@@ -659,8 +658,7 @@ static int bridge_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   const uint32_t tiles = (p1 - (p0 & ~63u) + 63) / 64;
   const uint32_t grid = bp.on ? bp.grid : resident_grid(bk, (tiles + bw - 1) / bw, 64 * (int)bw);
   // (still zero after a segment that learned nothing: no reset launch)
-  if (!t.ctl_clean) VP_HIP(hipMemsetAsync(&t.ctl->miss_count, 0, 16, c->stream));  // .. touch_ovf
-  t.ctl_clean = false;
+  VP_TRY(seg_reset_counters(c, t));
   VP_HIP(ev_record(c->ktime, c->ev0, c->stream));
   BridgeArgs a1 = a;
   if (bp.on) a1.log = nullptr;
@@ -672,10 +670,7 @@ static int bridge_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   VP_HIP(hipGetLastError());
   VP_HIP(ev_record(c->ktime, c->ev1, c->stream));
   VP_TRY(tbl_fold_read_ctl(c, t, bp, w.log, p0, p1, now, c->seq));
-  float kms = 0.f;
-  VP_HIP(ev_ms(c->ktime, c->ev0, c->ev1, &kms));
-  *ms += kms;
-  *launches += 1;
+  VP_TRY(seg_classify_ms(c, ms, launches));
   const bool ovf = bp.on && t.h_ctl.touch_ovf != 0;
   if (ovf)  // touches that found their bin slice full, logged alone
     VP_TRY(tbl_late_touches(c, t, bp.bins.oent, bp.bins.ocnt, 0, bp.range, bp.grid,
@@ -687,48 +682,35 @@ static int bridge_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   t.ctl_clean = !nmiss && !ovf;
   if (!nmiss) return 0;
 
-  size_t need = 0;
-  hipcub::DeviceRadixSort::SortKeys(nullptr, need, w.miss, w.miss_sorted,
-                                    (int)nmiss, 0, 32, c->stream);
-  VP_TRY(cub_reserve(c, need));
-  VP_HIP(hipcub::DeviceRadixSort::SortKeys(w.cub_tmp, w.cub_bytes, w.miss,
-                                           w.miss_sorted, (int)nmiss, 0, 32,
-                                           c->stream));
-  bridge_miss_keys<<<grid_for(nmiss), 256, 0, c->stream>>>(a, w.miss_sorted, nmiss,
-                                                           w.mkey, w.mhash);
-  VP_HIP(hipGetLastError());
-  VP_TRY(tbl_new_keys(c, t, NewKeys{nmiss, w.miss_sorted}, c->seq, nullptr));
-  a.t = tbl_dev(t);  // a rebuild may have changed the layout
-  bridge_learn_finish<<<grid_for(nmiss), 256, 0, c->stream>>>(
-      a, w.miss_sorted, nmiss, w.scratch, w.rep, w.assign);
-  VP_HIP(hipGetLastError());
+  VP_TRY(phase_b_round(c, t, nmiss, &a.t, [&] {
+    bridge_miss_keys<<<grid_for(nmiss), 256, 0, c->stream>>>(a, w.miss_sorted, nmiss,
+                                                             w.mkey, w.mhash);
+  }, [&] {
+    bridge_learn_finish<<<grid_for(nmiss), 256, 0, c->stream>>>(
+        a, w.miss_sorted, nmiss, w.scratch, w.rep, w.assign);
+  }));
+  // (over the whole segment: the provisional floods addressed to a MAC learned here)
   bridge_defer_finish<<<grid_for(p1 - p0), 256, 0, c->stream>>>(a);
   VP_HIP(hipGetLastError());
   *allocated |= 1u;
   // the learning packets' touches on top of the fold (last toucher wins)
-  VP_TRY(tbl_late_touches(c, t, w.miss_sorted, nullptr, nmiss, 256, (nmiss + 255) / 256,
-                          w.log, now, c->seq));
+  VP_TRY(tbl_late_list(c, t, w.miss_sorted, nmiss, w.log, now, c->seq));
   VP_TRY(read_ctl(c, t));
   return 0;
 }
 
-int bridge_process_device(vp_ctx *c, const vp_dev_batch *b) {
+static int bridge_process_device(vp_ctx *c, const vp_dev_batch *b) {
   ExpiringTable tabs[1] = {{&c->ft, bridge_cutoff}};
   return run_batch(c, b, tabs, 1, bridge_segment);
 }
 
 // ---------------------------------------------------- vp_process_one --
 // vigbridge's launcher of the resident kernel (serve_launch, vp_serve.hip).
-int bridge_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
+static int bridge_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
   BridgeArgs a{};
   bridge_tables(c, &a);
-  const JournalDev j = serve_journal_dev(c, bridge_serve_nf());
-  if (j.ctl)
-    bridge_serve<true><<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags, j);
-  else
-    bridge_serve<false><<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags, j);
-  VP_HIP(hipGetLastError());
-  return 0;
+  return serve_launch_one(c, bridge_serve<true>, bridge_serve<false>, a, dbox, flags,
+                          serve_journal_dev(c, bridge_ops().serve));
 }
 
 // The largest host batch routed to the server as burst requests: the largest
@@ -745,10 +727,21 @@ constexpr uint32_t kBridgeBurstRoute = 384;
 // so one packet sends 12 bytes and takes none back; a burst copies a frame's
 // first 16 bytes in and nothing back. No stage clock. The kernel expires from
 // the touch journal.
-const ServeNf &bridge_serve_nf() {
-  static const ServeNf nf = {bridge_cutoff, &vp_ctx::ft, false,   12,      0,   16, 0,
-                             kBridgeBurstRoute, false,   nullptr, nullptr, true};
-  return nf;
+const NfOps &bridge_ops() {
+  static const NfOps ops = [] {
+    NfOps o{};
+    o.process_device = bridge_process_device;  o.serve_launch = bridge_serve_launch;
+    o.n_devices = [](const vp_ctx *c) -> uint32_t { return c->brg.n_devices; };
+    o.reads_in_port = false;
+    ServeNf &s = o.serve;
+    s.cutoff = bridge_cutoff;  s.table = &vp_ctx::ft;
+    s.one_whole = false;  s.one_in = 12;  s.one_back = 0;
+    s.burst_in = 16;  s.burst_back = 0;  s.burst_route = kBridgeBurstRoute;
+    s.prof = false;  s.journal = true;
+    s.cutoff2 = nullptr;  s.table2 = nullptr;
+    return o;
+  }();
+  return ops;
 }
 
 void build_bridge_tables(std::vector<uint32_t> &tab) {

@@ -21,7 +21,6 @@
 // + padding), the int_devices vector lives in the padding byte positions,
 // and probes compare the protocol byte only (bucket_match<0xFF>).
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstring>
@@ -664,8 +663,7 @@ static int fw_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
     a.tileq = 1;
   }
   // (still zero after a segment that queued nothing: no reset launch)
-  if (!t.ctl_clean) VP_HIP(hipMemsetAsync(&t.ctl->miss_count, 0, 16, c->stream));  // .. reprobe
-  t.ctl_clean = false;
+  VP_TRY(seg_reset_counters(c, t));
   VP_HIP(ev_record(c->ktime, c->ev0, c->stream));
   if (p1 > p0) {
     if (tiles64) {
@@ -695,37 +693,23 @@ static int fw_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   if (ovf)  // touches that found their bin slice full, logged alone
     VP_TRY(tbl_late_touches(c, t, bp.bins.oent, bp.bins.ocnt, 0, range64, grid64,
                             w.log, now, seq0));
-  float kms = 0.f;
-  VP_HIP(ev_ms(c->ktime, c->ev0, c->ev1, &kms));
-  *ms += kms;
-  *launches += 1;
+  VP_TRY(seg_classify_ms(c, ms, launches));
   const uint32_t nmiss = t.h_ctl.miss_count, ndefer = t.h_ctl.defer_count;
   if (nmiss) {
-    size_t need = 0;
-    hipcub::DeviceRadixSort::SortKeys(nullptr, need, w.miss, w.miss_sorted,
-                                      (int)nmiss, 0, 32, c->stream);
-    VP_TRY(cub_reserve(c, need));
-    VP_HIP(hipcub::DeviceRadixSort::SortKeys(w.cub_tmp, w.cub_bytes, w.miss,
-                                             w.miss_sorted, (int)nmiss, 0, 32,
-                                             c->stream));
-    fw_miss_keys<<<grid_for(nmiss), 256, 0, c->stream>>>(a, w.miss_sorted, nmiss,
-                                                         w.mkey, w.mhash);
-    VP_HIP(hipGetLastError());
-    VP_TRY(tbl_new_keys(c, t, NewKeys{nmiss, w.miss_sorted}, c->seq, nullptr));
-    a.t = tbl_dev(t);  // a rebuild may have moved the buckets
-    fw_miss_finish<<<grid_for(nmiss), 256, 0, c->stream>>>(
-        a, w.miss_sorted, nmiss, w.mkey, w.scratch, w.rep, w.assign);
-    VP_HIP(hipGetLastError());
-    VP_TRY(tbl_late_touches(c, t, w.miss_sorted, nullptr, nmiss, 256,
-                            (nmiss + 255) / 256, w.log, now, seq0));
+    VP_TRY(phase_b_round(c, t, nmiss, &a.t, [&] {
+      fw_miss_keys<<<grid_for(nmiss), 256, 0, c->stream>>>(a, w.miss_sorted, nmiss, w.mkey,
+                                                           w.mhash);
+    }, [&] {
+      fw_miss_finish<<<grid_for(nmiss), 256, 0, c->stream>>>(
+          a, w.miss_sorted, nmiss, w.mkey, w.scratch, w.rep, w.assign);
+    }));
+    VP_TRY(tbl_late_list(c, t, w.miss_sorted, nmiss, w.log, now, seq0));
     *allocated |= 1u;
   }
-  if (ndefer) {
-    a.t = tbl_dev(t);  // a rebuild during phase B may have changed the layout
+  if (ndefer) {  // (a.t: phase B's round refreshed it)
     fw_defer_finish<<<grid_for(ndefer), 256, 0, c->stream>>>(a, w.defer, ndefer);
     VP_HIP(hipGetLastError());
-    VP_TRY(tbl_late_touches(c, t, w.defer, nullptr, ndefer, 256, (ndefer + 255) / 256,
-                            w.log, now, seq0));
+    VP_TRY(tbl_late_list(c, t, w.defer, ndefer, w.log, now, seq0));
   }
   if (nmiss || ndefer) VP_TRY(read_ctl(c, t));
   // steady state: frames and ports complete, only the stamp fold may run
@@ -735,27 +719,22 @@ static int fw_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   return 0;
 }
 
-int fw_process_device(vp_ctx *c, const vp_dev_batch *b) {
+static int fw_process_device(vp_ctx *c, const vp_dev_batch *b) {
   ExpiringTable tabs[1] = {{&c->ft, fw_cutoff}};
   return run_batch(c, b, tabs, 1, fw_segment);
 }
 
 // ---------------------------------------------------- vp_process_one --
 // vigfw's launcher of the resident kernel (serve_launch, vp_serve.hip).
-int fw_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
+static int fw_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
   FwArgs a{};
   a.t = tbl_dev(c->ft);
   a.crc_tab = c->crc_tab;
   a.macw = c->macw;
   a.wan = c->fw.wan_device;
   a.n_dev = c->fw.n_devices;
-  const JournalDev j = serve_journal_dev(c, fw_serve_nf());
-  if (j.ctl)
-    fw_serve<true><<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags, j);
-  else
-    fw_serve<false><<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags, j);
-  VP_HIP(hipGetLastError());
-  return 0;
+  return serve_launch_one(c, fw_serve<true>, fw_serve<false>, a, dbox, flags,
+                          serve_journal_dev(c, fw_ops().serve));
 }
 
 // The largest host batch routed to the server as burst requests: the largest
@@ -771,10 +750,21 @@ constexpr uint32_t kFwBurstRoute = 256;
 // bytes and only the MACs change, so one packet sends at most that much and
 // takes back bytes 0-11; fw_burst reads a frame's first 64 bytes and 16 come
 // back.
-const ServeNf &fw_serve_nf() {
-  static const ServeNf nf = {fw_cutoff, &vp_ctx::ft,    false,   kServeInline, 12, 64, 16,
-                             kFwBurstRoute, false, nullptr, nullptr,      true};
-  return nf;
+const NfOps &fw_ops() {
+  static const NfOps ops = [] {
+    NfOps o{};
+    o.process_device = fw_process_device;  o.serve_launch = fw_serve_launch;
+    o.n_devices = [](const vp_ctx *c) -> uint32_t { return c->fw.n_devices; };
+    o.reads_in_port = false;
+    ServeNf &s = o.serve;
+    s.cutoff = fw_cutoff;  s.table = &vp_ctx::ft;
+    s.one_whole = false;  s.one_in = kServeInline;  s.one_back = 12;
+    s.burst_in = 64;  s.burst_back = 16;  s.burst_route = kFwBurstRoute;
+    s.prof = false;  s.journal = true;
+    s.cutoff2 = nullptr;  s.table2 = nullptr;
+    return o;
+  }();
+  return ops;
 }
 
 // State by flow index: alloc, ts, FlowId bytes (vigfw/flow.h layout, padding

@@ -523,9 +523,7 @@ inline void serve_unpack(const ServeBox *bx, uint8_t *frame, uint32_t back) {
   memcpy(frame, &m[3], back);
 }
 
-// What of a served NF the mailbox's host side needs to know (nat_serve_nf,
-// vp_nat.hip; fw_serve_nf, vp_fw.hip; bridge_serve_nf, vp_bridge.hip;
-// pol_serve_nf, vp_pol.hip; lb_serve_nf, vp_lb.hip).
+// What of a served NF the mailbox's host side needs to know (NfOps::serve).
 struct ServeNf {
   // the table whose entries expire and the cutoff for a packet at time t: a
   // request is sent only while no expiry is due
@@ -552,18 +550,38 @@ struct ServeNf {
   // expiring table) once the context has met a due expiry (serve_journal_ok)
   bool journal = false;
 };
-const ServeNf &nat_serve_nf();
-const ServeNf &fw_serve_nf();
-const ServeNf &bridge_serve_nf();
-const ServeNf &pol_serve_nf();
-const ServeNf &lb_serve_nf();
-inline const ServeNf *serve_nf(int kind) {  // (nullptr: the NF has no resident kernel)
-  return kind == KIND_NAT      ? &nat_serve_nf()
-         : kind == KIND_FW     ? &fw_serve_nf()
-         : kind == KIND_BRIDGE ? &bridge_serve_nf()
-         : kind == KIND_POL    ? &pol_serve_nf()
-         : kind == KIND_LB     ? &lb_serve_nf()
-                               : nullptr;
+// Everything the runtime needs to know of an NF kind, defined by the NF's
+// unit beside its process_device (nat_ops, vp_nat.hip; bridge_ops,
+// vp_bridge.hip; lb_ops, vp_lb.hip; fw_ops, vp_fw.hip; pol_ops, vp_pol.hip).
+// A lookup is a compare and a call that returns a constant's address, with no
+// lock: it sits on vp_process_one's per-packet path.
+struct NfOps {
+  int (*process_device)(vp_ctx *c, const vp_dev_batch *b);
+  // the launcher of the NF's resident kernel on c->stream. flags: its polling
+  // parameters -- bits 10-17 the first poll's delay after an answer, bit 18
+  // adapt it, bits 19-23 the ticks a late poll adds (serve_poll, vp_serve_dev.h)
+  int (*serve_launch)(vp_ctx *c, ServeBox *dbox, uint32_t flags);
+  ServeNf serve;
+  uint32_t (*n_devices)(const vp_ctx *c);
+  // one port for a whole batch (vp_dev_batch.in_dev == NULL): on one GPU the
+  // NF's 64-byte-slot kernels read in_port themselves (else vp_process_device
+  // makes the port array)
+  bool reads_in_port;
+};
+const NfOps &nat_ops();
+const NfOps &bridge_ops();
+const NfOps &lb_ops();
+const NfOps &fw_ops();
+const NfOps &pol_ops();
+inline const NfOps *nf_ops(int kind) {  // (nullptr: no such NF)
+  switch (kind) {
+    case KIND_NAT: return &nat_ops();
+    case KIND_BRIDGE: return &bridge_ops();
+    case KIND_LB: return &lb_ops();
+    case KIND_FW: return &fw_ops();
+    case KIND_POL: return &pol_ops();
+    default: return nullptr;
+  }
 }
 // One packet through the persistent kernel (one GPU, no expiry due): 0 done;
 // 1 not eligible, or declined by the kernel with nothing written (the caller
@@ -600,15 +618,6 @@ bool serve_prof();  // VIGPATH_SERVE_PROF (vignat's stage clock)
 // The largest host batch routed as burst requests: VIGPATH_SERVE_BURST, else
 // the NF's own limit `dflt`.
 uint32_t serve_burst_limit(uint32_t dflt);
-// The NFs' launchers of their resident kernel on c->stream (serve_launch
-// dispatches on c->kind). flags: the kernel's polling parameters -- bits
-// 10-17 the first poll's delay after an answer, bit 18 adapt it, bits 19-23
-// the ticks a late poll adds (serve_poll, vp_serve_dev.h).
-int nat_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
-int fw_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
-int bridge_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
-int pol_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
-int lb_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags);
 
 }  // namespace vp
 

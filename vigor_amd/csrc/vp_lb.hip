@@ -41,7 +41,6 @@
 // flow_id_to_backend_id, so a hit resolves in one bucket read.
 #include <hip/hip_runtime.h>
 #include <cstddef>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstring>
@@ -1055,16 +1054,6 @@ static inline int64_t lb_backend_cutoff(const vp_ctx *c, int64_t t) {
                    (uint64_t)((int64_t)c->lb.backend_expiration_time * 1000));
 }
 
-static int sort_list(vp_ctx *c, const uint32_t *in, uint32_t *out, uint32_t n) {
-  if (!n) return 0;
-  size_t need = 0;
-  hipcub::DeviceRadixSort::SortKeys(nullptr, need, in, out, (int)n, 0, 32, c->stream);
-  VP_TRY(cub_reserve(c, need));
-  VP_HIP(hipcub::DeviceRadixSort::SortKeys(c->ws.cub_tmp, c->ws.cub_bytes, in, out,
-                                           (int)n, 0, 32, c->stream));
-  return 0;
-}
-
 struct Queues {
   const uint32_t *m, *s, *h;
   uint32_t nm, ns, nh;
@@ -1204,19 +1193,16 @@ static int lb_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
     VP_TRY(tbl_touch_reduce(c, c->ft, w.log, p0, p1, now, c->seq));
     VP_TRY(read_ctl2_wait(c, c->ft2, c->ft));
   }
-  float kms = 0.f;
-  VP_HIP(ev_ms(c->ktime, c->ev0, c->ev1, &kms));
-  *ms += kms;
-  *launches += 1;
+  VP_TRY(seg_classify_ms(c, ms, launches));
   const uint32_t nm = c->ft.h_ctl.miss_count, ns = c->ft.h_ctl.defer_count;
   const uint32_t nh = c->ft2.h_ctl.miss_count, nhb = c->ft2.h_ctl.defer_count;
   const bool ovf = bp.on && c->ft.h_ctl.touch_ovf != 0;
 
   std::vector<uint32_t> M_all, S_all;  // phase A's queues (multi-round segments)
   if (nm || ns || nh) {
-    VP_TRY(sort_list(c, w.miss, w.miss_sorted, nm));
-    VP_TRY(sort_list(c, w.defer, w.defer_sorted, ns));
-    VP_TRY(sort_list(c, w.aux, w.aux_sorted, nh));
+    VP_TRY(sort_keys(c, w.miss, w.miss_sorted, nm));
+    VP_TRY(sort_keys(c, w.defer, w.defer_sorted, ns));
+    VP_TRY(sort_keys(c, w.aux, w.aux_sorted, nh));
     if (!nh) {
       VP_TRY(lb_round(c, a, Queues{w.miss_sorted, w.defer_sorted, nullptr, nm, ns, 0},
                       allocated));
@@ -1268,9 +1254,9 @@ static int lb_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
             VP_TRY(read_ctl2(c, c->ft2, c->ft));
             const uint32_t rm = c->ft.h_ctl.miss_count, rs = c->ft.h_ctl.defer_count;
             const uint32_t rh = c->ft2.h_ctl.miss_count;
-            VP_TRY(sort_list(c, w.miss, w.miss_sorted, rm));
-            VP_TRY(sort_list(c, w.defer, w.defer_sorted, rs));
-            VP_TRY(sort_list(c, w.aux, w.aux_sorted, rh));
+            VP_TRY(sort_keys(c, w.miss, w.miss_sorted, rm));
+            VP_TRY(sort_keys(c, w.defer, w.defer_sorted, rs));
+            VP_TRY(sort_keys(c, w.aux, w.aux_sorted, rh));
             VP_TRY(lb_round(c, a, Queues{w.miss_sorted, w.defer_sorted, w.aux_sorted,
                                          rm, rs, rh},
                             allocated));
@@ -1301,20 +1287,15 @@ static int lb_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
         lm = w.rlist;
         ls = w.rlist + nm;
       }
-      if (nm)
-        VP_TRY(tbl_late_touches(c, c->ft, lm, nullptr, nm, 256, (nm + 255) / 256, w.log, now,
-                                c->seq));
-      if (ns)
-        VP_TRY(tbl_late_touches(c, c->ft, ls, nullptr, ns, 256, (ns + 255) / 256, w.log, now,
-                                c->seq));
+      if (nm) VP_TRY(tbl_late_list(c, c->ft, lm, nm, w.log, now, c->seq));
+      if (ns) VP_TRY(tbl_late_list(c, c->ft, ls, ns, w.log, now, c->seq));
     }
   } else if (nm || ns || nh) {
     // the rounds completed the log: refold it
     VP_TRY(tbl_touch_reduce(c, c->ft, w.log, p0, p1, now, c->seq));
   }
   if (nhb)  // the heartbeats' backend touches (log2 holds only theirs)
-    VP_TRY(tbl_late_touches(c, c->ft2, w.hbl, nullptr, nhb, 256, (nhb + 255) / 256,
-                            w.log2, now, c->seq));
+    VP_TRY(tbl_late_list(c, c->ft2, w.hbl, nhb, w.log2, now, c->seq));
   // steady state: frames and ports complete, only the flow fold may still
   // run (not when it reads the caller's time array)
   c->fold_pending = !(nm || ns || nh || ovf || nhb) && !b->now;
@@ -1322,7 +1303,7 @@ static int lb_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   return 0;
 }
 
-int lb_process_device(vp_ctx *c, const vp_dev_batch *b) {
+static int lb_process_device(vp_ctx *c, const vp_dev_batch *b) {
   ExpiringTable tabs[2] = {{&c->ft, lb_flow_cutoff}, {&c->ft2, lb_backend_cutoff}};
   return run_batch(c, b, tabs, 2, lb_segment);
 }
@@ -1333,7 +1314,7 @@ int lb_process_device(vp_ctx *c, const vp_dev_batch *b) {
 // CRC tables and the devices' MACs; the batch's fields stay empty. The
 // instance with the journals runs once both tables' are seeded (serve_ready
 // seeds them together).
-int lb_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
+static int lb_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
   LbArgs a{};
   a.ft = tbl_dev(c->ft);
   a.bt = tbl_dev(c->ft2);
@@ -1345,8 +1326,8 @@ int lb_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
   a.dmacw = c->dmacw;
   a.wan = c->lb.wan_device;
   a.n_dev = c->lb.n_devices;
-  const JournalDev jf = serve_journal_dev(c, lb_serve_nf()),
-                   jb = serve_journal_dev(c, lb_serve_nf(), true);
+  const JournalDev jf = serve_journal_dev(c, lb_ops().serve),
+                   jb = serve_journal_dev(c, lb_ops().serve, true);
   if (jf.ctl && jb.ctl)
     lb_serve<true><<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags, jf, jb);
   else
@@ -1374,11 +1355,21 @@ constexpr uint32_t kLbBurstRoute = 128;
 // kServeInline through `frame`, and a burst's frame comes back in its first 64
 // bytes. Two expiring tables, each with its own lifetime and its own touch
 // journal: the kernel expires both. No stage clock.
-const ServeNf &lb_serve_nf() {
-  static const ServeNf nf = {lb_flow_cutoff, &vp_ctx::ft,   true,          kServeInline,
-                             kServeInline,   kServeFrame,   64,            kLbBurstRoute,
-                             false,          lb_backend_cutoff, &vp_ctx::ft2, true};
-  return nf;
+const NfOps &lb_ops() {
+  static const NfOps ops = [] {
+    NfOps o{};
+    o.process_device = lb_process_device;  o.serve_launch = lb_serve_launch;
+    o.n_devices = [](const vp_ctx *c) -> uint32_t { return c->lb.n_devices; };
+    o.reads_in_port = true;  // (LbArgs::in0)
+    ServeNf &s = o.serve;
+    s.cutoff = lb_flow_cutoff;  s.table = &vp_ctx::ft;
+    s.one_whole = true;  s.one_in = kServeInline;  s.one_back = kServeInline;
+    s.burst_in = kServeFrame;  s.burst_back = 64;  s.burst_route = kLbBurstRoute;
+    s.prof = false;  s.journal = true;
+    s.cutoff2 = lb_backend_cutoff;  s.table2 = &vp_ctx::ft2;
+    return o;
+  }();
+  return ops;
 }
 
 void build_lb_tables(std::vector<uint32_t> &tab) {

@@ -881,12 +881,12 @@ int vp_process_mbufs(vp_ctx *c, const vp_mbuf_batch *b) {
   if (b->n && (!b->frames || !b->len || !b->in_dev || !b->out_dev)) return VP_EINVAL;
   if (!b->now && (b->now_step < 0 || b->now0 < 0)) return VP_ENOTSUP;
   vp_mbuf_batch rest;
-  const ServeNf *nf = serve_nf(c->kind);
+  const NfOps *nf = nf_ops(c->kind);
   if (nf && b->n) {
     // a small burst goes to the NF's resident kernel, which stays
     // (no hipSetDevice: a served burst makes no HIP call, as vp_process_one)
     uint32_t done = 0;
-    const int rc = serve_process_burst(c, *nf, b, 0, b->n, &done);
+    const int rc = serve_process_burst(c, nf->serve, b, 0, b->n, &done);
     if (rc <= 0) return rc;
     if (done) {  // the kernel declined a later request: the rest below
       rest = *b;

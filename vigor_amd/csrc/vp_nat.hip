@@ -17,7 +17,6 @@
 // every packet that touches a flow writes its index to the touch log, which
 // tbl_touch_reduce folds into the dchain timestamps (last toucher wins).
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <chrono>
@@ -2569,8 +2568,7 @@ static int nat_phase_a_owner(vp_ctx *c, const vp_dev_batch *b, NatArgs &a,
 
   // (counters still zero after a segment that appended nothing, and the
   // overflow flag after an exchange that fit: no reset launches)
-  if (!t.ctl_clean) VP_HIP(hipMemsetAsync(&t.ctl->miss_count, 0, 16, c->stream));  // .. reprobe
-  t.ctl_clean = false;
+  VP_TRY(seg_reset_counters(c, t));
   if (!w.ovf64_clean) VP_HIP(hipMemsetAsync(w.ovf64, 0, 8, c->stream));
   w.ovf64_clean = false;
   VP_HIP(ev_record(c->ktime, c->ev0, c->stream));
@@ -3064,9 +3062,7 @@ static int nat_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
     a.mq = w.missq;
   }
   if (!owner) {
-  if (!t.ctl_clean)
-    VP_HIP(hipMemsetAsync(&t.ctl->miss_count, 0, 16, c->stream));  // .. reprobe
-  t.ctl_clean = false;
+  VP_TRY(seg_reset_counters(c, t));
   hostprof(1);
   uint32_t pub_epoch = 0;  // (nonzero: the classify publishes, tile_publish)
   if (p1 > p0) {  // (the launch's own timestamps in ev0 / ev1)
@@ -3150,13 +3146,7 @@ static int nat_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
         2 * span <= (uint64_t)(p1 - p0))
       t.fs_hint = (uint32_t)((span + 63) & ~63ull);
   } else if (nmiss) {
-    size_t need = 0;
-    hipcub::DeviceRadixSort::SortKeys(nullptr, need, w.miss, w.miss_sorted,
-                                      (int)nmiss, 0, 32, c->stream);
-    VP_TRY(cub_reserve(c, need));
-    VP_HIP(hipcub::DeviceRadixSort::SortKeys(w.cub_tmp, w.cub_bytes, w.miss,
-                                             w.miss_sorted, (int)nmiss, 0, 32,
-                                             c->stream));
+    VP_TRY(sort_keys(c, w.miss, w.miss_sorted, nmiss));
     nat_miss_keys<<<grid_for(nmiss), 256, 0, c->stream>>>(a, w.miss_sorted, nmiss,
                                                           w.mkey, w.mhash);
     VP_HIP(hipGetLastError());
@@ -3178,16 +3168,14 @@ static int nat_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
       nat_miss_finish<<<grid_for(nmiss), 256, 0, c->stream>>>(
           a, w.miss_sorted, nmiss, w.scratch, w.rep + union_off, w.assign, nullptr);
       VP_HIP(hipGetLastError());
-      VP_TRY(tbl_late_touches(c, t, w.miss_sorted, nullptr, nmiss, 256,
-                              (nmiss + 255) / 256, w.log, now, seq0));
+      VP_TRY(tbl_late_list(c, t, w.miss_sorted, nmiss, w.log, now, seq0));
     }
     *allocated |= 1u;
   }
   if (ndefer) {
     nat_defer_finish<<<grid_for(ndefer), 256, 0, c->stream>>>(a, w.defer, ndefer);
     VP_HIP(hipGetLastError());
-    VP_TRY(tbl_late_touches(c, t, w.defer, nullptr, ndefer, 256, (ndefer + 255) / 256,
-                            w.log, now, seq0));
+    VP_TRY(tbl_late_list(c, t, w.defer, ndefer, w.log, now, seq0));
   }
   if ((union_n && !nku) || ndefer) VP_TRY(read_ctl(c, t));  // (unsorted: read already)
   // steady state (every packet a phase-A hit): the frames and ports are
@@ -3202,7 +3190,7 @@ static int nat_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
 }
 
 // Whole batch: segments without expiry (run_batch, vp_table.hip).
-int nat_process_device(vp_ctx *c, const vp_dev_batch *b) {
+static int nat_process_device(vp_ctx *c, const vp_dev_batch *b) {
   ExpiringTable tabs[1] = {{&c->ft, nat_cutoff}};
   return run_batch(c, b, tabs, 1, nat_segment);
 }
@@ -3214,7 +3202,7 @@ int nat_dump(vp_ctx *c, uint8_t *alloc, int64_t *ts, uint8_t *keys) {
 // ---------------------------------------------------- vp_process_one --
 // vignat's launcher of the resident kernel (serve_launch, vp_serve.hip:
 // `flags` holds the polling parameters every server takes, bits 10-23).
-int nat_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
+static int nat_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
   const FlowTable &t = c->ft;
   NatArgs a{};
   a.t = tbl_dev(t);
@@ -3239,7 +3227,7 @@ int nat_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
     return e ? (uint32_t)std::min(127, std::max(0, atoi(e))) : 35u;
   }();
   // (the journal's control words live in one wave's registers: off with more)
-  JournalDev j = serve_journal_dev(c, nat_serve_nf());
+  JournalDev j = serve_journal_dev(c, nat_ops().serve);
   if (waves > 1) j = JournalDev{};
   const uint32_t fl = (serve_prof() ? 1u : 0u) | (gap << 3) | flags;
   if (j.ctl)
@@ -3262,12 +3250,21 @@ constexpr uint32_t kServeBurstRoute = 256;
 // vp_serve.hip): the whole frame goes and comes back rewritten, one longer
 // than kServeInline through `frame`; of a burst's frame all bytes go (the L4
 // checksum's) and the first 64 come back. The stage clock is vignat's.
-const ServeNf &nat_serve_nf() {
-  static const ServeNf nf = {nat_cutoff,  &vp_ctx::ft, true,
-                             kServeInline, kServeInline, kServeFrame,
-                             64,          kServeBurstRoute, true,
-                             nullptr,     nullptr,     true};
-  return nf;
+const NfOps &nat_ops() {
+  static const NfOps ops = [] {
+    NfOps o{};
+    o.process_device = nat_process_device;  o.serve_launch = nat_serve_launch;
+    o.n_devices = [](const vp_ctx *c) -> uint32_t { return c->nat.n_devices; };
+    o.reads_in_port = true;  // (NatArgs::in0)
+    ServeNf &s = o.serve;
+    s.cutoff = nat_cutoff;  s.table = &vp_ctx::ft;
+    s.one_whole = true;  s.one_in = kServeInline;  s.one_back = kServeInline;
+    s.burst_in = kServeFrame;  s.burst_back = 64;  s.burst_route = kServeBurstRoute;
+    s.prof = true;  s.journal = true;
+    s.cutoff2 = nullptr;  s.table2 = nullptr;
+    return o;
+  }();
+  return ops;
 }
 
 void build_flowid_tables(std::vector<uint32_t> &tab) {

@@ -862,35 +862,22 @@ static int pol_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
     VP_TRY(tbl_wait_pub(c, t, epoch));
   else
     VP_TRY(read_ctl(c, t));
-  float kms = 0.f;
-  VP_HIP(ev_ms(c->ktime, c->ev0, c->ev1, &kms));
-  *ms += kms;
-  *launches += 1;
+  VP_TRY(seg_classify_ms(c, ms, launches));
   const uint32_t nmiss = t.h_ctl.miss_count, ndefer = t.h_ctl.defer_count;
-  if (nmiss) {
-    size_t need = 0;
-    hipcub::DeviceRadixSort::SortKeys(nullptr, need, w.miss, w.miss_sorted,
-                                      (int)nmiss, 0, 32, c->stream);
-    VP_TRY(cub_reserve(c, need));
-    VP_HIP(hipcub::DeviceRadixSort::SortKeys(w.cub_tmp, w.cub_bytes, w.miss,
-                                             w.miss_sorted, (int)nmiss, 0, 32,
-                                             c->stream));
-    pol_miss_keys<<<grid_for(nmiss), 256, 0, c->stream>>>(a, w.miss_sorted, nmiss,
-                                                          w.mkey, w.mhash);
-    VP_HIP(hipGetLastError());
-    VP_TRY(tbl_new_keys(c, t, NewKeys{nmiss, w.miss_sorted}, c->seq, nullptr));
-    a.t = tbl_dev(t);  // a rebuild may have moved the buckets
-    pol_miss_finish<<<grid_for(nmiss), 256, 0, c->stream>>>(
-        a, w.miss_sorted, nmiss, w.scratch, w.rep, w.assign);
-    VP_HIP(hipGetLastError());
+  if (nmiss) {  // (no late touches: phase T below stamps every policed packet's index)
+    VP_TRY(phase_b_round(c, t, nmiss, &a.t, [&] {
+      pol_miss_keys<<<grid_for(nmiss), 256, 0, c->stream>>>(a, w.miss_sorted, nmiss,
+                                                            w.mkey, w.mhash);
+    }, [&] {
+      pol_miss_finish<<<grid_for(nmiss), 256, 0, c->stream>>>(
+          a, w.miss_sorted, nmiss, w.scratch, w.rep, w.assign);
+    }));
     *allocated |= 1u;
   }
-  if (ndefer) {
-    a.t = tbl_dev(t);  // a rebuild during phase B may have changed the layout
+  if (ndefer) {  // (a.t: phase B's round refreshed it)
     pol_defer_finish<<<grid_for(ndefer), 256, 0, c->stream>>>(a, w.defer, ndefer);
     VP_HIP(hipGetLastError());
   }
-  a.t = tbl_dev(t);
   // the grouping path already ran (every policed packet was a counted
   // phase-A hit and runs are short): nothing left
   if (grouping && !nmiss && !ndefer && t.h_ctl.aux_count == 0) {
@@ -909,13 +896,7 @@ static int pol_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   while ((1ull << bits) <= t.cap) bits++;
   pol_sort_keys<<<grid_for(n), 256, 0, c->stream>>>(w.log, p0, n, t.cap, w.rank);
   VP_HIP(hipGetLastError());
-  size_t need = 0;
-  hipcub::DeviceRadixSort::SortPairs(nullptr, need, w.rank, w.skey, w.iota + p0,
-                                     w.sval, (int)n, 0, (int)bits, c->stream);
-  VP_TRY(cub_reserve(c, need));
-  VP_HIP(hipcub::DeviceRadixSort::SortPairs(w.cub_tmp, w.cub_bytes, w.rank, w.skey,
-                                            w.iota + p0, w.sval, (int)n, 0,
-                                            (int)bits, c->stream));
+  VP_TRY(sort_pairs(c, w.rank, w.skey, w.iota + p0, w.sval, n, (int)bits));
   pol_buckets<<<grid_for(n), 256, 0, c->stream>>>(a, w.skey, w.sval, n, t.cap, now,
                                                   c->pol_size, c->pol_time);
   VP_HIP(hipGetLastError());
@@ -923,7 +904,7 @@ static int pol_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   return 0;
 }
 
-int pol_process_device(vp_ctx *c, const vp_dev_batch *b) {
+static int pol_process_device(vp_ctx *c, const vp_dev_batch *b) {
   // expiries only up to the batch's last IPv4 packet
   uint32_t exp_end = b->n;
   // With affine time the whole batch may be free of expiries (the cutoff
@@ -953,7 +934,7 @@ int pol_process_device(vp_ctx *c, const vp_dev_batch *b) {
 
 // ---------------------------------------------------- vp_process_one --
 // vigpol's launcher of the resident kernel (serve_launch, vp_serve.hip).
-int pol_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
+static int pol_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
   PolServeArgs a{};
   a.t = tbl_dev(c->ft);
   a.crc_tab = c->crc_tab;
@@ -963,13 +944,8 @@ int pol_serve_launch(vp_ctx *c, ServeBox *dbox, uint32_t flags) {
   a.bsize = c->pol_size;
   a.btime = c->pol_time;
   a.ports = (uint32_t)c->pol.lan_device | ((uint32_t)c->pol.wan_device << 16);
-  const JournalDev j = serve_journal_dev(c, pol_serve_nf());
-  if (j.ctl)
-    pol_serve<true><<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags, j);
-  else
-    pol_serve<false><<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags, j);
-  VP_HIP(hipGetLastError());
-  return 0;
+  return serve_launch_one(c, pol_serve<true>, pol_serve<false>, a, dbox, flags,
+                          serve_journal_dev(c, pol_ops().serve));
 }
 
 // The largest host batch routed to the server as burst requests: the largest
@@ -991,10 +967,21 @@ constexpr uint32_t kPolBurstRoute = 512;
 // from the touch journal; its E is 0 - pol_cutoff(c, 0) (serve_expire_e), the
 // 64-bit burst * 1e9 / rate itself, and a lifetime that does not fit a signed
 // 64-bit time leaves the journal off (serve_journal_ok).
-const ServeNf &pol_serve_nf() {
-  static const ServeNf nf = {pol_cutoff,     &vp_ctx::ft, false,   34,      0,   48, 0,
-                             kPolBurstRoute, false,       nullptr, nullptr, true};
-  return nf;
+const NfOps &pol_ops() {
+  static const NfOps ops = [] {
+    NfOps o{};
+    o.process_device = pol_process_device;  o.serve_launch = pol_serve_launch;
+    o.n_devices = [](const vp_ctx *c) -> uint32_t { return c->pol.n_devices; };
+    o.reads_in_port = false;
+    ServeNf &s = o.serve;
+    s.cutoff = pol_cutoff;  s.table = &vp_ctx::ft;
+    s.one_whole = false;  s.one_in = 34;  s.one_back = 0;
+    s.burst_in = 48;  s.burst_back = 0;  s.burst_route = kPolBurstRoute;
+    s.prof = false;  s.journal = true;
+    s.cutoff2 = nullptr;  s.table2 = nullptr;
+    return o;
+  }();
+  return ops;
 }
 
 // State by index: alloc, ts, dyn_keys (u32 address), dyn_vals.

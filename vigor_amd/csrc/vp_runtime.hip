@@ -39,20 +39,15 @@ int state_fail(const char *fmt, ...) {
   return VP_ESTATE;
 }
 
-int nat_process_device(vp_ctx *c, const vp_dev_batch *b);
 int nat_dump(vp_ctx *c, uint8_t *alloc, int64_t *ts, uint8_t *keys);
 void build_flowid_tables(std::vector<uint32_t> &tab);
-int bridge_process_device(vp_ctx *c, const vp_dev_batch *b);
 void build_bridge_tables(std::vector<uint32_t> &tab);
 int bridge_static_build(const vp_bridge_config *cfg, std::vector<Bucket> &bk,
                         uint32_t *bmask);
-int lb_process_device(vp_ctx *c, const vp_dev_batch *b);
 void build_lb_tables(std::vector<uint32_t> &tab);
 void lb_fill_cht(uint32_t height, uint32_t bcap, std::vector<uint32_t> &cht);
-int fw_process_device(vp_ctx *c, const vp_dev_batch *b);
 void build_fw_tables(std::vector<uint32_t> &tab);
 int fw_dump(vp_ctx *c, uint8_t *alloc, int64_t *ts, uint8_t *keys, uint32_t *int_dev);
-int pol_process_device(vp_ctx *c, const vp_dev_batch *b);
 void build_pol_tables(std::vector<uint32_t> &tab);
 int pol_dump(vp_ctx *c, uint8_t *alloc, int64_t *ts, uint32_t *keys,
              uint64_t *bucket_size, int64_t *bucket_time);
@@ -176,12 +171,8 @@ int callbuf_reserve(CallBuf &w, size_t bytes, hipStream_t s) {
 }
 
 uint32_t ctx_devices(const vp_ctx *c) {
-  return c->kind == KIND_NAT      ? c->nat.n_devices
-         : c->kind == KIND_BRIDGE ? c->brg.n_devices
-         : c->kind == KIND_LB     ? c->lb.n_devices
-         : c->kind == KIND_FW     ? c->fw.n_devices
-         : c->kind == KIND_POL    ? c->pol.n_devices
-                                  : 0;
+  const NfOps *nf = nf_ops(c->kind);
+  return nf ? nf->n_devices(c) : 0;
 }
 
 static void mac_words(const uint8_t d[6], const uint8_t s[6], uint32_t w[3]) {
@@ -727,12 +718,12 @@ int vp_process_device(vp_ctx *c, const vp_dev_batch *b, void *stream) {
     VP_HIP(hipEventRecord(dep, user));
     VP_HIP(hipStreamWaitEvent(c->stream, dep, 0));
   }
-  // one port for the whole batch (in_dev == NULL): vignat's and viglb's
-  // 64-byte slots on one GPU read in_port themselves; elsewhere the port
-  // array is made here
+  // one port for the whole batch (in_dev == NULL): some NFs' 64-byte slots
+  // on one GPU read in_port themselves (NfOps::reads_in_port); elsewhere the
+  // port array is made here
+  const NfOps *nf = nf_ops(c->kind);
   vp_dev_batch one;
-  if (!b->in_dev && b->n &&
-      ((c->kind != KIND_NAT && c->kind != KIND_LB) || c->comm || b->slot != 64)) {
+  if (!b->in_dev && b->n && (!nf || !nf->reads_in_port || c->comm || b->slot != 64)) {
     Workspace &w = c->ws;
     if (w.in_fill_n < b->n) {
       VP_HIP(hipStreamSynchronize(c->stream));
@@ -747,26 +738,7 @@ int vp_process_device(vp_ctx *c, const vp_dev_batch *b, void *stream) {
     one.in_dev = w.in_fill;
     b = &one;
   }
-  int rc = VP_ENOTSUP;
-  switch (c->kind) {
-    case KIND_NAT:
-      rc = nat_process_device(c, b);
-      break;
-    case KIND_BRIDGE:
-      rc = bridge_process_device(c, b);
-      break;
-    case KIND_LB:
-      rc = lb_process_device(c, b);
-      break;
-    case KIND_FW:
-      rc = fw_process_device(c, b);
-      break;
-    case KIND_POL:
-      rc = pol_process_device(c, b);
-      break;
-    default:
-      break;
-  }
+  const int rc = nf ? nf->process_device(c, b) : VP_ENOTSUP;
   if (dep) {
     hipEventRecord(dep, c->stream);
     hipStreamWaitEvent(user, dep, 0);
@@ -791,10 +763,10 @@ int vp_process_device(vp_ctx *c, const vp_dev_batch *b, void *stream) {
 int vp_process_one(vp_ctx *c, uint16_t in_dev, uint8_t *frame, uint16_t len, int64_t now,
                    uint16_t *out_dev) {
   if (!c || !frame || !out_dev) return VP_EINVAL;
-  if (const ServeNf *nf = serve_nf(c->kind)) {
+  if (const NfOps *nf = nf_ops(c->kind)) {
     // (no hipSetDevice here: a served packet makes no HIP call; the server's
     // launch and stop set the device themselves)
-    const int rc = serve_process_one(c, *nf, in_dev, frame, len, now, out_dev);
+    const int rc = serve_process_one(c, nf->serve, in_dev, frame, len, now, out_dev);
     if (rc <= 0) return rc;
     // 1: not eligible or declined, and the server is stopped. Straight to the
     // batch pipeline: a burst request of one would meet the same refusal

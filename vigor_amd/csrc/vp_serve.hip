@@ -132,25 +132,9 @@ static int serve_launch(vp_ctx *c) {
     return e && !atoi(e) ? 0u : 1u;
   }();
   const uint32_t flags = (after << 10) | (adapt << 18) | (up << 19);
-  switch (c->kind) {
-    case KIND_NAT:
-      VP_TRY(nat_serve_launch(c, dbox, flags));
-      break;
-    case KIND_FW:
-      VP_TRY(fw_serve_launch(c, dbox, flags));
-      break;
-    case KIND_BRIDGE:
-      VP_TRY(bridge_serve_launch(c, dbox, flags));
-      break;
-    case KIND_POL:
-      VP_TRY(pol_serve_launch(c, dbox, flags));
-      break;
-    case KIND_LB:
-      VP_TRY(lb_serve_launch(c, dbox, flags));
-      break;
-    default:
-      return state_fail("no resident kernel for NF kind %d", c->kind);
-  }
+  const NfOps *nf = nf_ops(c->kind);
+  if (!nf) return state_fail("no resident kernel for NF kind %d", c->kind);
+  VP_TRY(nf->serve_launch(c, dbox, flags));
   c->srv_stats.launches += 1;
   if (!c->srv_on) {
     static std::once_flag once;
@@ -282,9 +266,9 @@ int serve_ready(vp_ctx *c) {
     // the context's last fallback was a due expiry: from this launch on the
     // kernel expires itself, from a journal of the table as it is now
     if (c->jr_want) {
-      const ServeNf *nf = serve_nf(c->kind);
+      const ServeNf &nf = nf_ops(c->kind)->serve;
       c->jr_want = false;
-      for (FlowTable vp_ctx::*m : {nf->table, nf->table2}) {
+      for (FlowTable vp_ctx::*m : {nf.table, nf.table2}) {
         if (!m || (c->*m).jr_on) continue;
         VP_TRY(tbl_journal_seed(c, c->*m));
         c->srv_exp.seeds += 1;  // (tables seeded: viglb's two count 2)

@@ -406,6 +406,65 @@ using SegmentFn = int (*)(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
 int run_batch(vp_ctx *c, const vp_dev_batch *b, ExpiringTable *tabs, int ntabs,
               SegmentFn seg, uint32_t exp_end = UINT32_MAX);
 
+// The steps every NF's SegmentFn takes on the host, written once (DESIGN.md
+// §5.10.1); each queues on c->stream in the order written here.
+// Radix sorts through ws.cub_tmp: n 32-bit keys (a miss or defer list: packet
+// positions), or n (key, value) pairs by the keys' low `bits` bits (stable).
+int sort_keys(vp_ctx *c, const uint32_t *in, uint32_t *out, uint32_t n);
+template <class K>
+int sort_pairs(vp_ctx *c, const K *kin, K *kout, const uint32_t *vin, uint32_t *vout,
+               uint32_t n, int bits);
+// A segment's start: miss_count .. reprobe_count zeroed, unless the last
+// segment left them zero (FlowTable::ctl_clean).
+inline int seg_reset_counters(vp_ctx *c, FlowTable &t) {
+  if (!t.ctl_clean) VP_HIP(hipMemsetAsync(&t.ctl->miss_count, 0, 16, c->stream));
+  t.ctl_clean = false;
+  return 0;
+}
+// The classify launch's time between ev0 and ev1 (vp_kernel_timing) added to
+// *ms, and the launch counted.
+inline int seg_classify_ms(vp_ctx *c, float *ms, int *launches) {
+  float kms = 0.f;
+  VP_HIP(ev_ms(c->ktime, c->ev0, c->ev1, &kms));
+  *ms += kms;
+  *launches += 1;
+  return 0;
+}
+// tbl_late_touches of a plain list of n packets.
+inline int tbl_late_list(vp_ctx *c, FlowTable &t, const uint32_t *list, uint32_t n,
+                         const uint32_t *log, const NowSpec &now, uint64_t seq_base) {
+  return tbl_late_touches(c, t, list, nullptr, n, 256, (n + 255) / 256, log, now, seq_base);
+}
+// Phase B's round for the n misses in ws.miss: sort them into ws.miss_sorted;
+// keys(), the NF's kernel that writes their keys to ws.mkey / ws.mhash;
+// tbl_new_keys; *dev = tbl_dev(t), the NF's copy in its kernels' arguments (a
+// rebuild inside tbl_new_keys may have moved the buckets); finish(), the NF's
+// kernel that completes the packets. Both callables launch from the NF's unit.
+template <class Keys, class Finish>
+int phase_b_round(vp_ctx *c, FlowTable &t, uint32_t n, TableDev *dev, Keys keys, Finish finish) {
+  Workspace &w = c->ws;
+  VP_TRY(sort_keys(c, w.miss, w.miss_sorted, n));
+  keys();
+  VP_HIP(hipGetLastError());
+  VP_TRY(tbl_new_keys(c, t, NewKeys{n, w.miss_sorted}, c->seq, nullptr));
+  *dev = tbl_dev(t);
+  finish();
+  VP_HIP(hipGetLastError());
+  return 0;
+}
+// A one-wave resident kernel on c->stream: its instance that expires from the
+// touch journal (kj) when the journal is on (j.ctl), else the other (k0).
+template <class A>
+using ServeKernel = void (*)(A, ServeBox *, uint64_t, uint64_t, uint32_t, JournalDev);
+template <class A>
+int serve_launch_one(vp_ctx *c, ServeKernel<A> kj, ServeKernel<A> k0, const A &a, ServeBox *dbox,
+                     uint32_t flags, const JournalDev &j) {
+  const auto k = j.ctl ? kj : k0;
+  k<<<1, 64, 0, c->stream>>>(a, dbox, c->seq, c->srv_idle, flags, j);
+  VP_HIP(hipGetLastError());
+  return 0;
+}
+
 // ------------------------------------------------- multi-GPU new keys --
 // (run_batch_sharded, vp_table.hip) Gather every rank's count of local new
 // keys: the union size and this rank's offset in it.

@@ -1593,13 +1593,7 @@ int tbl_expire(vp_ctx *c, FlowTable &t, int64_t cutoff, uint32_t *n_out) {
   t.ts_floor = t.h_ctl.min_ts;  // (~0: nothing stays)
   if (n_out) *n_out = k;
   if (k == 0) return 0;
-  size_t need = 0;
-  hipcub::DeviceRadixSort::SortPairs(nullptr, need, t.ekey, t.ekey2, t.eidx,
-                                     t.eidx2, (int)k, 0, 64, c->stream);
-  VP_TRY(cub_reserve(c, need));
-  VP_HIP(hipcub::DeviceRadixSort::SortPairs(c->ws.cub_tmp, c->ws.cub_bytes,
-                                            t.ekey, t.ekey2, t.eidx, t.eidx2,
-                                            (int)k, 0, 64, c->stream));
+  VP_TRY(sort_pairs(c, t.ekey, t.ekey2, t.eidx, t.eidx2, k, 64));
   exp_apply<<<grid_for(k), 256, 0, c->stream>>>(tbl_dev(t), t.eidx2, k);
   exp_commit<<<1, 64, 0, c->stream>>>(t.ctl, k, t.h_ctl.n_tomb);
   VP_HIP(hipGetLastError());
@@ -1672,12 +1666,7 @@ int tbl_journal_seed(vp_ctx *c, FlowTable &t) {
   const uint64_t *seq = t.ekey;
   const uint32_t *idx = t.eidx;
   if (k > 1) {
-    size_t need = 0;
-    hipcub::DeviceRadixSort::SortPairs(nullptr, need, t.ekey, t.ekey2, t.eidx, t.eidx2, (int)k, 0,
-                                       64, c->stream);
-    VP_TRY(cub_reserve(c, need));
-    VP_HIP(hipcub::DeviceRadixSort::SortPairs(c->ws.cub_tmp, c->ws.cub_bytes, t.ekey, t.ekey2,
-                                              t.eidx, t.eidx2, (int)k, 0, 64, c->stream));
+    VP_TRY(sort_pairs(c, t.ekey, t.ekey2, t.eidx, t.eidx2, k, 64));
     seq = t.ekey2;
     idx = t.eidx2;
   }
@@ -1691,6 +1680,30 @@ int tbl_journal_seed(vp_ctx *c, FlowTable &t) {
 // ---------------------------------------------------------- batch driver --
 
 int ws_reserve(vp_ctx *c, uint32_t n);
+
+int sort_keys(vp_ctx *c, const uint32_t *in, uint32_t *out, uint32_t n) {
+  if (!n) return 0;
+  size_t need = 0;
+  hipcub::DeviceRadixSort::SortKeys(nullptr, need, in, out, (int)n, 0, 32, c->stream);
+  VP_TRY(cub_reserve(c, need));
+  VP_HIP(hipcub::DeviceRadixSort::SortKeys(c->ws.cub_tmp, c->ws.cub_bytes, in, out,
+                                           (int)n, 0, 32, c->stream));
+  return 0;
+}
+
+template <class K>
+int sort_pairs(vp_ctx *c, const K *kin, K *kout, const uint32_t *vin, uint32_t *vout,
+               uint32_t n, int bits) {
+  size_t need = 0;
+  hipcub::DeviceRadixSort::SortPairs(nullptr, need, kin, kout, vin, vout, (int)n, 0, bits,
+                                     c->stream);
+  VP_TRY(cub_reserve(c, need));
+  VP_HIP(hipcub::DeviceRadixSort::SortPairs(c->ws.cub_tmp, c->ws.cub_bytes, kin, kout, vin,
+                                            vout, (int)n, 0, bits, c->stream));
+  return 0;
+}
+template int sort_pairs(vp_ctx *, const uint32_t *, uint32_t *, const uint32_t *, uint32_t *,
+                        uint32_t, int);  // (vigpol's replay order, vp_pol.hip)
 
 // No entry of a table can expire at packet p while cutoff(t_p) <= min(live
 // stamps); inside a segment starting at packet a the live stamps are
@@ -1709,7 +1722,7 @@ int run_batch(vp_ctx *c, const vp_dev_batch *b, ExpiringTable *tabs, int ntabs,
   c->last_launches = 0;
   if (n == 0) return 0;
   if (b->slot < 64 || (b->slot & 15) || !b->frames || ((uintptr_t)b->frames & 15) ||
-      !b->len || (!b->in_dev && ((c->kind != KIND_NAT && c->kind != KIND_LB) || b->slot != 64)) || !b->out_dev)
+      !b->len || (!b->in_dev && (!nf_ops(c->kind)->reads_in_port || b->slot != 64)) || !b->out_dev)
     return VP_EINVAL;  // (frames are read as aligned 16-byte chunks; in_dev: see vp_process_device)
   // the pipeline touches and expires without journalling: a resident kernel's
   // touch journal no longer describes the tables (seeded again on demand)
