@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import orc
 import vigor_amd
-from gpuh import check_batches, run_gpu
+from gpuh import check_batches, dumps_equal, run_gpu
 from tracegen import mixed_fw_trace
 from vigor_amd import traces as T
 
@@ -34,13 +34,7 @@ def make_pair(max_flows=65536, expire_us=60_000_000, wan=1, n_dev=3):
 
 
 def check_state(fw, oracle, max_flows):
-    ga, gts, gk, gd = fw.dump()
-    oa, ots, ok, od = oracle.fw_dump(max_flows)
-    np.testing.assert_array_equal(ga, oa)
-    live = oa == 1
-    np.testing.assert_array_equal(gts[live], ots[live])
-    np.testing.assert_array_equal(gk[live], ok[live])
-    np.testing.assert_array_equal(gd[live], od[live])
+    dumps_equal(fw.dump(), oracle.fw_dump(max_flows))
 
 
 @pytest.mark.parametrize("seed,max_flows,expire_us,n_flows,cuts", [

@@ -666,6 +666,7 @@ static int fw_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   VP_TRY(seg_reset_counters(c, t));
   VP_HIP(ev_record(c->ktime, c->ev0, c->stream));
   if (p1 > p0) {
+    c->last_kernel = tiles64 ? "fw_classify64" : "fw_classify";
     if (tiles64) {
       FwArgs a64 = a;
       if (bp.on) a64.log = nullptr;  // touches go to the bins only

@@ -468,7 +468,8 @@ class NfBase:
         """vp_last_kernel: the tile kernel the last call launched ("" if none).
         vigpol: the classify kernel plus the phase-T path of the call's last
         segment, e.g. "pol_classify64+pol_runs", "pol_classify+pol_scatter+pol_runs"
-        or "pol_classify64+pol_buckets"."""
+        or "pol_classify64+pol_buckets". vigfw: "fw_classify64" (64-byte slots) or
+        "fw_classify"."""
         return (self.L.vp_last_kernel(self.h) or b"").decode()
 
     STAGES = ("pass1", "offsets", "a2a_keys", "probe", "a2a_answers", "pass2", "fold",
