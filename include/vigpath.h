@@ -1008,6 +1008,88 @@ int vp_fw_dump(vp_ctx *ctx, uint8_t *alloc, int64_t *ts, uint8_t *keys,
 int vp_pol_dump(vp_ctx *ctx, uint8_t *alloc, int64_t *ts, uint32_t *keys,
                 uint64_t *bucket_size, int64_t *bucket_time);
 
+/* ------------------------------------------------------- state images -- */
+
+/* Save and restore a context's table state: failover, warm restart, moving
+ * an NF to another GPU, warming a table without replaying its traffic.
+ *
+ * A dump (above) is an observation, not a state: it leaves out the order
+ * among equal timestamps in the dchain's allocated list (which of two flows
+ * with one stamp expires first) and the order of the free list (the index,
+ * and for vignat the external port, of every later new flow). The image holds
+ * both, and nothing that depends on how the device keeps the tables.
+ *
+ * The image, version 1. Little-endian; every array starts at a multiple of
+ * 16 bytes from the image's first byte and is followed by zero bytes up to
+ * the next multiple of 16; every reserved byte is zero. Its size follows the
+ * live entries and the freed indices, not the capacity.
+ *
+ *   header, 32 bytes
+ *     u32 magic        VP_STATE_MAGIC (the bytes "VPST")
+ *     u32 version      VP_STATE_VERSION
+ *     u32 kind         1 vignat, 2 vigbridge, 3 viglb, 4 vigfw, 5 vigpol
+ *     u32 n_tables     1; viglb 2 (its flows, then its backends)
+ *     u64 total_bytes  of the whole image
+ *     i64 last_now     the time of the last packet processed (-1: none yet)
+ *   then per table
+ *     table header, 32 bytes
+ *       u32 capacity
+ *       u32 n_live
+ *       u32 fresh_next   the never-used tail is fresh_next .. capacity - 1
+ *       u32 value_size   bytes per entry in value[] (below)
+ *       u32 n_freed
+ *       u32 reserved[3]  zero
+ *     u32 lru[n_live]    the allocated indices, oldest first: the dchain's
+ *                        allocated list, the order in which they would expire
+ *     u32 freed[n_freed] the free indices that precede the tail, in the order
+ *                        the allocator will hand them out
+ *     i64 ts[n_live]     entry j's timestamp; it never decreases along j
+ *     u8  key[n_live][16]          entry j's key, zero-padded to 16 bytes
+ *     u8  value[n_live][value_size] entry j's value
+ *   Entry j of ts, key and value belongs to index lru[j].
+ *
+ *   table              key (as the dump gives it)       value (value_size)
+ *   vignat flows       FlowId, 16 bytes                 none (0)
+ *   vigbridge MACs     the address, 6 bytes             u32 port, <= 0xFFFF (4)
+ *   vigfw flows        FlowId, 13 bytes                 u32 int_dev, <= 0xFFFF (4)
+ *   viglb flows        LoadBalancedFlow, 13 bytes       u32 backend id, below
+ *                                                       backend_capacity (4)
+ *   viglb backends     the address, u32 as b_ip         mac[6], u16 nic (8)
+ *   vigpol             the address, u32 as keys[]       u64 bucket_size,
+ *                                                       i64 bucket_time (16)
+ *
+ * The image is canonical: two contexts in the same libVig state give the
+ * same bytes, whatever their bucket layouts, batch splits or entry points
+ * were. After the indices of freed[], the allocator hands out the tail in
+ * ascending order; the tail is the longest run at the end of the hand-out
+ * order that is ascending and consecutive up to capacity - 1, so freed[]
+ * never ends with fresh_next - 1 (that index belongs to the tail).
+ * n_live + n_freed + (capacity - fresh_next) == capacity, and lru, freed and
+ * the tail name every index once.
+ *
+ * All three calls stop the NF's resident kernel and wait for the context's
+ * stream first, and return VP_ENOTSUP on a context attached to a multi-GPU
+ * communicator. buf is host memory.
+ *
+ * vp_state_size: *bytes = an upper bound of what a save would write now.
+ * vp_state_save: writes the image and its size to *bytes. With cap too small
+ * it writes *bytes only and returns VP_EINVAL.
+ * vp_state_load: replaces the whole table state of ctx, the time of the last
+ * packet and the packet sequence; afterwards every entry point behaves as on
+ * the context that was saved. Configuration is not state: the NF kind and
+ * the table capacities must match, while addresses, ports, expiry times,
+ * static bridge rules and the CHT stay ctx's own. An image that is not
+ * exactly as described above -- sizes, counts, an index out of range or
+ * named twice, a time below 0, above last_now or decreasing along lru, a
+ * value out of range, a key that occurs twice, a non-zero pad byte -- is
+ * VP_EINVAL, vp_last_error() names the first offending field, and ctx still
+ * holds the state it had before the call. */
+#define VP_STATE_MAGIC 0x54535056u
+#define VP_STATE_VERSION 1u
+int vp_state_size(vp_ctx *ctx, uint64_t *bytes);
+int vp_state_save(vp_ctx *ctx, void *buf, uint64_t cap, uint64_t *bytes);
+int vp_state_load(vp_ctx *ctx, const void *buf, uint64_t bytes);
+
 /* Number of live flows / learned MACs / flows+backends. */
 int64_t vp_live_count(vp_ctx *ctx);
 

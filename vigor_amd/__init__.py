@@ -249,7 +249,8 @@ EXPORTS = ["vp_nat_create", "vp_bridge_create", "vp_lb_create", "vp_fw_create",
            "vp_probe_slots_w", "vp_process_one", "vp_last_kernel", "vp_serve_stats_get",
            "vp_serve_expiry_stats_get", "vp_tx_build", "vp_tx_pack", "vp_tx_rebatch",
            "vp_tx_merge", "vp_rx_unpack", "vp_rx_merge", "vp_tx_return", "vp_chain_create", "vp_chain_destroy",
-           "vp_chain_run", "vp_chain_view_get", "vp_chain_process_device"]
+           "vp_chain_run", "vp_chain_view_get", "vp_chain_process_device",
+           "vp_state_size", "vp_state_save", "vp_state_load"]
 
 _libs = {}
 
@@ -382,6 +383,12 @@ def lib(path: str | None = None):
     L.vp_chain_process_device.argtypes = [C.c_void_p, C.POINTER(DevBatchC),
                                           C.POINTER(TxReturnStatsC), C.c_void_p]
     L.vp_chain_process_device.restype = C.c_int
+    L.vp_state_size.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.vp_state_size.restype = C.c_int
+    L.vp_state_save.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.vp_state_save.restype = C.c_int
+    L.vp_state_load.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    L.vp_state_load.restype = C.c_int
     L.vp_last_error.argtypes = []
     L.vp_last_error.restype = C.c_char_p
     _libs[path] = L

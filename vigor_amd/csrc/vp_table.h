@@ -368,6 +368,18 @@ struct JournalDev {
 // sort. The first call allocates the ring (VIGPATH_SERVE_JOURNAL records per
 // index, default 8, at least 2). The resident kernel must not be running.
 int tbl_journal_seed(vp_ctx *c, FlowTable &t);
+// The journal seed's two steps, shared with vp_state_save (vp_state.hip):
+// every live index with its tseq into t.eidx / t.ekey, counted in
+// ctl->exp_count (queued; the caller reads the count back), and those k in
+// the dchain's LRU order (*seq / *idx point into the expiry workspace).
+int tbl_live_collect(vp_ctx *c, FlowTable &t);
+int tbl_live_sort(vp_ctx *c, FlowTable &t, uint32_t k, const uint64_t **seq,
+                  const uint32_t **idx);
+// The home-bucket layout a fresh table starts with (VIGPATH_MIX), and the
+// layout checks that follow new keys, for a table whose keys were all put in
+// at once (vp_state_load): reads the control block back first.
+uint32_t tbl_initial_mix();
+int tbl_layout_check(vp_ctx *c, FlowTable &t);
 
 // Owner mode (rank r of n): a fresh table keeps only the keys it owns in its
 // buckets (sized for 1/n of the keys) and every key by index in kv.

@@ -165,6 +165,11 @@ static uint64_t tbl_entries(const FlowTable &t) {
   return (uint64_t)(t.bmask + 1) * kBucketEntries;
 }
 
+uint32_t tbl_initial_mix() {
+  const char *mix = getenv("VIGPATH_MIX");  // diagnostics: start multiplicative
+  return mix && atoi(mix) ? kMixMul : 0;
+}
+
 int tbl_alloc(vp_ctx *c, FlowTable &t, uint32_t cap) {
   (void)c;
   // Every NF's flow table (vignat, vigfw, vigpol flows, vigbridge MACs, viglb
@@ -187,8 +192,7 @@ int tbl_alloc(vp_ctx *c, FlowTable &t, uint32_t cap) {
   t.bmask = (uint32_t)(nb - 1);
   t.nb_nominal = nb;
   t.cap = cap;
-  const char *mix = getenv("VIGPATH_MIX");  // diagnostics: start multiplicative
-  t.mix = mix && atoi(mix) ? kMixMul : 0;
+  t.mix = tbl_initial_mix();
   VP_TRY(dalloc(&t.bk, nb));
   VP_TRY(dalloc(&t.slot_of, cap));
   VP_TRY(dalloc(&t.hash_of, cap));
@@ -1642,6 +1646,38 @@ __global__ void jr_fill(TableDev t, const uint64_t *seq, const uint32_t *idx, ui
   }
 }
 
+// Every live index with the sequence number of its last touch, in any order,
+// into t.eidx / t.ekey, counted in ctl->exp_count: exp_collect with a cutoff
+// past every stamp (no stamp reaches INT64_MAX: times are >= 0 as int64).
+// Queued on c->stream; the count is read back by the caller.
+int tbl_live_collect(vp_ctx *c, FlowTable &t) {
+  VP_HIP(hipMemsetAsync(&t.ctl->exp_count, 0, 4, c->stream));
+  VP_HIP(hipMemsetAsync(&t.ctl->min_ts, 0xFF, 8, c->stream));
+  exp_collect<<<grid_for(t.cap, 256, 512), 256, 0, c->stream>>>(tbl_dev(t), INT64_MAX, t.ekey,
+                                                                t.eidx);
+  VP_HIP(hipGetLastError());
+  return 0;
+}
+
+// The k collected indices in the dchain's LRU order, oldest first (tseq
+// ascending, tbl_expire): *seq / *idx point into the table's expiry workspace.
+int tbl_live_sort(vp_ctx *c, FlowTable &t, uint32_t k, const uint64_t **seq,
+                  const uint32_t **idx) {
+  *seq = t.ekey;
+  *idx = t.eidx;
+  if (k > 1) {
+    VP_TRY(sort_pairs(c, t.ekey, t.ekey2, t.eidx, t.eidx2, k, 64));
+    *seq = t.ekey2;
+    *idx = t.eidx2;
+  }
+  return 0;
+}
+
+int tbl_layout_check(vp_ctx *c, FlowTable &t) {
+  VP_TRY(read_ctl(c, t));
+  return tbl_after_new_keys(c, t);
+}
+
 int tbl_journal_seed(vp_ctx *c, FlowTable &t) {
   if (!t.jr) {
     static const uint32_t mult = [] {
@@ -1654,22 +1690,13 @@ int tbl_journal_seed(vp_ctx *c, FlowTable &t) {
     VP_TRY(dalloc(&t.jr, 1));
     t.jr_n = (uint32_t)n;
   }
-  // every live index: no stamp reaches INT64_MAX (times are >= 0 as int64)
-  VP_HIP(hipMemsetAsync(&t.ctl->exp_count, 0, 4, c->stream));
-  VP_HIP(hipMemsetAsync(&t.ctl->min_ts, 0xFF, 8, c->stream));
-  exp_collect<<<grid_for(t.cap, 256, 512), 256, 0, c->stream>>>(tbl_dev(t), INT64_MAX, t.ekey,
-                                                                t.eidx);
-  VP_HIP(hipGetLastError());
+  VP_TRY(tbl_live_collect(c, t));
   VP_TRY(read_ctl(c, t));
   const uint32_t k = t.h_ctl.exp_count;
   if (k > t.cap) return state_fail("journal: %u live indices in a table of %u", k, t.cap);
-  const uint64_t *seq = t.ekey;
-  const uint32_t *idx = t.eidx;
-  if (k > 1) {
-    VP_TRY(sort_pairs(c, t.ekey, t.ekey2, t.eidx, t.eidx2, k, 64));
-    seq = t.ekey2;
-    idx = t.eidx2;
-  }
+  const uint64_t *seq = nullptr;
+  const uint32_t *idx = nullptr;
+  VP_TRY(tbl_live_sort(c, t, k, &seq, &idx));
   jr_fill<<<grid_for(std::max(k, 1u)), 256, 0, c->stream>>>(tbl_dev(t), seq, idx, k, t.jrec, t.jr);
   VP_HIP(hipGetLastError());
   VP_HIP(stream_wait(c->stream));

@@ -495,6 +495,32 @@ class NfBase:
         self._ck(self.L.vp_table_stats_get(self.h, table, C.byref(st)), "vp_table_stats_get")
         return {k: int(getattr(st, k)) for k, _ in TableStatsC._fields_ if k != "pad"}
 
+    def save_state(self) -> bytes:
+        """vp_state_save: the context's table state (both tables for viglb),
+        the LRU order among equal stamps and the free list's order included,
+        as the canonical image include/vigpath.h describes. Stops the
+        resident kernel."""
+        n = C.c_uint64()
+        self._ck(self.L.vp_state_size(self.h, C.byref(n)), "vp_state_size")
+        buf = np.empty(max(int(n.value), 1), np.uint8)
+        self._ck(self.L.vp_state_save(self.h, C.c_void_p(buf.ctypes.data), buf.size, C.byref(n)),
+                 "vp_state_save")
+        return buf[:int(n.value)].tobytes()
+
+    def load_state(self, data):
+        """vp_state_load: replace this context's whole table state with an
+        image (bytes-like) saved from a context of the same NF and
+        capacities; the configuration stays this context's. A malformed image
+        raises (vp_last_error names the first offending field) and leaves the
+        state as it was."""
+        buf = np.frombuffer(data, np.uint8)
+        if not buf.size:
+            buf = np.zeros(1, np.uint8)
+            size = 0
+        else:
+            size = buf.size
+        self._ck(self.L.vp_state_load(self.h, C.c_void_p(buf.ctypes.data), size), "vp_state_load")
+
     def live_count(self) -> int:
         v = self.L.vp_live_count(self.h)
         if v < 0:
