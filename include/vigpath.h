@@ -1090,6 +1090,105 @@ int vp_state_size(vp_ctx *ctx, uint64_t *bytes);
 int vp_state_save(vp_ctx *ctx, void *buf, uint64_t cap, uint64_t *bytes);
 int vp_state_load(vp_ctx *ctx, const void *buf, uint64_t bytes);
 
+/* ------------------------------------------------ incremental state images -- */
+
+/* What changed in a context's table state since a named earlier moment, and
+ * its application to a context that holds that earlier state: a standby that
+ * follows a live box without a full image every time.
+ *
+ * A mark names a moment of a context: seq is its packet sequence then, epoch
+ * the number of vp_state_load calls it has had (a load restarts the
+ * sequence, so marks of an earlier epoch name nothing any more). A full save
+ * taken at a mark, with no packet in between, is the image of that mark.
+ *
+ * The delta from a mark B to now, version 1. Little-endian, arrays and pads
+ * as in the image above.
+ *
+ *   header, 64 bytes
+ *     u32 magic        VP_STATE_DELTA_MAGIC (the bytes "VPSD")
+ *     u32 version      VP_STATE_DELTA_VERSION
+ *     u32 kind, u32 n_tables            as in the image
+ *     u64 total_bytes  of the whole delta
+ *     i64 last_now     the time of the last packet processed (-1: none yet)
+ *     u64 base_seq, u64 base_epoch      the mark B
+ *     u64 mark_seq, u64 mark_epoch      the mark of now
+ *                      (both as the saving context counts them)
+ *   then per table
+ *     table header, 32 bytes
+ *       u32 capacity, n_live, fresh_next, value_size, n_freed   of the state
+ *                        now, exactly as a full image taken now holds them
+ *                        (after the same tail normalisation)
+ *       u32 n_new
+ *       u32 reserved[2]  zero
+ *     u32 idx[n_new]     the indices that are live now and whose last touch
+ *                        (allocation or rejuvenation) came after B, in LRU
+ *                        order, oldest first
+ *     u32 freed[n_freed] the whole free list before the tail, as in the image
+ *     i64 ts[n_new]
+ *     u8  key[n_new][16]
+ *     u8  value[n_new][value_size]
+ *   Entry j of ts, key and value belongs to index idx[j]; idx, ts, key and
+ *   value together are called new[]. Nothing is said of an entry that was
+ *   not touched since B.
+ *
+ * Applying it to a context that holds the state at B gives the state now:
+ *   - every index outside freed[] and below fresh_next is live afterwards; an
+ *     index that was live and is named free (in freed[] or in the tail)
+ *     leaves, and its key is erased. Removals need no list of their own, and
+ *     need not be the oldest entries (viglb erases a flow out of LRU order).
+ *   - an index of new[] that holds the same key is updated in place (stamp,
+ *     value); if it holds another key or is free, the old key (if any) is
+ *     erased and the new one put in.
+ *   - the entries that are neither free nor in new[] (the kept ones) keep
+ *     their order, and new[] follows them in its own order.
+ *   - the free list becomes freed[] and the tail from fresh_next.
+ * freed[] travels whole, 4 bytes per freed index: a delta taken after a mass
+ * expiry is not small.
+ *
+ * All five calls stop the NF's resident kernel and wait for the context's
+ * stream first, and return VP_ENOTSUP on a context attached to a multi-GPU
+ * communicator. buf is host memory.
+ *
+ * vp_state_mark: *mark names the present state.
+ * vp_state_delta_size: *bytes = an upper bound of what a delta from base
+ * would take now.
+ * vp_state_delta_save: writes the delta from base to now, its size to *bytes
+ * and the mark of now to *mark. base must carry this context's current epoch
+ * and a seq not above the current one, else VP_EINVAL; any earlier mark of
+ * the epoch will do, so deltas are cumulative and several standbys may
+ * follow at their own pace. With cap too small it writes *bytes only and
+ * returns VP_EINVAL. It changes nothing in ctx.
+ * vp_state_follow: declares that ctx holds the state the primary named
+ * *mark (call it after vp_state_load of the image taken at that mark).
+ * vp_state_delta_apply: VP_EINVAL unless ctx is following, nothing has
+ * changed it since (no packet, no load), and the delta's base is the
+ * followed mark. On success the followed mark becomes the delta's mark. A
+ * delta that is not exactly as described -- sizes and offsets against the
+ * byte count, pad and reserved bytes, kind, table count, capacities, value
+ * sizes; n_live + n_freed + (capacity - fresh_next) != capacity; freed[]
+ * ending with fresh_next - 1; an index out of range, named twice in idx[] or
+ * freed[], in both, or inside the tail; a stamp below 0, above last_now or
+ * decreasing along new[]; new[0]'s stamp below the largest stamp of a kept
+ * entry; last_now below ctx's; a value out of range; a non-zero key pad
+ * byte; a key of new[] that a kept entry at another index holds, or that
+ * occurs twice; the kept entries plus n_new differing from n_live -- is
+ * VP_EINVAL as well. On every refusal vp_last_error() names the first
+ * offending field, and ctx holds the state and the followed mark it had.
+ * Processing packets on a following context promotes it: the following
+ * ends. */
+typedef struct vp_state_mark_t {
+  uint64_t seq;
+  uint64_t epoch;
+} vp_state_mark_t;
+#define VP_STATE_DELTA_MAGIC 0x44535056u
+#define VP_STATE_DELTA_VERSION 1u
+int vp_state_mark(vp_ctx *ctx, vp_state_mark_t *mark);
+int vp_state_delta_size(vp_ctx *ctx, const vp_state_mark_t *base, uint64_t *bytes);
+int vp_state_delta_save(vp_ctx *ctx, const vp_state_mark_t *base, void *buf, uint64_t cap,
+                        uint64_t *bytes, vp_state_mark_t *mark);
+int vp_state_follow(vp_ctx *ctx, const vp_state_mark_t *mark);
+int vp_state_delta_apply(vp_ctx *ctx, const void *buf, uint64_t bytes);
+
 /* Number of live flows / learned MACs / flows+backends. */
 int64_t vp_live_count(vp_ctx *ctx);
 

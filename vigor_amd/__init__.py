@@ -39,6 +39,15 @@ class TableStatsC(C.Structure):
                 ("pad", C.c_uint32)]
 
 
+class StateMarkC(C.Structure):
+    """vp_state_mark_t (include/vigpath.h)."""
+    _fields_ = [("seq", C.c_uint64), ("epoch", C.c_uint64)]
+
+
+STATE_DELTA_MAGIC = 0x44535056  # VP_STATE_DELTA_MAGIC, the bytes "VPSD"
+STATE_DELTA_VERSION = 1         # VP_STATE_DELTA_VERSION
+
+
 class ServeStatsC(C.Structure):
     """vp_serve_stats (include/vigpath.h)."""
     _fields_ = [("packets_one", C.c_uint64), ("bursts", C.c_uint64),
@@ -250,7 +259,9 @@ EXPORTS = ["vp_nat_create", "vp_bridge_create", "vp_lb_create", "vp_fw_create",
            "vp_serve_expiry_stats_get", "vp_tx_build", "vp_tx_pack", "vp_tx_rebatch",
            "vp_tx_merge", "vp_rx_unpack", "vp_rx_merge", "vp_tx_return", "vp_chain_create", "vp_chain_destroy",
            "vp_chain_run", "vp_chain_view_get", "vp_chain_process_device",
-           "vp_state_size", "vp_state_save", "vp_state_load"]
+           "vp_state_size", "vp_state_save", "vp_state_load", "vp_state_mark",
+           "vp_state_delta_size", "vp_state_delta_save", "vp_state_follow",
+           "vp_state_delta_apply"]
 
 _libs = {}
 
@@ -389,6 +400,18 @@ def lib(path: str | None = None):
     L.vp_state_save.restype = C.c_int
     L.vp_state_load.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     L.vp_state_load.restype = C.c_int
+    MP = C.POINTER(StateMarkC)
+    L.vp_state_mark.argtypes = [C.c_void_p, MP]
+    L.vp_state_mark.restype = C.c_int
+    L.vp_state_delta_size.argtypes = [C.c_void_p, MP, C.POINTER(C.c_uint64)]
+    L.vp_state_delta_size.restype = C.c_int
+    L.vp_state_delta_save.argtypes = [C.c_void_p, MP, C.c_void_p, C.c_uint64,
+                                      C.POINTER(C.c_uint64), MP]
+    L.vp_state_delta_save.restype = C.c_int
+    L.vp_state_follow.argtypes = [C.c_void_p, MP]
+    L.vp_state_follow.restype = C.c_int
+    L.vp_state_delta_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    L.vp_state_delta_apply.restype = C.c_int
     L.vp_last_error.argtypes = []
     L.vp_last_error.restype = C.c_char_p
     _libs[path] = L

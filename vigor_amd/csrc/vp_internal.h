@@ -107,6 +107,7 @@ hipError_t preload_rxmerge(hipStream_t s);
 hipError_t preload_txreturn(hipStream_t s);
 hipError_t preload_chain(hipStream_t s);
 hipError_t preload_state(hipStream_t s);
+hipError_t preload_statedelta(hipStream_t s);
 
 // vp_txpack.hip's one-block exclusive scan of m 64-bit sums in place, also
 // launched by vp_rx_unpack (vp_rxunpack.hip): <<<1, kTxpScanThreads>>>
@@ -717,4 +718,12 @@ struct vp_ctx {
   // the next launch seeds the journal; vp_serve_expiry_stats_get's counters
   bool jr_want = false;
   vp_serve_expiry_stats srv_exp{};
+  // incremental state images (vp_statedelta.hip): the vp_state_load calls so
+  // far (a mark's epoch); while following, the primary's mark whose state this
+  // context holds, and its own sequence when it was recorded (any packet, load
+  // or other change since moves c->seq or ends the following)
+  uint64_t st_epoch = 0;
+  bool st_following = false;
+  vp_state_mark_t st_mark{};
+  uint64_t st_follow_seq = 0;
 };

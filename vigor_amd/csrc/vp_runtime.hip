@@ -194,7 +194,8 @@ static int preload_units(int gpu, hipStream_t s) {
   for (auto f : {preload_runtime, preload_table, preload_nat, preload_bridge, preload_lb,
                  preload_fw, preload_pol, preload_comm, preload_mbuf, preload_tx,
                  preload_txpack, preload_txbatch, preload_txmerge, preload_rxunpack,
-                 preload_rxmerge, preload_txreturn, preload_chain, preload_state})
+                 preload_rxmerge, preload_txreturn, preload_chain, preload_state,
+                 preload_statedelta})
     VP_HIP(f(s));
   VP_HIP(hipStreamSynchronize(s));
   done.push_back(gpu);

@@ -19,103 +19,19 @@
 #include <cstring>
 #include <vector>
 
-#include "vp_table.h"
+#include "vp_state_dev.h"
 
 namespace vp {
 
 VP_PRELOAD_UNIT(state)
 
+using namespace stimg;
+
 namespace {
 
 constexpr uint32_t kStMagic = VP_STATE_MAGIC;
 constexpr uint32_t kStVersion = VP_STATE_VERSION;
-constexpr uint32_t kStHdr = 32, kStTblHdr = 32;
-
-// What a table keeps per index beside the stamps (the image's key and value).
-enum TblType : uint32_t { TT_NAT, TT_BRIDGE, TT_FW, TT_LBFLOW, TT_LBBACK, TT_POL };
-constexpr uint32_t kValSize[6] = {0, 4, 4, 4, 8, 16};
-const char *const kTblName[6] = {"flows", "MACs", "flows", "flows", "backends", "destinations"};
-
-// The per-index arrays outside the buckets (viglb backends[], vigpol dyn_vals).
-struct SideVals {
-  uint4 *be_rec;
-  uint64_t *pol_size;
-  int64_t *pol_time;
-};
-
-// One table's arrays inside an image on the device.
-struct ImgDev {
-  uint32_t *lru, *freed;
-  int64_t *ts;
-  uint4 *key;
-  uint8_t *val;
-  uint32_t n_live, n_freed, fresh;
-};
-
-template <class T>
-int dalloc(T **p, size_t count) {
-  if (count == 0) count = 1;
-  hipError_t e = hipMalloc((void **)p, sizeof(T) * count);
-  return e == hipSuccess ? 0 : hip_fail(e, "hipMalloc", __FILE__, __LINE__);
-}
-
-// The bits of a bucket entry's key words that are the libVig key; the others
-// carry the entry's value (vigbridge: word 2 the port; vigfw, viglb flows:
-// word 3 above the protocol byte) or are zero.
-__host__ __device__ __forceinline__ uint4 key_mask(uint32_t tt) {
-  switch (tt) {
-    case TT_NAT: return make_uint4(~0u, ~0u, ~0u, ~0u);
-    case TT_BRIDGE: return make_uint4(~0u, 0xFFFFu, 0u, 0u);
-    case TT_FW:
-    case TT_LBFLOW: return make_uint4(~0u, ~0u, ~0u, 0xFFu);
-    default: return make_uint4(~0u, 0u, 0u, 0u);
-  }
-}
-__device__ __forceinline__ uint4 and4(uint4 a, uint4 m) {
-  return make_uint4(a.x & m.x, a.y & m.y, a.z & m.z, a.w & m.w);
-}
-__device__ __forceinline__ bool any4(uint4 a) { return (a.x | a.y | a.z | a.w) != 0; }
-
-// The NF's own key hash of an image key (the generated *_hash functions the
-// classify kernels evaluate through position tables: vp_nat.hip flowid_hash,
-// vp_fw.hip fw_hash, vp_lb.hip lbflow_hash / ip_hash, vp_bridge.hip eth_hash,
-// vp_pol.hip pol_hash), as the chain of crc32c_u32 steps it is.
-__device__ __forceinline__ uint32_t key_hash(uint32_t tt, uint4 k) {
-  uint32_t h = 0;
-  switch (tt) {
-    case TT_NAT:  // src_port, dst_port, src_ip, dst_ip, internal_device, protocol
-      h = crc32c_u32(h, k.x & 0xFFFFu);
-      h = crc32c_u32(h, k.x >> 16);
-      h = crc32c_u32(h, k.y);
-      h = crc32c_u32(h, k.z);
-      h = crc32c_u32(h, k.w & 0xFFFFu);
-      h = crc32c_u32(h, (k.w >> 16) & 0xFFu);
-      break;
-    case TT_FW:  // src_port, dst_port, src_ip, dst_ip, protocol
-      h = crc32c_u32(h, k.x & 0xFFFFu);
-      h = crc32c_u32(h, k.x >> 16);
-      h = crc32c_u32(h, k.y);
-      h = crc32c_u32(h, k.z);
-      h = crc32c_u32(h, k.w & 0xFFu);
-      break;
-    case TT_LBFLOW:  // src_ip, dst_ip, src_port, dst_port, protocol
-      h = crc32c_u32(h, k.x);
-      h = crc32c_u32(h, k.y);
-      h = crc32c_u32(h, k.z & 0xFFFFu);
-      h = crc32c_u32(h, k.z >> 16);
-      h = crc32c_u32(h, k.w & 0xFFu);
-      break;
-    case TT_BRIDGE:  // rte_ether_addr_hash: one step per address byte
-      for (uint32_t b = 0; b < 4; b++) h = crc32c_u32(h, (k.x >> (8 * b)) & 0xFFu);
-      h = crc32c_u32(h, k.y & 0xFFu);
-      h = crc32c_u32(h, (k.y >> 8) & 0xFFu);
-      break;
-    default:  // ip_addr_hash
-      h = crc32c_u32(h, k.x);
-      break;
-  }
-  return h;
-}
+constexpr uint32_t kStHdr = 32;
 
 // ---------------------------------------------------------------- save --
 
@@ -150,10 +66,6 @@ __global__ __launch_bounds__(256) void st_freed(TableDev t, uint32_t *freed, uin
 
 // The image's arrays of one table, entry j = the j-th oldest live index.
 // Thread 0 also zeroes the pad bytes behind each array (pad[]: from, to).
-struct Pads {
-  uint8_t *at[5];
-  uint32_t n[5];
-};
 __global__ __launch_bounds__(256) void st_gather(TableDev t, uint32_t tt, SideVals sv,
                                                  const uint32_t *idx, ImgDev im, Pads pads) {
   const uint4 mask = key_mask(tt);
@@ -232,14 +144,6 @@ __global__ __launch_bounds__(256) void st_check(ImgDev im, uint32_t tt, uint32_t
       if (j == im.n_freed - 1 && i + 1 == im.fresh) st_fail(err, E_FREED_NORM, j);
     }
   }
-}
-
-// The entry's key words from the image's key and value.
-__device__ __forceinline__ uint4 raw_key(uint32_t tt, const ImgDev &im, uint32_t j) {
-  uint4 k = im.key[j];
-  if (tt == TT_BRIDGE) k.z = reinterpret_cast<const uint32_t *>(im.val)[j];
-  if (tt == TT_FW || tt == TT_LBFLOW) k.w |= reinterpret_cast<const uint32_t *>(im.val)[j] << 8;
-  return k;
 }
 
 // The bucket array built aside (`t`: new buckets, slot_of, hash_of and
@@ -325,10 +229,6 @@ __global__ __launch_bounds__(256) void st_commit(TableDev t, uint32_t tt, SideVa
 
 // ---------------------------------------------------------------- host --
 
-struct StTable {
-  FlowTable *t;
-  uint32_t tt;
-};
 int st_tables(vp_ctx *c, StTable out[2]) {
   switch (c->kind) {
     case KIND_NAT: out[0] = {&c->ft, TT_NAT}; return 1;
@@ -340,32 +240,8 @@ int st_tables(vp_ctx *c, StTable out[2]) {
   }
 }
 
-uint64_t pad16(uint64_t v) { return (v + 15) & ~15ull; }
+}  // namespace
 
-// One table's section of an image: offsets from the image's first byte.
-struct Section {
-  uint32_t cap, n_live, fresh, vsz, n_freed;
-  uint64_t lru, freed, ts, key, val, end;
-};
-void section_layout(Section &s, uint64_t at) {
-  s.lru = at + kStTblHdr;
-  s.freed = s.lru + pad16(4ull * s.n_live);
-  s.ts = s.freed + pad16(4ull * s.n_freed);
-  s.key = s.ts + pad16(8ull * s.n_live);
-  s.val = s.key + 16ull * s.n_live;
-  s.end = s.val + pad16((uint64_t)s.vsz * s.n_live);
-}
-ImgDev section_dev(const Section &s, uint8_t *img) {
-  return ImgDev{reinterpret_cast<uint32_t *>(img + s.lru), reinterpret_cast<uint32_t *>(img + s.freed),
-                reinterpret_cast<int64_t *>(img + s.ts), reinterpret_cast<uint4 *>(img + s.key),
-                img + s.val, s.n_live, s.n_freed, s.fresh};
-}
-
-// VP_EINVAL with its reason in vp_last_error().
-#define ST_BAD(...) (state_fail(__VA_ARGS__), VP_EINVAL)
-
-// Every state call's start: the resident kernel stopped, a pending timestamp
-// fold waited for, no communicator attached.
 int st_enter(vp_ctx *c, StTable tabs[2], int *ntabs) {
   if (!c) return VP_EINVAL;
   if (hipSetDevice(c->gpu) != hipSuccess) return VP_EIO;
@@ -376,15 +252,21 @@ int st_enter(vp_ctx *c, StTable tabs[2], int *ntabs) {
   return *ntabs ? 0 : VP_EINVAL;
 }
 
-struct DevBuf {  // freed on every way out
-  void *p = nullptr;
-  ~DevBuf() { hipFree(p); }
-};
+int st_launch_freed(vp_ctx *c, FlowTable &t, uint32_t *freed, uint32_t *res) {
+  st_freed<<<grid_for(t.cap), 256, 0, c->stream>>>(tbl_dev(t), freed, res);
+  VP_HIP(hipGetLastError());
+  return 0;
+}
 
-void put32(uint8_t *p, uint32_t v) { memcpy(p, &v, 4); }
-void put64(uint8_t *p, uint64_t v) { memcpy(p, &v, 8); }
-uint32_t get32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
-uint64_t get64(const uint8_t *p) { uint64_t v; memcpy(&v, p, 8); return v; }
+int st_launch_gather(vp_ctx *c, FlowTable &t, uint32_t tt, const uint32_t *idx, const ImgDev &im,
+                     const Pads &pads) {
+  st_gather<<<grid_for(std::max(im.n_live, 1u)), 256, 0, c->stream>>>(
+      tbl_dev(t), tt, SideVals{c->be_rec, c->pol_size, c->pol_time}, idx, im, pads);
+  VP_HIP(hipGetLastError());
+  return 0;
+}
+
+namespace {
 
 int state_save(vp_ctx *c, uint8_t *buf, uint64_t cap, uint64_t *bytes, bool size_only) {
   StTable tabs[2];
@@ -410,8 +292,7 @@ int state_save(vp_ctx *c, uint8_t *buf, uint64_t cap, uint64_t *bytes, bool size
   for (int k = 0; k < nt; k++) {
     FlowTable &t = *tabs[k].t;
     VP_TRY(tbl_live_collect(c, t));
-    st_freed<<<grid_for(t.cap), 256, 0, c->stream>>>(tbl_dev(t), t.eidx2, (uint32_t *)res.p + 2 * k);
-    VP_HIP(hipGetLastError());
+    VP_TRY(st_launch_freed(c, t, t.eidx2, (uint32_t *)res.p + 2 * k));
   }
   VP_HIP(hipMemcpyAsync(h_res, res.p, sizeof h_res, hipMemcpyDeviceToHost, c->stream));
   uint64_t at = kStHdr;
@@ -452,10 +333,7 @@ int state_save(vp_ctx *c, uint8_t *buf, uint64_t cap, uint64_t *bytes, bool size
       pads.at[a] = d + ends[a];
       pads.n[a] = (uint32_t)(pad16(ends[a]) - ends[a]);
     }
-    st_gather<<<grid_for(std::max(s.n_live, 1u)), 256, 0, c->stream>>>(
-        tbl_dev(t), tabs[k].tt, SideVals{c->be_rec, c->pol_size, c->pol_time}, idx,
-        section_dev(s, d), pads);
-    VP_HIP(hipGetLastError());
+    VP_TRY(st_launch_gather(c, t, tabs[k].tt, idx, section_dev(s, d), pads));
   }
   VP_HIP(hipMemcpyAsync(buf, d, total, hipMemcpyDeviceToHost, c->stream));
   VP_HIP(hipStreamSynchronize(c->stream));
@@ -581,7 +459,7 @@ int state_load(vp_ctx *c, const uint8_t *buf, uint64_t bytes) {
   for (int k = 0; k < nt; k++) {
     const Section &s = sec[k];
     const uint32_t tt = tabs[k].tt;
-    const uint32_t vmax = tt == TT_BRIDGE || tt == TT_FW ? 0x10000u : tt == TT_LBFLOW ? c->ft2.cap : 0u;
+    const uint32_t vmax = value_bound(c, tt);
     st_check<<<grid_for(std::max({s.n_live, s.n_freed, 1u})), 256, 0, c->stream>>>(
         section_dev(s, d), tt, s.cap, last_now, vmax, sw + words[k], err + k);
     VP_HIP(hipGetLastError());
@@ -656,6 +534,8 @@ int state_load(vp_ctx *c, const uint8_t *buf, uint64_t bytes) {
   c->last_now = last_now;
   c->seq = (uint64_t)most + 1;  // (past every tseq: the LRU ranks 0 .. n_live - 1)
   c->fold_pending = false;
+  c->st_epoch++;  // (the sequence restarted: marks taken before name nothing now)
+  c->st_following = false;
   for (int k = 0; k < nt; k++) VP_TRY(tbl_layout_check(c, *tabs[k].t));
   return 0;
 }

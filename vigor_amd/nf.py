@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import (BridgeConfigC, DevBatchC, FwConfigC, LbConfigC, MAX_DEV, MbufBatchC,
-               NatConfigC, PolConfigC, RX_MERGE_MAX, RxQueueC, RxStreamC, ServeExpiryStatsC, ServeStatsC, TableStatsC,
+               NatConfigC, PolConfigC, RX_MERGE_MAX, RxQueueC, RxStreamC, ServeExpiryStatsC, ServeStatsC, StateMarkC, TableStatsC,
                TX_MERGE_MAX, TxFramesC, TxListsC, TxMergedC, TxNextC, TxReturnStatsC, TxSourceC,
                TxStatsC, TxWayHomeC, _check, lib)
 
@@ -520,6 +520,43 @@ class NfBase:
         else:
             size = buf.size
         self._ck(self.L.vp_state_load(self.h, C.c_void_p(buf.ctypes.data), size), "vp_state_load")
+
+    def state_mark(self):
+        """vp_state_mark: (seq, epoch), the name of the present state; a
+        save_state() taken now, with no packet in between, is its image."""
+        m = StateMarkC()
+        self._ck(self.L.vp_state_mark(self.h, C.byref(m)), "vp_state_mark")
+        return int(m.seq), int(m.epoch)
+
+    def save_delta(self, base):
+        """vp_state_delta_save: (the delta from the mark `base` to now as
+        bytes, the mark of now). Any earlier mark of this context since its
+        last load_state will do as the base."""
+        b, m, n = StateMarkC(*base), StateMarkC(), C.c_uint64()
+        self._ck(self.L.vp_state_delta_size(self.h, C.byref(b), C.byref(n)), "vp_state_delta_size")
+        buf = np.empty(max(int(n.value), 1), np.uint8)
+        self._ck(self.L.vp_state_delta_save(self.h, C.byref(b), C.c_void_p(buf.ctypes.data),
+                                            buf.size, C.byref(n), C.byref(m)),
+                 "vp_state_delta_save")
+        return buf[:int(n.value)].tobytes(), (int(m.seq), int(m.epoch))
+
+    def follow(self, mark):
+        """vp_state_follow: this context holds the state its primary named
+        `mark` (call it after load_state of the image taken at that mark)."""
+        m = StateMarkC(*mark)
+        self._ck(self.L.vp_state_follow(self.h, C.byref(m)), "vp_state_follow")
+
+    def apply_delta(self, data):
+        """vp_state_delta_apply: bring this following context from the mark
+        it follows to the delta's. A delta of another base, a malformed one or
+        a context that changed since it followed raises (vp_last_error says
+        why) and leaves the state and the followed mark as they were."""
+        buf = np.frombuffer(data, np.uint8)
+        size = buf.size
+        if not size:
+            buf = np.zeros(1, np.uint8)
+        self._ck(self.L.vp_state_delta_apply(self.h, C.c_void_p(buf.ctypes.data), size),
+                 "vp_state_delta_apply")
 
     def live_count(self) -> int:
         v = self.L.vp_live_count(self.h)
