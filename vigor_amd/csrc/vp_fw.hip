@@ -650,7 +650,7 @@ static int fw_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   a.n_dev = c->fw.n_devices;
 
   // 64-byte slots: the classify launch also bins its touches (TouchBins)
-  const bool tiles64 = p1 > p0 && b->slot == 64 && c->coalesced_io;
+  const bool tiles64 = p1 > p0 && b->slot == 64;
   BinsPlan bp{};
   uint32_t grid64 = 0, range64 = 0;
   TileQueue rq{};

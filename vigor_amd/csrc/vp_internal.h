@@ -171,12 +171,11 @@ struct Ctl {
                         // (cumulative, never reset: the host takes differences)
   uint32_t last_first;  // unsorted new keys: 1 + the last first sighting's
                         // position in the segment (nku_firsts)
-  uint32_t arrive;      // classify blocks finished (tile_publish; 0 between launches)
 };
 
-// The control block as a fold kernel (or, one GPU, the classify's last
-// block: tile_publish) publishes it into page-locked host memory
-// (tbl_fold_read_ctl, vp_table.hip); the host polls `epoch`.
+// The control block as a fold kernel publishes it into page-locked host
+// memory (tbl_fold_read_ctl, vp_table.hip; ctl_publish, vp_table.h, states
+// what its ordering rests on); the host polls `epoch`.
 // Multi-GPU: the fold also publishes every rank's segment counters
 // (miss, defer, touch_ovf, reprobe: gathered on the device before the fold)
 // and, owner mode, this rank's key count per owner.
@@ -677,7 +676,6 @@ struct vp_ctx {
   uint32_t *crc_tab = nullptr;  // CRC position tables (LDS-staged)
   uint32_t *macw = nullptr;     // per device: d_addr|s_addr header words
   uint32_t wan_macw[3] = {0, 0, 0};
-  bool coalesced_io = true;  // LDS-staged 64 B frame I/O (VIGPATH_COALESCED=0 off)
   vp::Workspace ws;
   // multi-GPU (vp_attach_*): this rank's collectives, and during a batch the
   // global position of local packet 0 and the per-rank slice sizes

@@ -1148,7 +1148,7 @@ static int lb_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   }
   c->ft.ctl_clean = false;
   BinsPlan bp{};
-  const bool tiles64 = b->slot == 64 && c->coalesced_io;
+  const bool tiles64 = b->slot == 64;
   VP_HIP(ev_record(c->ktime, c->ev0, c->stream));
   if (tiles64) {
     // the flow touches go to the touch bins (256 of them: lb_classify64 keeps

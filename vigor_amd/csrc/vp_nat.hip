@@ -200,50 +200,11 @@ struct NatArgs {
   uint32_t *mhash;
   uint4 *mkq;
   uint32_t *mhq;
-  // 1024-thread tiles: bin entries staged in LDS and stored a whole line at
-  // a time (bins_put_staged; VIGPATH_BIN_STAGE=0 off, for A/B)
-  uint32_t bstage;
   // 1024-thread tiles: the block's range cut into `split` contiguous
   // sub-ranges, W / split waves interleaved over each (tile_split(); 0 or 1:
   // all W waves over the whole range)
   uint32_t split;
-  // one GPU, touch bins: the launch's last block publishes phase A's control
-  // block (tile_publish; pub.pub null: the fold does)
-  PubArgs pub;
 };
-
-// The end of a 64-byte tile block: every block releases its counters (its
-// XCD's L2 written back, so plain stores such as TouchBins' overflow flag
-// reach memory too) and counts itself in Ctl::arrive; the last one acquires
-// and publishes the control block to the host (ctl_publish), which then
-// learns phase A's counts a fold-kernel dispatch earlier and launches the
-// next batch while the fold still runs.
-// Off by default (VIGPATH_TILE_PUB=1: on): every block's release lengthened
-// the headline kernel by 6 us and the step by 5 (profiles/r06s_tile_pub.txt)
-// -- the host is not on the step's critical path; the fold and the two
-// dispatches around it are.
-static bool tile_pub_on() {
-  static const bool on = [] {
-    const char *e = getenv("VIGPATH_TILE_PUB");
-    return e && atoi(e) != 0;
-  }();
-  return on;
-}
-__device__ __forceinline__ void tile_publish(const NatArgs &a) {
-  if (!a.pub.pub) return;
-  // every wave's stores and atomics acknowledged (in its XCD's L2) before the
-  // barrier, so thread 0's release writes them back with its own
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  Ctl *ctl = const_cast<Ctl *>(a.pub.ctl);
-  const uint32_t n =
-      __hip_atomic_fetch_add(&ctl->arrive, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-  if (n != gridDim.x - 1) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // (the other blocks' releases)
-  __hip_atomic_store(&ctl->arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  ctl_publish(a.pub);
-}
 
 // Queue packet p (FlowId key, hash h) as a phase-B miss.
 __device__ __forceinline__ void miss_add(const NatArgs &a, uint32_t p, const uint32_t key[4],
@@ -752,14 +713,20 @@ __device__ __forceinline__ uint32_t dense128_tail(const uint4 d[8]) {
 // O: owner mode compiled in (false: the single-table kernels, whose owner
 // paths -- pass 1's routing tile, nat_issue's remote keys, route notes --
 // fold away with own.n a constant 0, fewer registers for the lean tile).
-template <uint32_t G, uint32_t H = 1, bool D = false, bool X = false, bool PR = G == 0,
-          uint32_t W = 4, bool ST = false, bool O = true>
+template <uint32_t G, uint32_t H = 1, bool D = false, bool X = false, uint32_t W = 4,
+          bool ST = false, bool O = true>
 __device__ __forceinline__ void nat_tiles(NatArgs a, uint32_t n_all, TouchBins bins,
                                           TileQueue rq) {
   static_assert(!X || G == 0, "header slots (X) are 64-byte slots");
   if constexpr (!O) {
     a.own.n = 0;
     a.own.all = 0;
+  }
+  // (the owner-mode 1024-thread tile, nat_classify64wo, runs only between
+  // ranks, where phase B sorts the union: no keys beside the misses)
+  if constexpr (O && W == 16) {
+    a.mkey = nullptr, a.mkq = nullptr;
+    a.mhash = nullptr, a.mhq = nullptr;
   }
   __shared__ uint32_t T[kNatTabWords];
   __shared__ uint4 stage[W][256];
@@ -772,7 +739,7 @@ __device__ __forceinline__ void nat_tiles(NatArgs a, uint32_t n_all, TouchBins b
   __shared__ uint32_t swc[kStaged ? kStageBins * kStageLines : 1];
   __shared__ uint32_t sgen[kStaged ? kStageBins * kStageLines : 1];
   const BinStage bst{sring, swc, sgen};
-  const bool staged = kStaged && bins.ent && bins.bbits <= 7 && a.bstage;
+  const bool staged = kStaged && bins.ent && bins.bbits <= 7;
   if (kStaged) bins_stage_init(bst);
   if (threadIdx.x == 0) nruns = 0;
   for (uint32_t i = threadIdx.x; i < kCurs; i += blockDim.x) cur[i] = 0;
@@ -1022,9 +989,9 @@ __device__ __forceinline__ void nat_tiles(NatArgs a, uint32_t n_all, TouchBins b
       const uint32_t sip = f.u32at2(26), dip = f.u32at2(30);
       // the hash and the row and next-tile requests at a raised wave
       // priority: the SIMD issues them ahead of other waves' rewrite and
-      // checksum arithmetic, which keeps more requests in flight (PR;
+      // checksum arithmetic, which keeps more requests in flight (G == 0:
       // 64-byte slots 0.4-0.6 % faster, 128-byte slots no change: r04ah/ai)
-      if constexpr (PR) __builtin_amdgcn_s_setprio(1);
+      if constexpr (G == 0) __builtin_amdgcn_s_setprio(1);
       const uint32_t lh = flowid_hash_batched(T, sp, dp, sip, dip, in, proto);
       const uint32_t b = home_bucket(lh, a.t.bmask, a.t.mix, nat_lin(T));
       // lane L fetches part L % 4 of the row of packet 16 j + L / 4: the four
@@ -1043,7 +1010,7 @@ __device__ __forceinline__ void nat_tiles(NatArgs a, uint32_t n_all, TouchBins b
       const uint4 q2 = rows[4 * (size_t)b2 + part];
       const uint4 q3 = rows[4 * (size_t)b3 + part];
       if (tile + tstep < tend) fetch(tile + tstep);
-      if constexpr (PR) __builtin_amdgcn_s_setprio(0);
+      if constexpr (G == 0) __builtin_amdgcn_s_setprio(0);
       wave_lds_sync();
       S[chunk_swz(lane)] = q0;
       S[chunk_swz(64 + lane)] = q1;
@@ -1236,7 +1203,6 @@ __device__ __forceinline__ void nat_tiles(NatArgs a, uint32_t n_all, TouchBins b
       a.miss[mbase + i] = a.mkq ? (uint32_t)(s0 + i) | kMissSlice : a.mq[s0 + i];
   }
   route_publish(a, cur + kCurDest, rb);
-  tile_publish(a);
 }
 
 __global__ __launch_bounds__(256, 4) void nat_classify64(NatArgs a, uint32_t n_all,
@@ -1249,33 +1215,16 @@ __global__ __launch_bounds__(256, 4) void nat_classify64(NatArgs a, uint32_t n_a
 // extra registers cost round robin 2.5 %)
 __global__ __launch_bounds__(1024, 1) void nat_classify64w(NatArgs a, uint32_t n_all,
                                                           TouchBins bins, TileQueue rq) {
-  nat_tiles<0, 1, false, false, true, 16, false, false>(a, n_all, bins, rq);
+  nat_tiles<0, 1, false, false, 16, false, false>(a, n_all, bins, rq);
 }
 __global__ __launch_bounds__(1024, 1) void nat_classify64ws(NatArgs a, uint32_t n_all,
                                                            TouchBins bins, TileQueue rq) {
-  nat_tiles<0, 1, false, false, true, 16, true, false>(a, n_all, bins, rq);
-}
-// Two 512-thread blocks per CU (VIGPATH_TILE_WAVES=8, for A/B): between the
-// 256-thread shape's faster bare pass and the 1024-thread kernel
-__global__ __launch_bounds__(512, 4) void nat_classify64h(NatArgs a, uint32_t n_all,
-                                                         TouchBins bins, TileQueue rq) {
-  nat_tiles<0, 1, false, false, true, 8, false, false>(a, n_all, bins, rq);
-}
-// Four 256-thread blocks per CU with the owner paths compiled out
-// (VIGPATH_TILE_WAVES=4, for A/B; nat_classify64 keeps them)
-__global__ __launch_bounds__(256, 4) void nat_classify64q(NatArgs a, uint32_t n_all,
-                                                         TouchBins bins, TileQueue rq) {
-  nat_tiles<0, 1, false, false, true, 4, false, false>(a, n_all, bins, rq);
+  nat_tiles<0, 1, false, false, 16, true, false>(a, n_all, bins, rq);
 }
 // owner mode's pass 1 on the 1024-thread tile (nat_phase_a_owner)
 __global__ __launch_bounds__(1024, 1) void nat_classify64wo(NatArgs a, uint32_t n_all,
                                                            TouchBins bins, TileQueue rq) {
-  nat_tiles<0, 1, false, false, true, 16>(a, n_all, bins, rq);
-}
-// (diagnostics, VIGPATH_PRIO=0: the lean tile without the raised priority)
-__global__ __launch_bounds__(256, 4) void nat_classify64_p0(NatArgs a, uint32_t n_all,
-                                                           TouchBins bins, TileQueue rq) {
-  nat_tiles<0, 1, false, false, false>(a, n_all, bins, rq);
+  nat_tiles<0, 1, false, false, 16>(a, n_all, bins, rq);
 }
 
 // 64-byte header slots of longer host frames (vp_process_mbufs, vp_mbuf.hip):
@@ -1321,43 +1270,24 @@ static uint32_t nat_block_waves() {
   return w;
 }
 
-static uint32_t nat_tile_waves_env() {
-  static const uint32_t w = [] {
-    const char *e = getenv("VIGPATH_TILE_WAVES");
-    const int v = e ? atoi(e) : 16;
-    return v == 8 || v == 4 ? (uint32_t)v : 16u;
-  }();
-  return w;
-}
-
 static const char *nat_tile_kernel_name(NatTileKernel k) {
   return k == nat_classify64w    ? "nat_classify64w"
-         : k == nat_classify64h  ? "nat_classify64h"
-         : k == nat_classify64q  ? "nat_classify64q"
          : k == nat_classify64ws ? "nat_classify64ws"
          : k == nat_classify64   ? "nat_classify64"
          : k == nat_classify64x  ? "nat_classify64x"
-         : k == nat_classify64_p0 ? "nat_classify64_p0"
          : k == nat_classify128  ? "nat_classify128"
                                  : "nat_classify_wide";
 }
 
 static uint32_t nat_tile_waves(NatTileKernel k) {
-  return k == nat_classify64w || k == nat_classify64ws ? 16u : k == nat_classify64h ? 8u : 4u;  // (64q: 4)
+  return k == nat_classify64w || k == nat_classify64ws ? 16u : 4u;
 }
 
 static NatTileKernel nat_tile_kernel(uint32_t slot, bool hdr_tail = false,
                                      bool staged = false) {
-  static const bool p0 = [] {
-    const char *e = getenv("VIGPATH_PRIO");
-    return e && atoi(e) == 0;
-  }();
   if (slot == 64 && !hdr_tail && nat_block_waves() == 16)
-    return staged ? nat_classify64ws
-           : nat_tile_waves_env() == 8 ? nat_classify64h
-           : nat_tile_waves_env() == 4 ? nat_classify64q
-                                       : nat_classify64w;
-  if (slot == 64) return hdr_tail ? nat_classify64x : p0 ? nat_classify64_p0 : nat_classify64;
+    return staged ? nat_classify64ws : nat_classify64w;
+  if (slot == 64) return hdr_tail ? nat_classify64x : nat_classify64;
   if (slot == 128) return nat_classify128;
   const uint32_t nch = (slot - 64) / 16;
   if (nch <= 1) return nat_classify_wide<1>;
@@ -2521,7 +2451,7 @@ static int nat_phase_a_owner(vp_ctx *c, const vp_dev_batch *b, NatArgs &a,
   Comm &m = *c->comm;
   const uint32_t n = (uint32_t)m.n, r = (uint32_t)m.r;
   const uint32_t np = p1 - p0;
-  ph->tiles64 = np && b->slot == 64 && c->coalesced_io;
+  ph->tiles64 = np && b->slot == 64;
   uint32_t first;
   if (ph->tiles64) {
     first = p0 & ~63u;
@@ -2755,7 +2685,7 @@ uint32_t nat_own_chunk_packets() {
 static OwnChunks own_chunks_plan(vp_ctx *c, const vp_dev_batch *b) {
   OwnChunks oc;
   const uint32_t pk = nat_own_chunk_packets();
-  if (!pk || b->slot != 64 || !c->coalesced_io || c->rank_n.empty()) return oc;
+  if (!pk || b->slot != 64 || c->rank_n.empty()) return oc;
   const uint32_t G = own_grid();
   const uint32_t vper = pk / 64 / G;
   uint64_t off = 0, K = 0;
@@ -2829,11 +2759,7 @@ static int nat_phase_a_owner_chunked(vp_ctx *c, const vp_dev_batch *b, NatArgs &
       VP_HIP(hipEventCreateWithFlags(&w.ev_ans[i], hipEventDisableTiming));
     }
   }
-  static const bool one_stream = [] {  // (diagnostics: no overlap between the streams)
-    const char *e = getenv("VIGPATH_OWN_ONESTREAM");
-    return e && atoi(e);
-  }();
-  hipStream_t S = c->stream, X = one_stream ? c->stream : w.xstream;
+  hipStream_t S = c->stream, X = w.xstream;
   static const uint32_t route_all = [] {
     const char *e = getenv("VIGPATH_ROUTE_ALL");
     return e && atoi(e) ? 1u : 0u;
@@ -3012,18 +2938,9 @@ static int nat_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   a.n_dev = c->nat.n_devices;
   a.tail = c->hdr_tail;  // (vp_process_mbufs' header slots; null otherwise)
   // one GPU: phase B takes the misses unsorted, with the keys phase A leaves
-  // (tbl_new_keys_unsorted; VIGPATH_NK_SORTED=1: the sorted path, for A/B);
-  // multi-GPU ranks allocate the union in global order (sorted)
-  static const bool nk_sorted = [] {
-    const char *e = getenv("VIGPATH_NK_SORTED");
-    return e && atoi(e);
-  }();
-  const bool nku = !c->comm && !nk_sorted;
-  static const bool bin_stage = [] {
-    const char *e = getenv("VIGPATH_BIN_STAGE");
-    return !e || atoi(e) != 0;
-  }();
-  a.bstage = bin_stage ? 1u : 0u;
+  // (tbl_new_keys_unsorted); multi-GPU ranks allocate the union in global
+  // order (sorted)
+  const bool nku = !c->comm;
   a.split = tile_split();
   if (nku) {
     a.mkey = reinterpret_cast<uint4 *>(w.mkey);
@@ -3045,7 +2962,7 @@ static int nat_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   // tiles of 64 packets (64-byte slots, or wider ones: nat_tiles): the
   // classify launch also bins its touches (TouchBins) and queues reprobes
   // per block (TileQueue)
-  const bool tiles64 = owner ? ph.tiles64 : p1 > p0 && c->coalesced_io;
+  const bool tiles64 = owner ? ph.tiles64 : p1 > p0;
   // (staged bin lines unless the last segment's tiles were mostly runs)
   const NatTileKernel tk = nat_tile_kernel(b->slot, a.tail != nullptr, !t.runs_seen);
   const uint32_t tw = nat_tile_waves(tk);
@@ -3064,26 +2981,16 @@ static int nat_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   if (!owner) {
   VP_TRY(seg_reset_counters(c, t));
   hostprof(1);
-  uint32_t pub_epoch = 0;  // (nonzero: the classify publishes, tile_publish)
-  if (p1 > p0) {  // (the launch's own timestamps in ev0 / ev1)
-    if (tiles64) {
-      NatArgs a64 = a;
-      if (bp.on) a64.log = nullptr;  // touches go to the bins only
-      if (bp.on && !c->comm && tile_pub_on()) {
-        pub_epoch = ++t.pub_epoch;
-        a64.pub = PubArgs{t.d_pub, t.ctl, pub_epoch, nullptr, nullptr, 0, 0};
-      }
-      c->last_kernel = nat_tile_kernel_name(tk);
-      if (c->ktime) {
-        VP_HIP(launch_timed(tk, grid64, 64 * tw, c->stream, c->ev0, c->ev1, a64,
-                            (uint32_t)b->n, bp.bins, rq));
-      } else {
-        tk<<<grid64, 64 * tw, 0, c->stream>>>(a64, (uint32_t)b->n, bp.bins, rq);
-        VP_HIP(hipGetLastError());
-      }
+  if (tiles64) {  // (the launch's own timestamps in ev0 / ev1)
+    NatArgs a64 = a;
+    if (bp.on) a64.log = nullptr;  // touches go to the bins only
+    c->last_kernel = nat_tile_kernel_name(tk);
+    if (c->ktime) {
+      VP_HIP(launch_timed(tk, grid64, 64 * tw, c->stream, c->ev0, c->ev1, a64,
+                          (uint32_t)b->n, bp.bins, rq));
     } else {
-      VP_HIP(launch_timed(nat_classify, grid_for(p1 - p0), 256, c->stream, c->ev0,
-                          c->ev1, a));
+      tk<<<grid64, 64 * tw, 0, c->stream>>>(a64, (uint32_t)b->n, bp.bins, rq);
+      VP_HIP(hipGetLastError());
     }
   } else {
     VP_HIP(ev_record(c->ktime, c->ev0, c->stream));
@@ -3094,7 +3001,7 @@ static int nat_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   // applied on top of it afterwards as late touches (tbl_late_touches: last
   // toucher still wins).
   hostprof(2);
-  VP_TRY(tbl_fold_read_ctl(c, t, bp, w.log, p0, p1, now, seq0, nullptr, pub_epoch));
+  VP_TRY(tbl_fold_read_ctl(c, t, bp, w.log, p0, p1, now, seq0));
   if (tiles64 && bp.on) {  // (the run tiles of this launch: the next one's kernel)
     const uint32_t nrun = t.h_ctl.run_tiles - t.last_run_tiles;
     t.last_run_tiles = t.h_ctl.run_tiles;

@@ -824,7 +824,7 @@ static int pol_segment(vp_ctx *c, const vp_dev_batch *b, const NowSpec &now,
   const uint32_t epoch = ++t.pub_epoch;  // phase A's counts, published by pol_runs
   const PubArgs pub{t.d_pub, t.ctl, epoch, nullptr, nullptr, 0, 0};
   VP_HIP(ev_record(c->ktime, c->ev0, c->stream));
-  const bool tile64 = b->slot == 64 && c->coalesced_io;
+  const bool tile64 = b->slot == 64;
   // vp_last_kernel: the classify kernel plus the phase-T path that produced
   // this segment's results (the sorting path until the grouping path is
   // known to have run, below)

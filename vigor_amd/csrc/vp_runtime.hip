@@ -204,8 +204,6 @@ static int preload_units(int gpu, hipStream_t s) {
 
 static int ctx_common(vp_ctx *c, int gpu) {
   c->gpu = gpu;
-  const char *co = getenv("VIGPATH_COALESCED");
-  c->coalesced_io = !co || atoi(co) != 0;  // default on (tools/ablate.py)
   VP_HIP(hipSetDevice(gpu));
   VP_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   VP_TRY(preload_units(gpu, c->stream));

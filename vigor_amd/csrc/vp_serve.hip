@@ -111,27 +111,26 @@ static void serve_yield(vp_ctx *c) {
   }
 }
 
-// Launch c's resident kernel on c->stream: the polling parameters every
-// server takes (kernel flags bits 10-23), then the NF's own launcher.
+// The polling parameters every server takes (kernel flags bits 10-23,
+// serve_poll), as measured on the MI355X through nf.c's loop:
+// the first poll after an answer waits kServeAfter wall-clock ticks of 10 ns
+// (45: 4.59-4.65 us per packet, 60: 4.73-4.83, 0: 5.41-5.80,
+// profiles/r06o_serve_after.txt, r06p_serve_after_sweep.txt);
+constexpr uint32_t kServeAfter = 45;
+// the delay adapts, from there (fixed against adaptive from 0 / 45 / 90:
+// profiles/r06r_serve_adaptive.txt);
+constexpr uint32_t kServeAdapt = 1;
+// and grows by kServeUp ticks after a request it missed (4 to 24 within the
+// run-to-run spread, profiles/r06aj_serve_up.txt).
+constexpr uint32_t kServeUp = 8;
+
+// Launch c's resident kernel on c->stream: the polling parameters, then the
+// NF's own launcher.
 static int serve_launch(vp_ctx *c) {
   serve_yield(c);
   ServeBox *dbox = nullptr;
   VP_HIP(hipHostGetDevicePointer((void **)&dbox, c->sbox, 0));
-  static const uint32_t after = [] {  // (wall-clock ticks of 10 ns, < 256)
-    const char *e = getenv("VIGPATH_SERVE_AFTER");
-    // (45: 4.59-4.65 us per packet, 60: 4.73-4.83, 0: 5.41-5.80 through
-    // nf.c's loop, profiles/r06o_serve_after.txt, r06p_serve_after_sweep.txt)
-    return e ? (uint32_t)std::min(255, std::max(0, atoi(e))) : 45u;
-  }();
-  static const uint32_t up = [] {  // (VIGPATH_SERVE_UP: ticks added after a late poll)
-    const char *e = getenv("VIGPATH_SERVE_UP");
-    return e ? (uint32_t)std::min(31, std::max(1, atoi(e))) : 8u;
-  }();
-  static const uint32_t adapt = [] {  // VIGPATH_SERVE_ADAPT=0: a fixed delay
-    const char *e = getenv("VIGPATH_SERVE_ADAPT");
-    return e && !atoi(e) ? 0u : 1u;
-  }();
-  const uint32_t flags = (after << 10) | (adapt << 18) | (up << 19);
+  const uint32_t flags = (kServeAfter << 10) | (kServeAdapt << 18) | (kServeUp << 19);
   const NfOps *nf = nf_ops(c->kind);
   if (!nf) return state_fail("no resident kernel for NF kind %d", c->kind);
   VP_TRY(nf->serve_launch(c, dbox, flags));

@@ -494,7 +494,7 @@ __device__ __forceinline__ void burst_answer(const ServeIo &io, ServeBox *box, u
 // plus its own time): a poll issued at once reads the mailbox too early and
 // the request waits for the poll after it, a whole round trip later. The
 // first poll after an answer waits `after` wall-clock ticks (flags bits
-// 10-17; VIGPATH_SERVE_AFTER) so that it reads about when the request lands.
+// 10-17; kServeAfter, vp_serve.hip) so that it reads about when the request lands.
 // The delay adapts (flags bit 18): a request the first poll caught takes a
 // tick off it, one that needed a later poll adds `up` (bits 19-23) -- a late
 // poll costs a round trip, an early one only its excess -- so it settles just

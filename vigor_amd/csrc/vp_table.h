@@ -56,17 +56,28 @@ __host__ __device__ __forceinline__ uint32_t owner_of(uint32_t h, uint32_t n) {
 
 // A fold kernel's publication of the control block into host-coherent
 // memory (tbl_fold_read_ctl): pub == null means off. One thread calls
-// ctl_publish after the launch that filled `ctl` has completed (or, the
-// classify's last block, after every block's release: tile_publish):
-// device-scope loads of the block, system-scope stores, the epoch last
-// (release).
+// ctl_publish after the launch that filled `ctl` has completed:
+// device-scope loads of the block, system-scope stores, the epoch last.
+//
+// The invariant the epoch's ordering rests on: every published word (the
+// CtlPub's ctl and xtra) is written by the one publishing thread, with a
+// system-scope store. Such stores go past the GPU's caches, so that thread's
+// `s_waitcnt vmcnt(0)` means all of them have completed, and a relaxed
+// system-scope store of the epoch after it cannot be seen before them. No
+// release is needed, and none is used: it would also write the XCD's L2
+// back (buffer_wbl2), which the fold kernel could not end before
+// (profiles/r06ag_fold.txt; the release form was last in commit 9a57567).
+// A later edit must therefore not
+//  - write a published word with a plain store (it may sit in L2 when the
+//    host sees the epoch), or
+//  - publish from more than one lane or wave (vmcnt counts only the waiting
+//    wave's own stores; another wave's may still be in flight).
 struct PubArgs {
   CtlPub *pub;
   const Ctl *ctl;
   uint32_t epoch;
   const uint32_t *x0, *x1;  // extra words (CtlPub::xtra): x0[0..n0), then x1[0..n1)
   uint32_t n0, n1;
-  uint32_t rel = 0;  // the epoch stored with a system-scope release (A/B)
 };
 static_assert(sizeof(Ctl) % 8 == 0, "Ctl is published as 8-byte words");
 __device__ __forceinline__ void ctl_publish(const PubArgs &a) {
@@ -87,16 +98,9 @@ __device__ __forceinline__ void ctl_publish(const PubArgs &a) {
                        __hip_atomic_load(s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
-  // The epoch after every word above has completed. Those are system-scope
-  // stores (past the GPU's caches), so waiting for them orders them; a
-  // release would also write the XCD's L2 back (buffer_wbl2), which the fold
-  // kernel could not end before (VIGPATH_PUB_RELEASE=1: that form, for A/B)
-  if (a.rel) {
-    __hip_atomic_store(&a.pub->epoch, a.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __hip_atomic_store(&a.pub->epoch, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  // The epoch after every word above has completed (the invariant at PubArgs)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __hip_atomic_store(&a.pub->epoch, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 struct NowSpec {
@@ -289,7 +293,7 @@ int tbl_touch_reduce(vp_ctx *c, FlowTable &t, const uint32_t *log, uint32_t p0,
 
 // Touch bins for one 64-byte classify launch over [p0, p1) of `kernel`
 // (vp_device.h TouchBins). plan->on is false when the launch cannot bin
-// (unaligned segment, table or range too large, VIGPATH_TOUCH_BINS=0); then
+// (unaligned segment, table or range too large); then
 // pass plan->bins (ent = null) to the kernel and fold with tbl_touch_reduce.
 struct BinsPlan {
   bool on;
@@ -332,7 +336,7 @@ int tbl_bins_reduce(vp_ctx *c, FlowTable &t, const BinsPlan &plan, uint32_t p0,
 int tbl_wait_pub(vp_ctx *c, FlowTable &t, uint32_t epoch);
 int tbl_fold_read_ctl(vp_ctx *c, FlowTable &t, const BinsPlan &bp, const uint32_t *log,
                       uint32_t p0, uint32_t p1, const NowSpec &now, uint64_t seq_base,
-                      const uint32_t *sends = nullptr, uint32_t pub_epoch = 0);
+                      const uint32_t *sends = nullptr);
 
 
 // expire_items_single_map for cutoff: free every allocated index with
@@ -491,8 +495,8 @@ __global__ void union_stamp(const uint32_t *first, const uint32_t *assign,
 
 uint32_t grid_for(uint64_t n, uint32_t block = 256, uint32_t max_blocks = 2048);
 // Persistent grid for a grid-stride kernel of 256-thread blocks: as many
-// blocks as the device holds at once (occupancy of `kernel` x CUs; env
-// VIGPATH_BLOCKS_PER_CU overrides the per-CU count), at most work_blocks. A
+// blocks as the device holds at once (occupancy of `kernel` x CUs), at most
+// work_blocks. A
 // larger grid leaves the blocks that do not fit to run after the first wave
 // of blocks, as a tail at lower occupancy.
 uint32_t resident_grid(const void *kernel, uint64_t work_blocks, int threads = 256);

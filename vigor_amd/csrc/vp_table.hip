@@ -59,8 +59,6 @@ uint32_t resident_grid(const void *kernel, uint64_t work_blocks, int threads) {
       cache.push_back(Entry{kernel, dev, cus, per});
     }
   }
-  const char *env = getenv("VIGPATH_BLOCKS_PER_CU");  // diagnostics
-  if (env && atoi(env) > 0) per = (uint32_t)atoi(env);
   const uint64_t g = std::min<uint64_t>(work_blocks, (uint64_t)cus * per);
   return (uint32_t)std::max<uint64_t>(g, 1);
 }
@@ -1049,8 +1047,10 @@ int tbl_touch_reduce(vp_ctx *c, FlowTable &t, const uint32_t *log, uint32_t p0,
 // writes ts/tseq in runs of 64 consecutive indices. About 8 B of traffic per
 // packet (one write while classifying, one read here).
 constexpr uint32_t kBinLocalMax = 16384;  // in-bin indices held in LDS
+// 64-entry chunks in flight per fold wave: 16 and 32 measured no faster
+// (tools/sessions/gpu_r03k.sh, profiles/r04_fold_variants.json)
+constexpr uint32_t kFoldU = 8;
 
-template <uint32_t kU>  // 64-entry chunks in flight per wave
 __global__ __launch_bounds__(1024) void touch_bins_reduce(
     const uint32_t *ent, const uint32_t *cnt, uint32_t nsrc, uint32_t cap,
     uint32_t pbits, uint32_t bbits, uint32_t range, uint32_t L, uint32_t tcap,
@@ -1075,6 +1075,7 @@ __global__ __launch_bounds__(1024) void touch_bins_reduce(
   __syncthreads();
   const uint32_t lane = threadIdx.x & 63, nw = blockDim.x >> 6;
   const uint32_t pmask = (1u << pbits) - 1;
+  constexpr uint32_t kU = kFoldU;
   // wave w takes slices w, w + nw, ...; 64 of them per round, their sizes
   // loaded by one instruction (lane l <-> slice w + l * nw). The round's
   // slices are one list of 64-entry chunks (chunk t of the list belongs to
@@ -1171,32 +1172,29 @@ int tbl_bins_plan(vp_ctx *c, FlowTable &t, const void *kernel, uint32_t p0,
                   uint32_t vper) {
   Workspace &w = c->ws;
   *plan = BinsPlan{};
-  const char *env = getenv("VIGPATH_TOUCH_BINS");  // diagnostics: 0 = off
-  if ((env && !atoi(env)) || (p0 & 63) || p1 <= p0) return 0;
+  if ((p0 & 63) || p1 <= p0) return 0;
   const uint32_t tiles = (p1 - p0 + 63) / 64;
   const uint32_t grid = vper ? (tiles + vper - 1) / vper
                             : resident_grid(kernel, (tiles + waves - 1) / waves,
                                             64 * (int)waves);
   const uint32_t per_b = vper ? vper : (tiles + grid - 1) / grid;
   const uint32_t range = per_b * 64;
-  // The fewest bins (>= 2^bbits_min) whose in-bin index range fits the
+  // The fewest bins (>= 2^kBinBitsMin) whose in-bin index range fits the
   // fold's LDS, and at least 256 fold blocks whatever the bin count (2^sbits
   // per bin). A block keeps one partly written line per bin slice: at 256
   // bins, 32 MB over the chip, as much as all the L2s, which shuffled
   // touches (no runs) pay for (tools/sessions/gpu_r04ba.sh);
-  // two run words per block and bin keep round robin whole at 128.
-  static const uint32_t bbits_min = [] {  // (VIGPATH_BIN_BITS, for A/B)
-    const char *e = getenv("VIGPATH_BIN_BITS");
-    const int v = e ? atoi(e) : 7;
-    return v >= 6 && v <= 10 ? (uint32_t)v : 7u;
-  }();
+  // two run words per block and bin keep round robin whole at 128. 64 bins
+  // made the fold slower and 256 the uniform order (tools/sessions/
+  // gpu_r05zr.sh, interleaved twice; the figures are in DESIGN.md §5.1).
+  constexpr uint32_t kBinBitsMin = 7;
   auto split = [](uint32_t bb) { return bb < 8 ? 8 - bb : 0u; };
   auto in_bin = [&](uint32_t bb) {  // in-bin index range for 2^bb bins: a
     // whole number of runs per fold block
     const uint32_t q = kBinRunBits + split(bb);
     return (((uint64_t)t.cap + ((uint64_t)1 << (q + bb)) - 1) >> (q + bb)) << q;
   };
-  uint32_t bbits = std::max(bbits_min, std::min<uint32_t>(min_bits, 10));
+  uint32_t bbits = std::max(kBinBitsMin, std::min<uint32_t>(min_bits, 10));
   while (bbits < 10 && (in_bin(bbits) >> split(bbits)) > kBinLocalMax) bbits++;
   const uint32_t sbits = split(bbits);
   const uint32_t nbins = 1u << bbits;
@@ -1242,11 +1240,7 @@ int tbl_bins_plan(vp_ctx *c, FlowTable &t, const void *kernel, uint32_t p0,
     VP_TRY(dalloc(&w.bins_rtab, nr));
     w.bins_rtab_n = nr;
   }
-  static const uint32_t runs_env = [] {  // (VIGPATH_BIN_RUNS=0: off, for A/B)
-    const char *e = getenv("VIGPATH_BIN_RUNS");
-    return e ? (uint32_t)atoi(e) : 1u;
-  }();
-  const uint32_t runs = runs_env && range <= (1u << 20) && (L >> kBinRunBits) < (1u << 12);
+  const uint32_t runs = range <= (1u << 20) && (L >> kBinRunBits) < (1u << 12);
   plan->bins = TouchBins{w.bins_ent, w.bins_cnt, &t.ctl->touch_ovf, w.ovf_q,
                          w.ovf_cnt, w.log, cap, pbits, bbits, grid, w.bins_rtab, runs,
                          rwords};
@@ -1255,22 +1249,8 @@ int tbl_bins_plan(vp_ctx *c, FlowTable &t, const void *kernel, uint32_t p0,
 
 static int bins_reduce(vp_ctx *c, FlowTable &t, const BinsPlan &plan, uint32_t p0,
                        const NowSpec &now, uint64_t seq_base, PubArgs pub) {
-  static const uint32_t rel = [] {  // (VIGPATH_PUB_RELEASE=1: ctl_publish's release form)
-    const char *e = getenv("VIGPATH_PUB_RELEASE");
-    return e && atoi(e) ? 1u : 0u;
-  }();
-  pub.rel = rel;
-  // chunks in flight per fold wave (VIGPATH_FOLD_U: 8, 16 or 32; 16 and 32
-  // measured no faster than 8, r03k)
-  static const uint32_t fold_u = [] {
-    const char *e = getenv("VIGPATH_FOLD_U");
-    const int v = e ? atoi(e) : 0;
-    return v == 16 || v == 32 ? (uint32_t)v : 8u;
-  }();
-  auto *fold = fold_u == 8 ? touch_bins_reduce<8> : fold_u == 32 ? touch_bins_reduce<32>
-                                                                 : touch_bins_reduce<16>;
   const uint32_t Lp = plan.L >> plan.sbits;
-  fold<<<1u << (plan.bins.bbits + plan.sbits), 1024, 4u * (Lp + (Lp >> kBinRunBits)),
+  touch_bins_reduce<<<1u << (plan.bins.bbits + plan.sbits), 1024, 4u * (Lp + (Lp >> kBinRunBits)),
          c->stream>>>(plan.bins.ent, plan.bins.cnt, plan.grid, plan.bins.cap, plan.bins.pbits,
                       plan.bins.bbits, plan.range, plan.L, t.cap, p0, now, seq_base, t.ts,
                       t.tseq, pub, plan.bins.rtab, plan.sbits, plan.maxmode ? 1u : 0u,
@@ -1289,8 +1269,6 @@ int tbl_bins_reduce(vp_ctx *c, FlowTable &t, const BinsPlan &plan, uint32_t p0,
 // (the classify launch has completed: kernel boundary) and publishes it into
 // host-coherent memory, so no copy launch and its kernel boundary sit between
 // the classify and the fold; the host polls for it while the fold runs.
-// One GPU, 64-byte tiles (pub_epoch != 0): the classify's last block has
-// published it already (tile_publish, vp_nat.hip) and the fold only folds.
 // Without bins: a copy behind phase A, then the log fold. On return h_ctl
 // holds phase A's counts; the fold may still be running.
 // Multi-GPU (every rank, every segment, so the collective always matches):
@@ -1319,7 +1297,7 @@ int tbl_wait_pub(vp_ctx *c, FlowTable &t, uint32_t epoch) {
 
 int tbl_fold_read_ctl(vp_ctx *c, FlowTable &t, const BinsPlan &bp, const uint32_t *log,
                       uint32_t p0, uint32_t p1, const NowSpec &now, uint64_t seq_base,
-                      const uint32_t *sends, uint32_t pub_epoch) {
+                      const uint32_t *sends) {
   Workspace &w = c->ws;
   const uint32_t nr = c->comm ? (uint32_t)c->comm->n : 0u;
   const uint32_t ns = sends ? nr : 0u;
@@ -1344,12 +1322,9 @@ int tbl_fold_read_ctl(vp_ctx *c, FlowTable &t, const BinsPlan &bp, const uint32_
     }
     return 0;
   }
-  // (pub_epoch != 0: the classify launch publishes the block itself, one GPU)
-  const uint32_t epoch = pub_epoch ? pub_epoch : ++t.pub_epoch;
+  const uint32_t epoch = ++t.pub_epoch;
   VP_TRY(bins_reduce(c, t, bp, p0, now, seq_base,
-                     pub_epoch ? PubArgs{}
-                               : PubArgs{t.d_pub, t.ctl, epoch, w.gath, sends, kPubGath * nr,
-                                         ns}));
+                     PubArgs{t.d_pub, t.ctl, epoch, w.gath, sends, kPubGath * nr, ns}));
   hostprof(3);
   VP_TRY(tbl_wait_pub(c, t, epoch));
   if (nr) {
