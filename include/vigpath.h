@@ -1189,6 +1189,65 @@ int vp_state_delta_save(vp_ctx *ctx, const vp_state_mark_t *base, void *buf, uin
 int vp_state_follow(vp_ctx *ctx, const vp_state_mark_t *mark);
 int vp_state_delta_apply(vp_ctx *ctx, const void *buf, uint64_t bytes);
 
+/* ------------------------------------------------------ table lookups -- */
+
+/* Ask a context's table about a batch of keys or of indices without copying
+ * the table: is this flow tracked, when was it last seen, what is bound to
+ * it. Read-only, answered on the device, n queries in one call.
+ *
+ * `table` is as in vp_table_stats_get: 0 the NF's flow table, 1 viglb's
+ * backends. Keys, stamps and values are exactly those of the state image,
+ * version 1 (above): the 16-byte zero-padded key, and per table the same
+ * value_size and value encoding. A lookup of an image's key[j] returns
+ * lru[j], ts[j] and value[j].
+ *
+ * vp_table_lookup, by key: query q hits iff a live entry holds exactly the
+ * 16 bytes keys[q]. A key with a non-zero pad byte is therefore a miss, not
+ * an error. A key may be given twice; both queries get the same answer.
+ * vp_table_entries, by index: an index at or above the capacity, or one that
+ * is not allocated, is a miss. For vignat the index is the flow's external
+ * port minus start_port, so this is the reverse NAT lookup: which internal
+ * 5-tuple holds external port P is entry P - start_port.
+ * vp_table_value_size: *bytes = the table's value_size (0 for vignat); the
+ * resident kernel stays.
+ *
+ * Every array of vp_lookup_out is device memory of n entries, written one
+ * entry per query, and any of them may be NULL (not wanted). keys is [n][16]
+ * and idx [n], device memory.
+ *
+ * The two queries change nothing in the context: no entry is rejuvenated,
+ * the packet sequence does not advance, no mark is set and a vp_state_follow
+ * stays in force, the vp_serve_* statistics and the touch journal's validity
+ * are as before. Like the state calls they stop the NF's resident kernel and
+ * wait for the context's stream first, so the timestamp fold a
+ * vp_process_device call with affine time may leave running is visible.
+ * They then run on `stream` (NULL: the context's own) and return once the
+ * results are in device memory.
+ *
+ * VP_ENOTSUP on a context attached to a multi-GPU communicator. VP_EINVAL,
+ * with the field named by vp_last_error(): a NULL ctx or out; a table the NF
+ * does not have; n > 0 with NULL keys / idx; a pointer that is not 16-byte
+ * aligned (keys, key), 8-byte aligned (ts), 4-byte aligned (index, idx) or,
+ * for value, aligned to value_size (4, 8 or 16). A refused call writes
+ * nothing. n == 0 is VP_OK and launches nothing. */
+#define VP_LOOKUP_MISS 0xFFFFFFFFu
+
+typedef struct vp_lookup_out {        /* all device pointers; any may be NULL */
+  uint32_t *index;   /* [n]  by key: the entry's index, or VP_LOOKUP_MISS
+                             by index: idx[q] if live, else VP_LOOKUP_MISS   */
+  int64_t  *ts;      /* [n]  the entry's stamp; 0 for a miss                 */
+  uint8_t  *key;     /* [n][16] the entry's key, zero-padded as in the image;
+                             zero for a miss                                 */
+  uint8_t  *value;   /* [n][value_size] as in the image; zero for a miss;
+                             never touched when value_size is 0 (vignat)     */
+} vp_lookup_out;
+
+int vp_table_lookup (vp_ctx *ctx, int table, uint32_t n, const uint8_t  *keys /* [n][16] device */,
+                     const vp_lookup_out *out, void *stream);
+int vp_table_entries(vp_ctx *ctx, int table, uint32_t n, const uint32_t *idx  /* [n] device */,
+                     const vp_lookup_out *out, void *stream);
+int vp_table_value_size(vp_ctx *ctx, int table, uint32_t *bytes);
+
 /* Number of live flows / learned MACs / flows+backends. */
 int64_t vp_live_count(vp_ctx *ctx);
 

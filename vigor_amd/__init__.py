@@ -48,6 +48,15 @@ STATE_DELTA_MAGIC = 0x44535056  # VP_STATE_DELTA_MAGIC, the bytes "VPSD"
 STATE_DELTA_VERSION = 1         # VP_STATE_DELTA_VERSION
 
 
+class VpLookupOutC(C.Structure):
+    """vp_lookup_out (include/vigpath.h): device pointers, any may be NULL."""
+    _fields_ = [("index", C.c_void_p), ("ts", C.c_void_p), ("key", C.c_void_p),
+                ("value", C.c_void_p)]
+
+
+LOOKUP_MISS = 0xFFFFFFFF  # VP_LOOKUP_MISS
+
+
 class ServeStatsC(C.Structure):
     """vp_serve_stats (include/vigpath.h)."""
     _fields_ = [("packets_one", C.c_uint64), ("bursts", C.c_uint64),
@@ -261,7 +270,8 @@ EXPORTS = ["vp_nat_create", "vp_bridge_create", "vp_lb_create", "vp_fw_create",
            "vp_chain_run", "vp_chain_view_get", "vp_chain_process_device",
            "vp_state_size", "vp_state_save", "vp_state_load", "vp_state_mark",
            "vp_state_delta_size", "vp_state_delta_save", "vp_state_follow",
-           "vp_state_delta_apply"]
+           "vp_state_delta_apply", "vp_table_lookup", "vp_table_entries",
+           "vp_table_value_size"]
 
 _libs = {}
 
@@ -412,6 +422,12 @@ def lib(path: str | None = None):
     L.vp_state_follow.restype = C.c_int
     L.vp_state_delta_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     L.vp_state_delta_apply.restype = C.c_int
+    for name in ("vp_table_lookup", "vp_table_entries"):
+        getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p,
+                                     C.POINTER(VpLookupOutC), C.c_void_p]
+        getattr(L, name).restype = C.c_int
+    L.vp_table_value_size.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint32)]
+    L.vp_table_value_size.restype = C.c_int
     L.vp_last_error.argtypes = []
     L.vp_last_error.restype = C.c_char_p
     _libs[path] = L

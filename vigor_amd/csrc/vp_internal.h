@@ -108,6 +108,7 @@ hipError_t preload_txreturn(hipStream_t s);
 hipError_t preload_chain(hipStream_t s);
 hipError_t preload_state(hipStream_t s);
 hipError_t preload_statedelta(hipStream_t s);
+hipError_t preload_lookup(hipStream_t s);
 
 // vp_txpack.hip's one-block exclusive scan of m 64-bit sums in place, also
 // launched by vp_rx_unpack (vp_rxunpack.hip): <<<1, kTxpScanThreads>>>

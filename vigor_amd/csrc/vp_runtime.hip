@@ -195,7 +195,7 @@ static int preload_units(int gpu, hipStream_t s) {
                  preload_fw, preload_pol, preload_comm, preload_mbuf, preload_tx,
                  preload_txpack, preload_txbatch, preload_txmerge, preload_rxunpack,
                  preload_rxmerge, preload_txreturn, preload_chain, preload_state,
-                 preload_statedelta})
+                 preload_statedelta, preload_lookup})
     VP_HIP(f(s));
   VP_HIP(hipStreamSynchronize(s));
   done.push_back(gpu);

@@ -68,26 +68,14 @@ __global__ __launch_bounds__(256) void st_freed(TableDev t, uint32_t *freed, uin
 // Thread 0 also zeroes the pad bytes behind each array (pad[]: from, to).
 __global__ __launch_bounds__(256) void st_gather(TableDev t, uint32_t tt, SideVals sv,
                                                  const uint32_t *idx, ImgDev im, Pads pads) {
-  const uint4 mask = key_mask(tt);
   for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < im.n_live;
        j += gridDim.x * blockDim.x) {
     const uint32_t i = idx[j];
-    const uint4 raw = tbl_key_of(t, i);
+    const Entry e = entry_of(t, tt, sv, i, tbl_key_of(t, i));
     im.lru[j] = i;
-    im.ts[j] = (int64_t)t.ts[i];
-    im.key[j] = and4(raw, mask);
-    if (tt == TT_BRIDGE) {
-      reinterpret_cast<uint32_t *>(im.val)[j] = raw.z;
-    } else if (tt == TT_FW || tt == TT_LBFLOW) {
-      reinterpret_cast<uint32_t *>(im.val)[j] = raw.w >> 8;
-    } else if (tt == TT_LBBACK) {
-      const uint4 r = sv.be_rec[i];  // {ip, mac 0-3, mac 4-5 | nic << 16, 0}
-      reinterpret_cast<uint2 *>(im.val)[j] = make_uint2(r.y, r.z);
-    } else if (tt == TT_POL) {
-      const uint64_t s = sv.pol_size[i], b = (uint64_t)sv.pol_time[i];
-      reinterpret_cast<uint4 *>(im.val)[j] =
-          make_uint4((uint32_t)s, (uint32_t)(s >> 32), (uint32_t)b, (uint32_t)(b >> 32));
-    }
+    im.ts[j] = e.ts;
+    im.key[j] = e.key;
+    value_put(tt, im.val, j, e.val);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0)
     for (uint32_t a = 0; a < 5; a++)
@@ -227,6 +215,8 @@ __global__ __launch_bounds__(256) void st_commit(TableDev t, uint32_t tt, SideVa
   }
 }
 
+}  // namespace
+
 // ---------------------------------------------------------------- host --
 
 int st_tables(vp_ctx *c, StTable out[2]) {
@@ -239,8 +229,6 @@ int st_tables(vp_ctx *c, StTable out[2]) {
     default: return 0;
   }
 }
-
-}  // namespace
 
 int st_enter(vp_ctx *c, StTable tabs[2], int *ntabs) {
   if (!c) return VP_EINVAL;

@@ -112,6 +112,43 @@ __device__ __forceinline__ uint32_t key_hash(uint32_t tt, uint4 k) {
   return h;
 }
 
+// What the image says of one live index: its stamp, its key and its value
+// (the first kValSize[tt] bytes of val, the rest zero). One reader for the
+// save's gather and the lookups (vp_lookup.hip).
+struct Entry {
+  int64_t ts;
+  uint4 key, val;
+};
+// raw: the key words of index i's bucket entry (tbl_key_of, or the entry a
+// probe stopped at).
+__device__ __forceinline__ Entry entry_of(const TableDev &t, uint32_t tt, const SideVals &sv,
+                                          uint32_t i, uint4 raw) {
+  Entry e{(int64_t)t.ts[i], and4(raw, key_mask(tt)), make_uint4(0u, 0u, 0u, 0u)};
+  if (tt == TT_BRIDGE) {
+    e.val.x = raw.z;
+  } else if (tt == TT_FW || tt == TT_LBFLOW) {
+    e.val.x = raw.w >> 8;
+  } else if (tt == TT_LBBACK) {
+    const uint4 r = sv.be_rec[i];  // {ip, mac 0-3, mac 4-5 | nic << 16, 0}
+    e.val.x = r.y;
+    e.val.y = r.z;
+  } else if (tt == TT_POL) {
+    const uint64_t s = sv.pol_size[i], b = (uint64_t)sv.pol_time[i];
+    e.val = make_uint4((uint32_t)s, (uint32_t)(s >> 32), (uint32_t)b, (uint32_t)(b >> 32));
+  }
+  return e;
+}
+// Entry j of a value array: kValSize[tt] bytes of v (vignat: nothing).
+__device__ __forceinline__ void value_put(uint32_t tt, uint8_t *val, uint32_t j, uint4 v) {
+  if (tt == TT_BRIDGE || tt == TT_FW || tt == TT_LBFLOW) {
+    reinterpret_cast<uint32_t *>(val)[j] = v.x;
+  } else if (tt == TT_LBBACK) {
+    reinterpret_cast<uint2 *>(val)[j] = make_uint2(v.x, v.y);
+  } else if (tt == TT_POL) {
+    reinterpret_cast<uint4 *>(val)[j] = v;
+  }
+}
+
 // The entry's key words from the image's key and value.
 __device__ __forceinline__ uint4 raw_key(uint32_t tt, const ImgDev &im, uint32_t j) {
   uint4 k = im.key[j];
@@ -179,6 +216,9 @@ inline uint64_t get64(const uint8_t *p) { uint64_t v; memcpy(&v, p, 8); return v
 // pending timestamp fold waited for, no communicator attached; the NF's
 // tables in image order.
 int st_enter(vp_ctx *c, stimg::StTable tabs[2], int *ntabs);
+// The NF's tables in image order and their number, nothing stopped or
+// waited for (0: a context of no known kind).
+int st_tables(vp_ctx *c, stimg::StTable out[2]);
 // st_freed: the free list in hand-out order with the never-used tail
 // normalised into freed[] (room for stack_top entries), res = {n_freed, the
 // normalised fresh_next}. Queued on c->stream.

@@ -201,6 +201,44 @@ __device__ __forceinline__ uint32_t tbl_probe(const TableDev &t, uint32_t h,
                             w3);
 }
 
+// tbl_probe's walk for a caller that knows the table's key only as a mask
+// over the entry's four words (the state images' key_mask; the other bits
+// carry the entry's value): buckets from the home bucket on, entries in
+// order, an empty entry ends the path, an erased one is passed over. `key`
+// has no bit outside `mask`. Returns the index and the entry's own words in
+// *raw, or kNone.
+__device__ __forceinline__ uint32_t tbl_probe_masked(const TableDev &t, uint32_t h, uint4 key,
+                                                     uint4 mask, uint4 *raw) {
+  uint32_t b = home_bucket(h, t.bmask, t.mix, t.lin);
+  for (uint32_t s = 0; s <= t.bmask; s++) {
+    const uint4 *q = reinterpret_cast<const uint4 *>(t.bk + b);
+    // (entry by entry with static names, as bucket_match: an array of the
+    // entries indexed by the loop went to scratch memory)
+    const uint4 k0 = q[0], k1 = q[1], k2 = q[2], ix = q[3];
+    auto holds = [&](const uint4 &k) {
+      return (((k.x ^ key.x) & mask.x) | ((k.y ^ key.y) & mask.y) | ((k.z ^ key.z) & mask.z) |
+              ((k.w ^ key.w) & mask.w)) == 0;
+    };
+    if (ix.x == kEmpty) return kNone;
+    if (ix.x != kTomb && holds(k0)) {
+      *raw = k0;
+      return ix.x;
+    }
+    if (ix.y == kEmpty) return kNone;
+    if (ix.y != kTomb && holds(k1)) {
+      *raw = k1;
+      return ix.y;
+    }
+    if (ix.z == kEmpty) return kNone;
+    if (ix.z != kTomb && holds(k2)) {
+      *raw = k2;
+      return ix.z;
+    }
+    b = (b + 1) & t.bmask;
+  }
+  return kNone;
+}
+
 // Key words of an allocated index's entry.
 // Claim the first empty-or-erased entry on key hash h's probe path (the
 // map_put position; the key is known to be absent) and store key + index.

@@ -15,7 +15,7 @@ import numpy as np
 from . import (BridgeConfigC, DevBatchC, FwConfigC, LbConfigC, MAX_DEV, MbufBatchC,
                NatConfigC, PolConfigC, RX_MERGE_MAX, RxQueueC, RxStreamC, ServeExpiryStatsC, ServeStatsC, StateMarkC, TableStatsC,
                TX_MERGE_MAX, TxFramesC, TxListsC, TxMergedC, TxNextC, TxReturnStatsC, TxSourceC,
-               TxStatsC, TxWayHomeC, _check, lib)
+               TxStatsC, TxWayHomeC, VpLookupOutC, _check, lib)
 
 
 def _dptr(t):
@@ -47,6 +47,7 @@ def _rx_stream(data, lens, pos, sel, now, now0, now_step, n):
 
 class NfBase:
     kind = "?"
+    gpu = 0
 
     def __init__(self, libpath=None):
         self.h = C.c_void_p()
@@ -558,6 +559,77 @@ class NfBase:
         self._ck(self.L.vp_state_delta_apply(self.h, C.c_void_p(buf.ctypes.data), size),
                  "vp_state_delta_apply")
 
+    def value_size(self, table: int = 0) -> int:
+        """vp_table_value_size: bytes per entry of `table`'s values (0 the
+        NF's flow table, 1 viglb's backends), as in the state image."""
+        n = C.c_uint32()
+        self._ck(self.L.vp_table_value_size(self.h, table, C.byref(n)), "vp_table_value_size")
+        return int(n.value)
+
+    def _table_query(self, call, what, n, src, index, ts, key, value, table, stream):
+        for t, width, count in ((index, 4, n), (ts, 8, n), (key, 1, 16 * n)):
+            if t is not None:
+                assert t.is_cuda and t.element_size() == width and t.numel() >= count
+        if value is not None:
+            assert value.is_cuda and value.numel() * value.element_size() >= n * self.value_size(table)
+        out = VpLookupOutC(index=_dptr(index), ts=_dptr(ts), key=_dptr(key), value=_dptr(value))
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        self._ck(call(self.h, table, n, _dptr(src) if n else None, C.byref(out), s), what)
+
+    def lookup_device(self, keys, index=None, ts=None, key=None, value=None, table: int = 0,
+                      stream=None):
+        """vp_table_lookup: for each 16-byte key of `keys` (uint8 CUDA tensor
+        of n * 16 bytes, zero-padded as the state image's keys) the live entry
+        that holds it -- its index (LOOKUP_MISS: none) into `index` (32-bit
+        CUDA tensor of n), its stamp into `ts` (64-bit), its key into `key`
+        (uint8, n * 16) and its value into `value` (n * value_size(table)
+        bytes); a miss writes zeros. Any output may be None. Read-only: no
+        entry is rejuvenated. Stops the resident kernel, runs on `stream` (the
+        context's own for None) and returns with the results written."""
+        assert keys.is_cuda and keys.element_size() == 1 and keys.numel() % 16 == 0
+        self._table_query(self.L.vp_table_lookup, "vp_table_lookup", keys.numel() // 16, keys,
+                          index, ts, key, value, table, stream)
+
+    def entries_device(self, idx, index=None, ts=None, key=None, value=None, table: int = 0,
+                       stream=None):
+        """vp_table_entries: the same answers for each index of `idx` (32-bit
+        CUDA tensor of n); an index that is not allocated, or not below the
+        capacity, is a miss. vignat's index is the external port minus
+        start_port: the reverse NAT lookup."""
+        assert idx.is_cuda and idx.element_size() == 4
+        self._table_query(self.L.vp_table_entries, "vp_table_entries", idx.numel(), idx,
+                          index, ts, key, value, table, stream)
+
+    def _table_query_host(self, query, src, n, table):
+        import torch
+        d = src.device
+        vsz = self.value_size(table)
+        index = torch.empty(n, dtype=torch.int32, device=d)
+        ts = torch.empty(n, dtype=torch.int64, device=d)
+        key = torch.empty(n * 16, dtype=torch.uint8, device=d)
+        value = torch.empty(n * vsz, dtype=torch.uint8, device=d) if vsz else None
+        query(src, index, ts, key, value, table)
+        return {"index": index.cpu().numpy().view(np.uint32), "ts": ts.cpu().numpy(),
+                "key": key.cpu().numpy().reshape(n, 16),
+                "value": (value.cpu().numpy() if vsz else np.zeros(0, np.uint8)).reshape(n, vsz)}
+
+    def lookup(self, keys: np.ndarray, table: int = 0) -> dict:
+        """lookup_device of uint8[n, 16] keys in host memory: a dict of numpy
+        arrays index (uint32[n]), ts (int64[n]), key (uint8[n, 16]) and value
+        (uint8[n, value_size])."""
+        import torch
+        keys = np.ascontiguousarray(keys, np.uint8).reshape(-1, 16)
+        src = torch.from_numpy(keys.reshape(-1).copy()).to("cuda:%d" % self.gpu)
+        return self._table_query_host(self.lookup_device, src, keys.shape[0], table)
+
+    def entries(self, indices: np.ndarray, table: int = 0) -> dict:
+        """entries_device of uint32[n] indices in host memory; the dict lookup
+        returns."""
+        import torch
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        src = torch.from_numpy(idx.view(np.int32).copy()).to("cuda:%d" % self.gpu)
+        return self._table_query_host(self.entries_device, src, idx.shape[0], table)
+
     def live_count(self) -> int:
         v = self.L.vp_live_count(self.h)
         if v < 0:
@@ -711,6 +783,7 @@ class Nat(NfBase):
     def __init__(self, cfg: NatConfigC, gpu: int = 0, libpath=None):
         super().__init__(libpath)
         self.cfg = cfg
+        self.gpu = gpu
         self._ck(self.L.vp_nat_create(C.byref(cfg), gpu, C.byref(self.h)),
                "vp_nat_create")
 
@@ -731,6 +804,7 @@ class Bridge(NfBase):
     def __init__(self, cfg: BridgeConfigC, gpu: int = 0, libpath=None):
         super().__init__(libpath)
         self.cfg = cfg
+        self.gpu = gpu
         self._ck(self.L.vp_bridge_create(C.byref(cfg), gpu, C.byref(self.h)),
                "vp_bridge_create")
 
@@ -753,6 +827,7 @@ class Lb(NfBase):
     def __init__(self, cfg: LbConfigC, gpu: int = 0, libpath=None):
         super().__init__(libpath)
         self.cfg = cfg
+        self.gpu = gpu
         self._ck(self.L.vp_lb_create(C.byref(cfg), gpu, C.byref(self.h)),
                "vp_lb_create")
 
@@ -778,6 +853,7 @@ class Fw(NfBase):
     def __init__(self, cfg: FwConfigC, gpu: int = 0, libpath=None):
         super().__init__(libpath)
         self.cfg = cfg
+        self.gpu = gpu
         self._ck(self.L.vp_fw_create(C.byref(cfg), gpu, C.byref(self.h)),
                "vp_fw_create")
 
@@ -802,6 +878,7 @@ class Pol(NfBase):
     def __init__(self, cfg: PolConfigC, gpu: int = 0, libpath=None):
         super().__init__(libpath)
         self.cfg = cfg
+        self.gpu = gpu
         self._ck(self.L.vp_pol_create(C.byref(cfg), gpu, C.byref(self.h)),
                "vp_pol_create")
 
