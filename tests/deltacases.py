@@ -116,6 +116,14 @@ def mutations(state0, delta):
         bad = 0x10000 if kind != "lb" else delta["tables"][1]["capacity"]
         m["value_range"] = DR.pack(_edit(delta, 0, value=_set(t["value"], 0,
                                                               bad.to_bytes(4, "little"))))
+    # two faults in one delta: the lower code is reported, wherever it stands,
+    # and what sd_check finds before anything sd_check2 would
+    m["idx_and_freed_ts_negative"] = DR.pack(
+        _edit(delta, 0, freed=_set(freed, 0, idx[2]), ts=_set(ts, 0, -5)))
+    m["range_0_ts_negative_2"] = DR.pack(
+        _edit(delta, 0, idx=_set(idx, 0, cap), ts=_set(ts, 2, -5)))
+    m["ts_negative_0_range_2"] = DR.pack(
+        _edit(delta, 0, idx=_set(idx, 2, cap), ts=_set(ts, 0, -5)))
     for name, blob in m.items():
         assert blob != good, name
     return m
@@ -126,7 +134,11 @@ NAMES = ["magic", "version", "kind", "short_1", "short_section", "long", "reserv
          "capacity", "value_size", "n_new_header", "pad_byte", "sum", "not_normalised",
          "idx_range", "freed_range", "idx_twice", "freed_twice", "idx_and_freed", "idx_in_tail",
          "freed_in_tail", "kept_count", "ts_negative", "ts_after_last_now", "ts_decreasing",
-         "ts_below_kept", "last_now_below", "key_twice", "key_of_kept"]
+         "ts_below_kept", "last_now_below", "key_twice", "key_of_kept",
+         "idx_and_freed_ts_negative", "range_0_ts_negative_2", "ts_negative_0_range_2"]
+# the faults the host finds in the headers and sizes alone, before any upload
+HEADER_LEVEL = ["magic", "version", "kind", "short_1", "short_section", "long", "reserved_word",
+                "capacity", "value_size", "n_new_header", "pad_byte", "sum", "one_table"]
 NOT_NAT = ["key_pad"]
 VALUED = ["value_range"]
 LB_ONLY = ["one_table"]

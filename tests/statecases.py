@@ -10,9 +10,15 @@ the stack and never-used ones left ("part"), or with the table full ("full").
 Act 2 opens with traffic over a larger population: the entries last touched
 in act 1 expire, new flows take the freed indices and then the never-used.
 """
+import functools
+import json
+import os
+
 import numpy as np
 
+import deltacases
 import orc
+import stateref as SR
 from tracegen import (mixed_bridge_trace, mixed_fw_trace, mixed_lb_trace, mixed_nat_trace,
                       mixed_pol_trace)
 from vigor_amd import traces as T
@@ -183,3 +189,112 @@ def census(kind, variant):
                        expired_in_act1=int(freed_once.sum()))
     res.update(expired=expired, born=born, out=out, frames=frames)
     return res
+
+
+# ------------------------------------------------------ rejected images --
+
+def _edit(state, table, **fields):
+    s = {"kind": state["kind"], "last_now": state["last_now"],
+         "tables": [dict(t) for t in state["tables"]]}
+    s["tables"][table].update(fields)
+    return s
+
+
+def _set(lst, j, v):
+    out = list(lst)
+    out[j] = v
+    return out
+
+
+def mutations(kind, img):
+    """{name: bytes}: one fault each in an image of vignat or viglb whose first
+    table has four live entries and two freed indices or more."""
+    s = SR.unpack(img)
+    t0 = s["tables"][0]
+    cap, n, nf = t0["capacity"], len(t0["lru"]), len(t0["freed"])
+    assert n >= 4 and nf >= 2
+    m = {}
+    m["magic"] = SR.pack(s, magic=SR.MAGIC ^ 1)
+    m["version"] = SR.pack(s, version=2)
+    m["kind"] = SR.pack(dict(s, kind="fw" if kind == "nat" else "nat"))
+    m["capacity"] = SR.pack(_edit(s, 0, capacity=cap * 2, fresh_next=t0["fresh_next"] + cap))
+    m["short_1"] = img[:-1]
+    m["short_section"] = img[:len(img) - 16 * n]
+    m["long"] = img + bytes(16)
+    m["index_eq_capacity"] = SR.pack(_edit(s, 0, lru=[cap] + t0["lru"][1:]), canon=False)
+    m["lru_and_freed"] = SR.pack(_edit(s, 0, freed=[t0["lru"][2]] + t0["freed"][1:]), canon=False)
+    m["free_missing"] = SR.pack(_edit(s, 0, freed=t0["freed"][1:]), canon=False)
+    m["n_live_gt_capacity"] = SR.pack(_edit(s, 0, n_live=cap + 1), canon=False)
+    ts = list(t0["ts"])
+    ts[1], ts[-1] = ts[-1] + 1, ts[1]
+    m["ts_decreasing"] = SR.pack(_edit(s, 0, ts=ts), canon=False)
+    m["ts_after_last_now"] = SR.pack(
+        _edit(s, 0, ts=t0["ts"][:-1] + [s["last_now"] + 1]), canon=False)
+    m["ts_negative"] = SR.pack(_edit(s, 0, ts=[-5] + t0["ts"][1:]), canon=False)
+    m["key_twice"] = SR.pack(_edit(s, 0, key=[t0["key"][3]] + t0["key"][1:]), canon=False)
+    m["not_normalised"] = SR.pack(
+        _edit(s, 0, freed=t0["freed"] + [t0["fresh_next"]], fresh_next=t0["fresh_next"] + 1),
+        canon=False)
+    if 4 * n % 16:
+        at = 32 + 32 + 4 * n
+    else:  # (lru[] ends on a 16-byte boundary: no pad there)
+        assert 4 * nf % 16, "no pad byte in the first table's index arrays"
+        at = 32 + 32 + 4 * n + 4 * nf
+    m["pad_byte"] = img[:at] + b"\x01" + img[at + 1:]
+    # two faults in one image: the lower code is reported, wherever it stands
+    m["range_0_ts_negative_2"] = SR.pack(
+        _edit(s, 0, lru=_set(t0["lru"], 0, cap), ts=_set(t0["ts"], 2, -5)), canon=False)
+    m["ts_negative_0_range_2"] = SR.pack(
+        _edit(s, 0, lru=_set(t0["lru"], 2, cap), ts=_set(t0["ts"], 0, -5)), canon=False)
+    if kind == "lb":
+        t1 = s["tables"][1]
+        bcap = t1["capacity"]
+        m["backend_id_eq_capacity"] = SR.pack(
+            _edit(s, 0, value=[bcap.to_bytes(4, "little")] + t0["value"][1:]), canon=False)
+        m["backends_capacity"] = SR.pack(
+            _edit(s, 1, capacity=bcap * 2, fresh_next=t1["fresh_next"] + bcap))
+        m["backends_index"] = SR.pack(_edit(s, 1, lru=[bcap] + t1["lru"][1:]), canon=False)
+        m["one_table"] = SR.pack(dict(s, tables=s["tables"][:1]))
+    for name, blob in m.items():
+        assert blob != img, name
+    return m
+
+
+MUTATIONS = ["magic", "version", "kind", "capacity", "short_1", "short_section", "long",
+             "index_eq_capacity", "lru_and_freed", "free_missing", "n_live_gt_capacity",
+             "ts_decreasing", "ts_after_last_now", "ts_negative", "key_twice", "not_normalised",
+             "pad_byte"]
+DOUBLE = ["range_0_ts_negative_2", "ts_negative_0_range_2"]
+LB_ONLY = ["backend_id_eq_capacity", "backends_capacity", "backends_index", "one_table"]
+# the faults the host finds in the headers and sizes alone, before any upload
+HEADER_LEVEL = ["magic", "version", "kind", "capacity", "short_1", "short_section", "long",
+                "n_live_gt_capacity", "pad_byte", "one_table", "backends_capacity"]
+
+
+def names_for(kind):
+    return MUTATIONS + DOUBLE + (LB_ONLY if kind == "lb" else [])
+
+
+def small_state(kind):
+    """The smallest case: deltacases.victim's state 0 (eight entries, two freed
+    indices; viglb: two backends beside them) as a state of vignat or viglb
+    over tables of CAP and LB_BCAP indices, packed on the CPU."""
+    s = deltacases.victim("lb", cap=CAP, bcap=LB_BCAP)[0]
+    if kind == "lb":
+        return s
+    assert kind == "nat"
+    t = dict(s["tables"][0], value_size=0, value=[b""] * len(s["tables"][0]["lru"]))
+    return {"kind": "nat", "last_now": s["last_now"], "tables": [t]}
+
+
+@functools.lru_cache(None)
+def recorded():
+    """tests/golden/state_messages.json, as tests/golden/make_state_messages.py
+    recorded it: {"image" | "image_small" | "delta": {kind: {name: [return
+    code, vp_last_error()]}}} of every refused image and delta of the suites.
+    "image": mutations() of the image a context saved after act 1 of the
+    "part" trace; "image_small": the HEADER_LEVEL ones of small_state()'s;
+    "delta": deltacases.mutations() of deltacases.victim's delta."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                           "state_messages.json")) as f:
+        return json.load(f)

@@ -304,18 +304,21 @@ def victims():
     return get
 
 
-def _refused(nf, blob, img, want=EINVAL):
+def _refused(nf, blob, img, want=EINVAL, recorded=None):
     buf = np.frombuffer(blob, np.uint8)
     rc = nf.L.vp_state_delta_apply(nf.h, C.c_void_p(buf.ctypes.data), buf.size)
     assert rc == want, rc
     assert nf.L.vp_last_error().decode().startswith("state delta apply:"), nf.L.vp_last_error()
+    if recorded:
+        assert [rc, nf.L.vp_last_error().decode()] == recorded
     assert nf.save_state() == img
 
 
 @pytest.mark.parametrize("kind,name", [(k, n) for k in ("fw", "lb") for n in DC.names_for(k)])
 def test_refused_delta(victims, kind, name):
     nf, s0, s1, good = victims(kind)
-    _refused(nf, DC.mutations(s0, good)[name], SR.pack(s0))
+    _refused(nf, DC.mutations(s0, good)[name], SR.pack(s0),
+             recorded=SC.recorded()["delta"][kind][name])
 
 
 @pytest.mark.parametrize("kind", ["fw", "lb"])

@@ -259,55 +259,6 @@ def test_kernel_shape_edges(cap, n_live, stacked):
 
 # ------------------------------------------------------ 6 rejected images --
 
-def _edit(state, table, **fields):
-    s = {"kind": state["kind"], "last_now": state["last_now"],
-         "tables": [dict(t) for t in state["tables"]]}
-    s["tables"][table].update(fields)
-    return s
-
-
-def _mutations(kind, img):
-    s = SR.unpack(img)
-    t0 = s["tables"][0]
-    cap, n, nf = t0["capacity"], len(t0["lru"]), len(t0["freed"])
-    assert n >= 4 and nf >= 2
-    m = {}
-    m["magic"] = SR.pack(s, magic=SR.MAGIC ^ 1)
-    m["version"] = SR.pack(s, version=2)
-    m["kind"] = SR.pack(dict(s, kind="fw" if kind == "nat" else "nat"))
-    m["capacity"] = SR.pack(_edit(s, 0, capacity=cap * 2, fresh_next=t0["fresh_next"] + cap))
-    m["short_1"] = img[:-1]
-    m["short_section"] = img[:len(img) - 16 * n]
-    m["long"] = img + bytes(16)
-    m["index_eq_capacity"] = SR.pack(_edit(s, 0, lru=[cap] + t0["lru"][1:]), canon=False)
-    m["lru_and_freed"] = SR.pack(_edit(s, 0, freed=[t0["lru"][2]] + t0["freed"][1:]), canon=False)
-    m["free_missing"] = SR.pack(_edit(s, 0, freed=t0["freed"][1:]), canon=False)
-    m["n_live_gt_capacity"] = SR.pack(_edit(s, 0, n_live=cap + 1), canon=False)
-    ts = list(t0["ts"])
-    ts[1], ts[-1] = ts[-1] + 1, ts[1]
-    m["ts_decreasing"] = SR.pack(_edit(s, 0, ts=ts), canon=False)
-    m["ts_after_last_now"] = SR.pack(
-        _edit(s, 0, ts=t0["ts"][:-1] + [s["last_now"] + 1]), canon=False)
-    m["ts_negative"] = SR.pack(_edit(s, 0, ts=[-5] + t0["ts"][1:]), canon=False)
-    m["key_twice"] = SR.pack(_edit(s, 0, key=[t0["key"][3]] + t0["key"][1:]), canon=False)
-    m["not_normalised"] = SR.pack(
-        _edit(s, 0, freed=t0["freed"] + [t0["fresh_next"]], fresh_next=t0["fresh_next"] + 1),
-        canon=False)
-    if 4 * n % 16:
-        at = 32 + 32 + 4 * n
-        m["pad_byte"] = img[:at] + b"\x01" + img[at + 1:]
-    if kind == "lb":
-        t1 = s["tables"][1]
-        bcap = t1["capacity"]
-        m["backend_id_eq_capacity"] = SR.pack(
-            _edit(s, 0, value=[bcap.to_bytes(4, "little")] + t0["value"][1:]), canon=False)
-        m["backends_capacity"] = SR.pack(
-            _edit(s, 1, capacity=bcap * 2, fresh_next=t1["fresh_next"] + bcap))
-        m["backends_index"] = SR.pack(_edit(s, 1, lru=[bcap] + t1["lru"][1:]), canon=False)
-        m["one_table"] = SR.pack(dict(s, tables=s["tables"][:1]))
-    return m
-
-
 @pytest.fixture(scope="module")
 def victims():
     """Per kind: a context in the state after act 1, its image, and its
@@ -324,33 +275,16 @@ def victims():
     return get
 
 
-MUTATIONS = ["magic", "version", "kind", "capacity", "short_1", "short_section", "long",
-             "index_eq_capacity", "lru_and_freed", "free_missing", "n_live_gt_capacity",
-             "ts_decreasing", "ts_after_last_now", "ts_negative", "key_twice", "not_normalised",
-             "pad_byte"]
-LB_ONLY = ["backend_id_eq_capacity", "backends_capacity", "backends_index", "one_table"]
-
-
-@pytest.mark.parametrize("kind,name", [("nat", m) for m in MUTATIONS] +
-                         [("lb", m) for m in MUTATIONS + LB_ONLY])
+@pytest.mark.parametrize("kind,name", [(k, m) for k in ("nat", "lb") for m in SC.names_for(k)])
 def test_rejected_image(victims, kind, name):
     nf, o, img, tr, cut = victims(kind)
-    muts = _mutations(kind, img)
-    if name not in muts:
-        assert name == "pad_byte"  # (lru[] ends on a 16-byte boundary: no pad there)
-        name, muts = "pad_byte_ts", {"pad_byte_ts": None}
-        s = SR.unpack(img)["tables"][0]
-        n, nf_ = len(s["lru"]), len(s["freed"])
-        at = 32 + 32 + 4 * n + (-4 * n % 16) + 4 * nf_
-        assert 4 * nf_ % 16, "no pad byte in the first table's index arrays"
-        muts[name] = img[:at] + b"\x01" + img[at + 1:]
-    bad = muts[name]
-    assert bad != img
+    bad = SC.mutations(kind, img)[name]
     buf = np.frombuffer(bad, np.uint8)
     L = nf.L
     rc = L.vp_state_load(nf.h, C.c_void_p(buf.ctypes.data), buf.size)
     assert rc == EINVAL, (name, rc)
     assert L.vp_last_error().decode().startswith("state load:"), L.vp_last_error()
+    assert [rc, L.vp_last_error().decode()] == SC.recorded()["image"][kind][name]
     assert nf.save_state() == img
 
 

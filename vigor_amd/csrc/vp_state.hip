@@ -29,10 +29,6 @@ using namespace stimg;
 
 namespace {
 
-constexpr uint32_t kStMagic = VP_STATE_MAGIC;
-constexpr uint32_t kStVersion = VP_STATE_VERSION;
-constexpr uint32_t kStHdr = 32;
-
 // ---------------------------------------------------------------- save --
 
 // freed[] of the image: the stack from its top down to the first index that
@@ -84,54 +80,17 @@ __global__ __launch_bounds__(256) void st_gather(TableDev t, uint32_t tt, SideVa
 
 // ---------------------------------------------------------------- load --
 
-// What st_check / st_dup report: code << 32 | position, the least one wins.
-enum StErr : uint32_t {
-  E_LRU_RANGE = 1, E_FREED_RANGE, E_LRU_TAIL, E_FREED_TAIL, E_LRU_TWICE, E_FREED_TWICE,
-  E_FREED_NORM, E_TS_NEG, E_TS_FUTURE, E_TS_ORDER, E_KEY_PAD, E_VAL_RANGE, E_KEY_TWICE
-};
-__device__ __forceinline__ void st_fail(unsigned long long *err, uint32_t code, uint32_t j) {
-  atomicMin(err, ((unsigned long long)code << 32) | j);
-}
-
 // Reads the image only. bitmap: one bit per index, zero on entry; vmax: the
-// first value out of range (0: any).
+// first value out of range (0: any). A key is looked at by st_dup.
+struct StCheck {
+  uint32_t *bm_idx, *bm_freed;
+  __device__ __forceinline__ void key(uint32_t, uint4, unsigned long long *) const {}
+};
 __global__ __launch_bounds__(256) void st_check(ImgDev im, uint32_t tt, uint32_t cap,
                                                 int64_t last_now, uint32_t vmax,
                                                 uint32_t *bitmap, unsigned long long *err) {
-  const uint4 mask = key_mask(tt);
-  const uint32_t n = max(im.n_live, im.n_freed);
-  for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
-    if (j < im.n_live) {
-      const uint32_t i = im.lru[j];
-      if (i >= cap) {
-        st_fail(err, E_LRU_RANGE, j);
-      } else {
-        if (i >= im.fresh) st_fail(err, E_LRU_TAIL, j);
-        if (atomicOr(&bitmap[i >> 5], 1u << (i & 31)) & (1u << (i & 31)))
-          st_fail(err, E_LRU_TWICE, j);
-      }
-      const int64_t ts = im.ts[j];
-      if (ts < 0) st_fail(err, E_TS_NEG, j);
-      if (ts > last_now) st_fail(err, E_TS_FUTURE, j);
-      if (j > 0 && im.ts[j - 1] > ts) st_fail(err, E_TS_ORDER, j);
-      const uint4 k = im.key[j];
-      if (any4(make_uint4(k.x & ~mask.x, k.y & ~mask.y, k.z & ~mask.z, k.w & ~mask.w)))
-        st_fail(err, E_KEY_PAD, j);
-      if (vmax && reinterpret_cast<const uint32_t *>(im.val)[j] >= vmax)
-        st_fail(err, E_VAL_RANGE, j);
-    }
-    if (j < im.n_freed) {
-      const uint32_t i = im.freed[j];
-      if (i >= cap) {
-        st_fail(err, E_FREED_RANGE, j);
-      } else {
-        if (i >= im.fresh) st_fail(err, E_FREED_TAIL, j);
-        if (atomicOr(&bitmap[i >> 5], 1u << (i & 31)) & (1u << (i & 31)))
-          st_fail(err, E_FREED_TWICE, j);
-      }
-      if (j == im.n_freed - 1 && i + 1 == im.fresh) st_fail(err, E_FREED_NORM, j);
-    }
-  }
+  img_check(im, tt, cap, last_now, vmax, err, StCheck{bitmap, bitmap},
+            blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
 // The bucket array built aside (`t`: new buckets, slot_of, hash_of and
@@ -180,7 +139,7 @@ __global__ __launch_bounds__(256) void st_dup(TableDev t, uint32_t tt, ImgDev im
       if (end) break;
       b = (b + 1) & t.bmask;
     }
-    if (found != i) st_fail(err, E_KEY_TWICE, j);
+    if (found != i) img_fail(err, E_KEY_TWICE, j);
   }
 }
 
@@ -196,14 +155,7 @@ __global__ __launch_bounds__(256) void st_commit(TableDev t, uint32_t tt, SideVa
       t.ts[i] = (uint64_t)im.ts[j];
       t.tseq[i] = j;
       t.birth[i] = 0;
-      if (tt == TT_LBBACK) {
-        const uint2 v = reinterpret_cast<const uint2 *>(im.val)[j];
-        sv.be_rec[i] = make_uint4(im.key[j].x, v.x, v.y, 0u);
-      } else if (tt == TT_POL) {
-        const uint4 v = reinterpret_cast<const uint4 *>(im.val)[j];
-        sv.pol_size[i] = (uint64_t)v.x | ((uint64_t)v.y << 32);
-        sv.pol_time[i] = (int64_t)((uint64_t)v.z | ((uint64_t)v.w << 32));
-      }
+      side_put(tt, sv, i, im, j);
     }
     if (j < im.n_freed) t.stack[im.n_freed - 1u - j] = im.freed[j];
   }
@@ -240,6 +192,35 @@ int st_enter(vp_ctx *c, StTable tabs[2], int *ntabs) {
   return *ntabs ? 0 : VP_EINVAL;
 }
 
+int st_replaced(vp_ctx *c, StTable tabs[2], int nt, const uint64_t floor[2], int64_t last_now) {
+  for (int k = 0; k < nt; k++) {
+    FlowTable &t = *tabs[k].t;
+    t.ts_floor = floor[k];
+    t.fs_hint = 0;
+    t.runs_seen = true;
+    t.last_run_tiles = 0;
+    t.ctl_clean = false;
+    t.jr_on = false;
+  }
+  c->jr_want = false;
+  c->last_now = last_now;
+  c->fold_pending = false;
+  for (int k = 0; k < nt; k++) VP_TRY(tbl_layout_check(c, *tabs[k].t));
+  return 0;
+}
+
+int st_size_bound(vp_ctx *c, StTable tabs[2], int nt, uint32_t hdr, uint64_t *bytes) {
+  uint64_t at = hdr;
+  for (int k = 0; k < nt; k++) {
+    FlowTable &t = *tabs[k].t;
+    VP_TRY(read_ctl(c, t));
+    const uint32_t n = t.h_ctl.n_live;
+    at = section_at(at, t.cap, n, 0, tabs[k].tt, t.h_ctl.stack_top, n).end;
+  }
+  *bytes = at;
+  return 0;
+}
+
 int st_launch_freed(vp_ctx *c, FlowTable &t, uint32_t *freed, uint32_t *res) {
   st_freed<<<grid_for(t.cap), 256, 0, c->stream>>>(tbl_dev(t), freed, res);
   VP_HIP(hipGetLastError());
@@ -260,19 +241,8 @@ int state_save(vp_ctx *c, uint8_t *buf, uint64_t cap, uint64_t *bytes, bool size
   StTable tabs[2];
   int nt = 0;
   VP_TRY(st_enter(c, tabs, &nt));
+  if (size_only) return st_size_bound(c, tabs, nt, kImage.hdr, bytes);
   Section sec[2];
-  if (size_only) {  // an upper bound: every stacked index counted as freed
-    uint64_t at = kStHdr;
-    for (int k = 0; k < nt; k++) {
-      FlowTable &t = *tabs[k].t;
-      VP_TRY(read_ctl(c, t));
-      sec[k] = Section{t.cap, t.h_ctl.n_live, 0, kValSize[tabs[k].tt], t.h_ctl.stack_top};
-      section_layout(sec[k], at);
-      at = sec[k].end;
-    }
-    *bytes = at;
-    return 0;
-  }
   // live indices and the free list of every table, one read-back each
   DevBuf res;
   VP_TRY(dalloc((uint32_t **)&res.p, 4));
@@ -283,7 +253,7 @@ int state_save(vp_ctx *c, uint8_t *buf, uint64_t cap, uint64_t *bytes, bool size
     VP_TRY(st_launch_freed(c, t, t.eidx2, (uint32_t *)res.p + 2 * k));
   }
   VP_HIP(hipMemcpyAsync(h_res, res.p, sizeof h_res, hipMemcpyDeviceToHost, c->stream));
-  uint64_t at = kStHdr;
+  uint64_t at = kImage.hdr;
   for (int k = 0; k < nt; k++) {
     FlowTable &t = *tabs[k].t;
     VP_TRY(read_ctl(c, t));
@@ -293,8 +263,7 @@ int state_save(vp_ctx *c, uint8_t *buf, uint64_t cap, uint64_t *bytes, bool size
         (uint64_t)h.n_live + h_res[2 * k] + (t.cap - h_res[2 * k + 1]) != t.cap)
       return state_fail("state save: table %d holds %u live of %u counted, %u freed, tail from %u "
                         "of %u", k, h.exp_count, h.n_live, h_res[2 * k], h_res[2 * k + 1], t.cap);
-    sec[k] = Section{t.cap, h.n_live, h_res[2 * k + 1], kValSize[tabs[k].tt], h_res[2 * k]};
-    section_layout(sec[k], at);
+    sec[k] = section_at(at, t.cap, h.n_live, h_res[2 * k + 1], tabs[k].tt, h_res[2 * k], h.n_live);
     at = sec[k].end;
   }
   const uint64_t total = at;
@@ -314,59 +283,14 @@ int state_save(vp_ctx *c, uint8_t *buf, uint64_t cap, uint64_t *bytes, bool size
     const uint64_t *seq = nullptr;
     const uint32_t *idx = nullptr;
     VP_TRY(tbl_live_sort(c, t, s.n_live, &seq, &idx));
-    const uint64_t ends[5] = {s.lru + 4ull * s.n_live, s.freed + 4ull * s.n_freed,
-                              s.ts + 8ull * s.n_live, s.val, s.val + (uint64_t)s.vsz * s.n_live};
-    Pads pads{};
-    for (int a = 0; a < 5; a++) {
-      pads.at[a] = d + ends[a];
-      pads.n[a] = (uint32_t)(pad16(ends[a]) - ends[a]);
-    }
-    VP_TRY(st_launch_gather(c, t, tabs[k].tt, idx, section_dev(s, d), pads));
+    VP_TRY(st_launch_gather(c, t, tabs[k].tt, idx, section_dev(s, d), section_pads(s, d)));
   }
   VP_HIP(hipMemcpyAsync(buf, d, total, hipMemcpyDeviceToHost, c->stream));
   VP_HIP(hipStreamSynchronize(c->stream));
   // the headers
-  memset(buf, 0, kStHdr);
-  put32(buf, kStMagic);
-  put32(buf + 4, kStVersion);
-  put32(buf + 8, (uint32_t)c->kind);
-  put32(buf + 12, (uint32_t)nt);
-  put64(buf + 16, total);
-  put64(buf + 24, (uint64_t)c->last_now);
-  for (int k = 0; k < nt; k++) {
-    uint8_t *h = buf + sec[k].lru - kStTblHdr;
-    memset(h, 0, kStTblHdr);
-    put32(h, sec[k].cap);
-    put32(h + 4, sec[k].n_live);
-    put32(h + 8, sec[k].fresh);
-    put32(h + 12, sec[k].vsz);
-    put32(h + 16, sec[k].n_freed);
-  }
+  put_header(kImage, buf, c->kind, nt, total, c->last_now);
+  for (int k = 0; k < nt; k++) put_table_header(kImage, buf, sec[k]);
   return 0;
-}
-
-const char *err_text(uint32_t code) {
-  switch (code) {
-    case E_LRU_RANGE: return "lru[%u] is not below the capacity";
-    case E_FREED_RANGE: return "freed[%u] is not below the capacity";
-    case E_LRU_TAIL: return "lru[%u] lies in the never-used tail";
-    case E_FREED_TAIL: return "freed[%u] lies in the never-used tail";
-    case E_LRU_TWICE: return "lru[%u] names an index that is named twice";
-    case E_FREED_TWICE: return "freed[%u] names an index that is named twice";
-    case E_FREED_NORM: return "freed[%u] is fresh_next - 1: the tail is not normalised";
-    case E_TS_NEG: return "ts[%u] is negative";
-    case E_TS_FUTURE: return "ts[%u] is later than last_now";
-    case E_TS_ORDER: return "ts[%u] is earlier than the entry before it";
-    case E_KEY_PAD: return "key[%u] has a non-zero pad byte";
-    case E_VAL_RANGE: return "value[%u] is out of range";
-    case E_KEY_TWICE: return "key[%u] occurs twice";
-    default: return "entry %u";
-  }
-}
-int image_fail(int k, uint32_t tt, unsigned long long e) {
-  char what[96];
-  snprintf(what, sizeof what, err_text((uint32_t)(e >> 32)), (uint32_t)e);
-  return ST_BAD("state load: table %d (%s): %s", k, kTblName[tt], what);
 }
 
 // The arrays of a table built aside, freed unless they were swapped in.
@@ -388,47 +312,12 @@ int state_load(vp_ctx *c, const uint8_t *buf, uint64_t bytes) {
   int nt = 0;
   VP_TRY(st_enter(c, tabs, &nt));
   // ---- the host's checks: nothing is uploaded before they pass
-  if (bytes < kStHdr) return ST_BAD("state load: %llu bytes hold no header", (unsigned long long)bytes);
-  if (get32(buf) != kStMagic) return ST_BAD("state load: magic 0x%08x", get32(buf));
-  if (get32(buf + 4) != kStVersion) return ST_BAD("state load: version %u", get32(buf + 4));
-  if (get32(buf + 8) != (uint32_t)c->kind)
-    return ST_BAD("state load: kind %u into a context of kind %d", get32(buf + 8), c->kind);
-  if (get32(buf + 12) != (uint32_t)nt)
-    return ST_BAD("state load: n_tables %u, this NF has %d", get32(buf + 12), nt);
-  if (get64(buf + 16) != bytes)
-    return ST_BAD("state load: total_bytes %llu, %llu given", (unsigned long long)get64(buf + 16),
-                  (unsigned long long)bytes);
-  const int64_t last_now = (int64_t)get64(buf + 24);
-  if (last_now < -1) return ST_BAD("state load: last_now %lld", (long long)last_now);
+  const Expect want = st_expect(c, tabs, nt);
+  char msg[256];
+  int64_t last_now;
+  if (!read_header(kImage, want, buf, bytes, &last_now, msg, sizeof msg)) return ST_BAD("%s", msg);
   Section sec[2];
-  uint64_t at = kStHdr;
-  for (int k = 0; k < nt; k++) {
-    const FlowTable &t = *tabs[k].t;
-    if (bytes - at < kStTblHdr) return ST_BAD("state load: table %d: header past the end", k);
-    const uint8_t *h = buf + at;
-    Section &s = sec[k];
-    s = Section{get32(h), get32(h + 4), get32(h + 8), get32(h + 12), get32(h + 16)};
-    if (s.cap != t.cap) return ST_BAD("state load: table %d: capacity %u, the context's is %u", k, s.cap, t.cap);
-    if (s.n_live > s.cap) return ST_BAD("state load: table %d: n_live %u above the capacity", k, s.n_live);
-    if (s.fresh > s.cap) return ST_BAD("state load: table %d: fresh_next %u above the capacity", k, s.fresh);
-    if (s.vsz != kValSize[tabs[k].tt]) return ST_BAD("state load: table %d: value size %u", k, s.vsz);
-    if (s.n_freed > s.cap || (uint64_t)s.n_live + s.n_freed + (s.cap - s.fresh) != s.cap)
-      return ST_BAD("state load: table %d: n_live %u + n_freed %u + tail %u is not the capacity %u",
-                    k, s.n_live, s.n_freed, s.cap - s.fresh, s.cap);
-    if (get32(h + 20) | get32(h + 24) | get32(h + 28))
-      return ST_BAD("state load: table %d: reserved header word not zero", k);
-    section_layout(s, at);
-    if (s.end > bytes) return ST_BAD("state load: table %d: arrays end at %llu of %llu bytes", k,
-                                     (unsigned long long)s.end, (unsigned long long)bytes);
-    const uint64_t ends[5] = {s.lru + 4ull * s.n_live, s.freed + 4ull * s.n_freed,
-                              s.ts + 8ull * s.n_live, s.val, s.val + (uint64_t)s.vsz * s.n_live};
-    for (uint64_t e : ends)
-      for (uint64_t b = e; b < pad16(e); b++)
-        if (buf[b]) return ST_BAD("state load: table %d: pad byte at %llu not zero", k, (unsigned long long)b);
-    at = s.end;
-  }
-  if (at != bytes) return ST_BAD("state load: %llu bytes behind the last table",
-                                 (unsigned long long)(bytes - at));
+  if (!read_sections(kImage, want, buf, bytes, sec, msg, sizeof msg)) return ST_BAD("%s", msg);
   // ---- upload, then the device's checks of the image's contents
   DevBuf img, scratch;
   VP_TRY(dalloc((uint8_t **)&img.p, bytes));
@@ -455,7 +344,7 @@ int state_load(vp_ctx *c, const uint8_t *buf, uint64_t bytes) {
   VP_HIP(hipMemcpyAsync(h_err, err, 16, hipMemcpyDeviceToHost, c->stream));
   VP_HIP(hipStreamSynchronize(c->stream));
   for (int k = 0; k < nt; k++)
-    if (h_err[k] != ~0ull) return image_fail(k, tabs[k].tt, h_err[k]);
+    if (h_err[k] != ~0ull) return img_refuse(kImage.who, "lru", k, tabs[k].tt, h_err[k]);
   // ---- the bucket arrays aside, and every key looked up in them
   Aside as[2];
   TableDev nd[2];
@@ -487,7 +376,7 @@ int state_load(vp_ctx *c, const uint8_t *buf, uint64_t bytes) {
   VP_HIP(hipMemcpyAsync(h_err, err, 16, hipMemcpyDeviceToHost, c->stream));
   VP_HIP(hipStreamSynchronize(c->stream));
   for (int k = 0; k < nt; k++)
-    if (h_err[k] != ~0ull) return image_fail(k, tabs[k].tt, h_err[k]);
+    if (h_err[k] != ~0ull) return img_refuse(kImage.who, "lru", k, tabs[k].tt, h_err[k]);
   // ---- apply: from here on the context's state is the image's
   for (int k = 0; k < nt; k++) {
     const Section &s = sec[k];
@@ -497,6 +386,7 @@ int state_load(vp_ctx *c, const uint8_t *buf, uint64_t bytes) {
   }
   VP_HIP(hipStreamSynchronize(c->stream));
   uint32_t most = 0;
+  uint64_t floor[2];
   for (int k = 0; k < nt; k++) {
     FlowTable &t = *tabs[k].t;
     Aside &a = as[k];
@@ -510,22 +400,13 @@ int state_load(vp_ctx *c, const uint8_t *buf, uint64_t bytes) {
     t.layout_tries = 0;
     t.ins_since = sec[k].n_live;
     t.rebuilds++;
-    t.ts_floor = sec[k].n_live ? get64(buf + sec[k].ts) : UINT64_MAX;
-    t.fs_hint = 0;
-    t.runs_seen = true;
-    t.last_run_tiles = 0;
-    t.ctl_clean = false;
-    t.jr_on = false;
+    floor[k] = sec[k].n_live ? get64(buf + sec[k].ts) : UINT64_MAX;
     most = std::max(most, sec[k].n_live);
   }
-  c->jr_want = false;
-  c->last_now = last_now;
   c->seq = (uint64_t)most + 1;  // (past every tseq: the LRU ranks 0 .. n_live - 1)
-  c->fold_pending = false;
   c->st_epoch++;  // (the sequence restarted: marks taken before name nothing now)
   c->st_following = false;
-  for (int k = 0; k < nt; k++) VP_TRY(tbl_layout_check(c, *tabs[k].t));
-  return 0;
+  return st_replaced(c, tabs, nt, floor, last_now);
 }
 
 }  // namespace

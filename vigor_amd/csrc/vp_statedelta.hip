@@ -34,10 +34,6 @@ using namespace stimg;
 
 namespace {
 
-constexpr uint32_t kSdMagic = VP_STATE_DELTA_MAGIC;
-constexpr uint32_t kSdVersion = VP_STATE_DELTA_VERSION;
-constexpr uint32_t kSdHdr = 64;
-
 // ---------------------------------------------------------------- save --
 
 // Every live index whose last touch has a sequence number of base or later,
@@ -66,15 +62,6 @@ __global__ __launch_bounds__(256) void sd_collect(TableDev t, uint64_t base, uin
 
 // --------------------------------------------------------------- apply --
 
-// What the check kernels report: code << 32 | position, the least one wins.
-enum SdErr : uint32_t {
-  E_IDX_RANGE = 1, E_FREED_RANGE, E_IDX_TAIL, E_FREED_TAIL, E_IDX_TWICE, E_FREED_TWICE,
-  E_FREED_NORM, E_BOTH, E_TS_NEG, E_TS_FUTURE, E_TS_ORDER, E_KEY_PAD, E_VAL_RANGE, E_KEY_TWICE,
-  E_KEY_KEPT, E_NOT_KEPT
-};
-__device__ __forceinline__ void sd_fail(unsigned long long *err, uint32_t code, uint32_t j) {
-  atomicMin(err, ((unsigned long long)code << 32) | j);
-}
 __device__ __forceinline__ bool bit_of(const uint32_t *bm, uint32_t i) {
   return (bm[i >> 5] >> (i & 31)) & 1u;
 }
@@ -93,54 +80,30 @@ struct SdScratch {
   uint32_t *cnt;
 };
 
-// Reads the delta only (im: new[] as an image's arrays, n_live = n_new).
-__global__ __launch_bounds__(256) void sd_check(ImgDev im, uint32_t tt, uint32_t cap,
-                                                int64_t last_now, uint32_t vmax, SdScratch s) {
-  const uint4 mask = key_mask(tt);
-  const uint32_t n = max(im.n_live, im.n_freed);
-  for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
-    if (j < im.n_live) {
-      const uint32_t i = im.lru[j];
-      if (i >= cap) {
-        sd_fail(s.err, E_IDX_RANGE, j);
-      } else {
-        if (i >= im.fresh) sd_fail(s.err, E_IDX_TAIL, j);
-        if (atomicOr(&s.bm_new[i >> 5], 1u << (i & 31)) & (1u << (i & 31)))
-          sd_fail(s.err, E_IDX_TWICE, j);
+// Reads the delta only (im: new[] as an image's arrays, n_live = n_new). A
+// key goes into the set: an entry on its path with the same key is a twin.
+struct SdCheck {
+  uint32_t *bm_idx, *bm_freed;
+  const ImgDev &im;
+  uint32_t tt;
+  const SdScratch &s;
+  __device__ __forceinline__ void key(uint32_t j, uint4 k, unsigned long long *err) const {
+    uint32_t b = key_hash(tt, k) & s.hmask;
+    for (uint32_t step = 0; step <= s.hmask; step++) {
+      const uint32_t old = atomicCAS(&s.hset[b], kNone, j);
+      if (old == kNone) break;
+      if (eq4(im.key[old], k)) {
+        img_fail(err, E_KEY_TWICE, max(j, old));
+        break;
       }
-      const int64_t ts = im.ts[j];
-      if (ts < 0) sd_fail(s.err, E_TS_NEG, j);
-      if (ts > last_now) sd_fail(s.err, E_TS_FUTURE, j);
-      if (j > 0 && im.ts[j - 1] > ts) sd_fail(s.err, E_TS_ORDER, j);
-      const uint4 k = im.key[j];
-      if (any4(make_uint4(k.x & ~mask.x, k.y & ~mask.y, k.z & ~mask.z, k.w & ~mask.w)))
-        sd_fail(s.err, E_KEY_PAD, j);
-      if (vmax && reinterpret_cast<const uint32_t *>(im.val)[j] >= vmax)
-        sd_fail(s.err, E_VAL_RANGE, j);
-      // the key into the set: an entry on its path with the same key is a twin
-      uint32_t b = key_hash(tt, k) & s.hmask;
-      for (uint32_t step = 0; step <= s.hmask; step++) {
-        const uint32_t old = atomicCAS(&s.hset[b], kNone, j);
-        if (old == kNone) break;
-        if (eq4(im.key[old], k)) {
-          sd_fail(s.err, E_KEY_TWICE, max(j, old));
-          break;
-        }
-        b = (b + 1) & s.hmask;
-      }
-    }
-    if (j < im.n_freed) {
-      const uint32_t i = im.freed[j];
-      if (i >= cap) {
-        sd_fail(s.err, E_FREED_RANGE, j);
-      } else {
-        if (i >= im.fresh) sd_fail(s.err, E_FREED_TAIL, j);
-        if (atomicOr(&s.bm_free[i >> 5], 1u << (i & 31)) & (1u << (i & 31)))
-          sd_fail(s.err, E_FREED_TWICE, j);
-      }
-      if (j == im.n_freed - 1 && i + 1 == im.fresh) sd_fail(s.err, E_FREED_NORM, j);
+      b = (b + 1) & s.hmask;
     }
   }
+};
+__global__ __launch_bounds__(256) void sd_check(ImgDev im, uint32_t tt, uint32_t cap,
+                                                int64_t last_now, uint32_t vmax, SdScratch s) {
+  img_check(im, tt, cap, last_now, vmax, s.err, SdCheck{s.bm_new, s.bm_free, im, tt, s},
+            blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
 // map_get of a masked key in the table as it stands: the index that holds it,
@@ -174,10 +137,10 @@ __global__ __launch_bounds__(256) void sd_check2(ImgDev im, TableDev t, uint32_t
   for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x) {
     if (j < t.cap) {
       const bool f = bit_of(s.bm_free, j), w = bit_of(s.bm_new, j);
-      if (f && w) sd_fail(s.err, E_BOTH, j);
+      if (f && w) img_fail(s.err, E_BOTH, j);
       if (!f && !w && j < im.fresh) {
         if (t.slot_of[j] == kNone) {
-          sd_fail(s.err, E_NOT_KEPT, j);
+          img_fail(s.err, E_NOT_KEPT, j);
         } else {
           const unsigned long long ts = t.ts[j];
           hi = max(hi, ts + 1);
@@ -191,7 +154,7 @@ __global__ __launch_bounds__(256) void sd_check2(ImgDev im, TableDev t, uint32_t
       const uint32_t at = sd_find(t, mask, key_hash(tt, k), k);
       if (at != kNone && at != im.lru[j] && at < im.fresh && !bit_of(s.bm_free, at) &&
           !bit_of(s.bm_new, at))
-        sd_fail(s.err, E_KEY_KEPT, j);
+        img_fail(s.err, E_KEY_KEPT, j);
     }
   }
   for (uint32_t o = 32; o > 0; o >>= 1) {
@@ -259,14 +222,7 @@ __global__ __launch_bounds__(256) void sd_upsert(ImgDev im, TableDev t, uint32_t
       t.ts[i] = (uint64_t)im.ts[j];
       t.tseq[i] = seq + j;
       t.birth[i] = 0;
-      if (tt == TT_LBBACK) {
-        const uint2 v = reinterpret_cast<const uint2 *>(im.val)[j];
-        sv.be_rec[i] = make_uint4(im.key[j].x, v.x, v.y, 0u);
-      } else if (tt == TT_POL) {
-        const uint4 v = reinterpret_cast<const uint4 *>(im.val)[j];
-        sv.pol_size[i] = (uint64_t)v.x | ((uint64_t)v.y << 32);
-        sv.pol_time[i] = (int64_t)((uint64_t)v.z | ((uint64_t)v.w << 32));
-      }
+      side_put(tt, sv, i, im, j);
     }
     wave_append(&s.cnt[1], put);
     wave_append(&s.cnt[2], tomb);
@@ -293,12 +249,6 @@ __global__ __launch_bounds__(256) void sd_commit(ImgDev im, TableDev t, uint32_t
 
 // ---------------------------------------------------------------- host --
 
-// A delta's table section: the image's layout over new[], and n_live.
-struct DSection {
-  Section s;  // (s.n_live = n_new)
-  uint32_t n_live;
-};
-
 bool mark_eq(const vp_state_mark_t &a, const vp_state_mark_t &b) {
   return a.seq == b.seq && a.epoch == b.epoch;
 }
@@ -319,19 +269,8 @@ int delta_save(vp_ctx *c, const vp_state_mark_t *base, uint8_t *buf, uint64_t ca
   int nt = 0;
   VP_TRY(st_enter(c, tabs, &nt));
   VP_TRY(base_check(c, base, size_only ? "state delta size" : "state delta save"));
-  DSection sec[2];
-  if (size_only) {  // an upper bound: every live index new, every stacked one freed
-    uint64_t at = kSdHdr;
-    for (int k = 0; k < nt; k++) {
-      FlowTable &t = *tabs[k].t;
-      VP_TRY(read_ctl(c, t));
-      sec[k].s = Section{t.cap, t.h_ctl.n_live, 0, kValSize[tabs[k].tt], t.h_ctl.stack_top};
-      section_layout(sec[k].s, at);
-      at = sec[k].s.end;
-    }
-    *bytes = at;
-    return 0;
-  }
+  if (size_only) return st_size_bound(c, tabs, nt, kDelta.hdr, bytes);
+  Section sec[2];
   // the touched indices and the free list of every table, one read-back
   DevBuf res;
   VP_TRY(dalloc((uint32_t **)&res.p, 6));
@@ -345,7 +284,7 @@ int delta_save(vp_ctx *c, const vp_state_mark_t *base, uint8_t *buf, uint64_t ca
     VP_TRY(st_launch_freed(c, t, t.eidx2, d_res + 2 * k));
   }
   VP_HIP(hipMemcpyAsync(h_res, d_res, sizeof h_res, hipMemcpyDeviceToHost, c->stream));
-  uint64_t at = kSdHdr;
+  uint64_t at = kDelta.hdr;
   for (int k = 0; k < nt; k++) {
     FlowTable &t = *tabs[k].t;
     VP_TRY(read_ctl(c, t));  // (waits for the stream: h_res is there)
@@ -355,10 +294,8 @@ int delta_save(vp_ctx *c, const vp_state_mark_t *base, uint8_t *buf, uint64_t ca
         (uint64_t)h.n_live + n_freed + (t.cap - fresh) != t.cap)
       return state_fail("state delta save: table %d holds %u touched of %u live, %u freed, tail "
                         "from %u of %u", k, n_new, h.n_live, n_freed, fresh, t.cap);
-    sec[k].s = Section{t.cap, n_new, fresh, kValSize[tabs[k].tt], n_freed};
-    sec[k].n_live = h.n_live;
-    section_layout(sec[k].s, at);
-    at = sec[k].s.end;
+    sec[k] = section_at(at, t.cap, n_new, fresh, tabs[k].tt, n_freed, h.n_live);
+    at = sec[k].end;
   }
   const uint64_t total = at;
   *bytes = total;
@@ -370,7 +307,7 @@ int delta_save(vp_ctx *c, const vp_state_mark_t *base, uint8_t *buf, uint64_t ca
   uint8_t *d = (uint8_t *)img.p;
   for (int k = 0; k < nt; k++) {
     FlowTable &t = *tabs[k].t;
-    const Section &s = sec[k].s;
+    const Section &s = sec[k];
     // (the free list leaves the expiry workspace before the sort writes there)
     if (s.n_freed)
       VP_HIP(hipMemcpyAsync(d + s.freed, t.eidx2, 4ull * s.n_freed, hipMemcpyDeviceToDevice,
@@ -378,70 +315,19 @@ int delta_save(vp_ctx *c, const vp_state_mark_t *base, uint8_t *buf, uint64_t ca
     const uint64_t *seq = nullptr;
     const uint32_t *idx = nullptr;
     VP_TRY(tbl_live_sort(c, t, s.n_live, &seq, &idx));
-    uint64_t ends[5];
-    section_ends(s, ends);
-    Pads pads{};
-    for (int a = 0; a < 5; a++) {
-      pads.at[a] = d + ends[a];
-      pads.n[a] = (uint32_t)(pad16(ends[a]) - ends[a]);
-    }
-    VP_TRY(st_launch_gather(c, t, tabs[k].tt, idx, section_dev(s, d), pads));
+    VP_TRY(st_launch_gather(c, t, tabs[k].tt, idx, section_dev(s, d), section_pads(s, d)));
   }
   VP_HIP(hipMemcpyAsync(buf, d, total, hipMemcpyDeviceToHost, c->stream));
   VP_HIP(hipStreamSynchronize(c->stream));
   // the headers
-  memset(buf, 0, kSdHdr);
-  put32(buf, kSdMagic);
-  put32(buf + 4, kSdVersion);
-  put32(buf + 8, (uint32_t)c->kind);
-  put32(buf + 12, (uint32_t)nt);
-  put64(buf + 16, total);
-  put64(buf + 24, (uint64_t)c->last_now);
+  put_header(kDelta, buf, c->kind, nt, total, c->last_now);
   put64(buf + 32, base->seq);
   put64(buf + 40, base->epoch);
   put64(buf + 48, c->seq);
   put64(buf + 56, c->st_epoch);
-  for (int k = 0; k < nt; k++) {
-    uint8_t *h = buf + sec[k].s.lru - kStTblHdr;
-    memset(h, 0, kStTblHdr);
-    put32(h, sec[k].s.cap);
-    put32(h + 4, sec[k].n_live);
-    put32(h + 8, sec[k].s.fresh);
-    put32(h + 12, sec[k].s.vsz);
-    put32(h + 16, sec[k].s.n_freed);
-    put32(h + 20, sec[k].s.n_live);
-  }
+  for (int k = 0; k < nt; k++) put_table_header(kDelta, buf, sec[k]);
   *mark = vp_state_mark_t{c->seq, c->st_epoch};
   return 0;
-}
-
-const char *err_text(uint32_t code) {
-  switch (code) {
-    case E_IDX_RANGE: return "idx[%u] is not below the capacity";
-    case E_FREED_RANGE: return "freed[%u] is not below the capacity";
-    case E_IDX_TAIL: return "idx[%u] lies in the never-used tail";
-    case E_FREED_TAIL: return "freed[%u] lies in the never-used tail";
-    case E_IDX_TWICE: return "idx[%u] names an index that is named twice";
-    case E_FREED_TWICE: return "freed[%u] names an index that is named twice";
-    case E_FREED_NORM: return "freed[%u] is fresh_next - 1: the tail is not normalised";
-    case E_BOTH: return "index %u is named in idx[] and in freed[]";
-    case E_TS_NEG: return "ts[%u] is negative";
-    case E_TS_FUTURE: return "ts[%u] is later than last_now";
-    case E_TS_ORDER: return "ts[%u] is earlier than the entry before it";
-    case E_KEY_PAD: return "key[%u] has a non-zero pad byte";
-    case E_VAL_RANGE: return "value[%u] is out of range";
-    case E_KEY_TWICE: return "key[%u] occurs twice";
-    case E_KEY_KEPT: return "key[%u] is held by a kept entry at another index";
-    case E_NOT_KEPT:
-      return "index %u is neither free nor new nor live here: the kept entries and n_new are "
-             "not n_live";
-    default: return "entry %u";
-  }
-}
-int delta_fail(int k, uint32_t tt, unsigned long long e) {
-  char what[128];
-  snprintf(what, sizeof what, err_text((uint32_t)(e >> 32)), (uint32_t)e);
-  return ST_BAD("state delta apply: table %d (%s): %s", k, kTblName[tt], what);
 }
 
 #define SD_BAD(...) ST_BAD("state delta apply: " __VA_ARGS__)
@@ -455,18 +341,10 @@ int delta_apply(vp_ctx *c, const uint8_t *buf, uint64_t bytes) {
   if (c->seq != c->st_follow_seq)
     return SD_BAD("the context changed since it followed (sequence %llu, then %llu)",
                   (unsigned long long)c->seq, (unsigned long long)c->st_follow_seq);
-  if (bytes < kSdHdr) return SD_BAD("%llu bytes hold no header", (unsigned long long)bytes);
-  if (get32(buf) != kSdMagic) return SD_BAD("magic 0x%08x", get32(buf));
-  if (get32(buf + 4) != kSdVersion) return SD_BAD("version %u", get32(buf + 4));
-  if (get32(buf + 8) != (uint32_t)c->kind)
-    return SD_BAD("kind %u into a context of kind %d", get32(buf + 8), c->kind);
-  if (get32(buf + 12) != (uint32_t)nt)
-    return SD_BAD("n_tables %u, this NF has %d", get32(buf + 12), nt);
-  if (get64(buf + 16) != bytes)
-    return SD_BAD("total_bytes %llu, %llu given", (unsigned long long)get64(buf + 16),
-                  (unsigned long long)bytes);
-  const int64_t last_now = (int64_t)get64(buf + 24);
-  if (last_now < -1) return SD_BAD("last_now %lld", (long long)last_now);
+  const Expect want = st_expect(c, tabs, nt);
+  char msg[256];
+  int64_t last_now;
+  if (!read_header(kDelta, want, buf, bytes, &last_now, msg, sizeof msg)) return ST_BAD("%s", msg);
   if (last_now < c->last_now)
     return SD_BAD("last_now %lld is below the context's %lld", (long long)last_now,
                   (long long)c->last_now);
@@ -479,37 +357,8 @@ int delta_apply(vp_ctx *c, const uint8_t *buf, uint64_t bytes) {
   if (mark.epoch != base.epoch || mark.seq < base.seq)
     return SD_BAD("mark (%llu, %llu) does not follow its base", (unsigned long long)mark.seq,
                   (unsigned long long)mark.epoch);
-  DSection sec[2];
-  uint64_t at = kSdHdr;
-  for (int k = 0; k < nt; k++) {
-    const FlowTable &t = *tabs[k].t;
-    if (bytes - at < kStTblHdr) return SD_BAD("table %d: header past the end", k);
-    const uint8_t *h = buf + at;
-    Section &s = sec[k].s;
-    const uint32_t n_live = get32(h + 4), n_new = get32(h + 20);
-    s = Section{get32(h), n_new, get32(h + 8), get32(h + 12), get32(h + 16)};
-    sec[k].n_live = n_live;
-    if (s.cap != t.cap) return SD_BAD("table %d: capacity %u, the context's is %u", k, s.cap, t.cap);
-    if (n_live > s.cap) return SD_BAD("table %d: n_live %u above the capacity", k, n_live);
-    if (s.fresh > s.cap) return SD_BAD("table %d: fresh_next %u above the capacity", k, s.fresh);
-    if (s.vsz != kValSize[tabs[k].tt]) return SD_BAD("table %d: value size %u", k, s.vsz);
-    if (s.n_freed > s.cap || (uint64_t)n_live + s.n_freed + (s.cap - s.fresh) != s.cap)
-      return SD_BAD("table %d: n_live %u + n_freed %u + tail %u is not the capacity %u", k, n_live,
-                    s.n_freed, s.cap - s.fresh, s.cap);
-    if (n_new > n_live) return SD_BAD("table %d: n_new %u above n_live %u", k, n_new, n_live);
-    if (get32(h + 24) | get32(h + 28)) return SD_BAD("table %d: reserved header word not zero", k);
-    section_layout(s, at);
-    if (s.end > bytes)
-      return SD_BAD("table %d: arrays end at %llu of %llu bytes", k, (unsigned long long)s.end,
-                    (unsigned long long)bytes);
-    uint64_t ends[5];
-    section_ends(s, ends);
-    for (uint64_t e : ends)
-      for (uint64_t b = e; b < pad16(e); b++)
-        if (buf[b]) return SD_BAD("table %d: pad byte at %llu not zero", k, (unsigned long long)b);
-    at = s.end;
-  }
-  if (at != bytes) return SD_BAD("%llu bytes behind the last table", (unsigned long long)(bytes - at));
+  Section sec[2];
+  if (!read_sections(kDelta, want, buf, bytes, sec, msg, sizeof msg)) return ST_BAD("%s", msg);
   // ---- upload, then the device's checks
   DevBuf img, scratch;
   VP_TRY(dalloc((uint8_t **)&img.p, bytes));
@@ -521,13 +370,13 @@ int delta_apply(vp_ctx *c, const uint8_t *buf, uint64_t bytes) {
   uint64_t woff = 0, fixed[2], bmw[2], hoff[2], hsz[2];
   for (int k = 0; k < nt; k++) {
     fixed[k] = woff;
-    bmw[k] = (sec[k].s.cap + 31) / 32;
+    bmw[k] = (sec[k].cap + 31) / 32;
     woff += kFixed + 2 * bmw[k];
   }
   const uint64_t zero_words = woff;
   for (int k = 0; k < nt; k++) {
     hoff[k] = woff;
-    hsz[k] = std::max<uint64_t>(next_pow2(2ull * sec[k].s.n_live), 2);
+    hsz[k] = std::max<uint64_t>(next_pow2(2ull * sec[k].n_live), 2);
     woff += hsz[k];
   }
   VP_TRY(dalloc((uint32_t **)&scratch.p, woff));
@@ -549,16 +398,16 @@ int delta_apply(vp_ctx *c, const uint8_t *buf, uint64_t bytes) {
     return 0;
   };
   for (int k = 0; k < nt; k++) {
-    const Section &s = sec[k].s;
+    const Section &s = sec[k];
     sd_check<<<grid_for(std::max({s.n_live, s.n_freed, 1u})), 256, 0, c->stream>>>(
         section_dev(s, d), tabs[k].tt, s.cap, last_now, value_bound(c, tabs[k].tt), sc[k]);
     VP_HIP(hipGetLastError());
   }
   VP_TRY(read_fixed());
   for (int k = 0; k < nt; k++)
-    if (h_fix[k][0] != ~0ull) return delta_fail(k, tabs[k].tt, h_fix[k][0]);
+    if (h_fix[k][0] != ~0ull) return img_refuse(kDelta.who, "idx", k, tabs[k].tt, h_fix[k][0]);
   for (int k = 0; k < nt; k++) {
-    const Section &s = sec[k].s;
+    const Section &s = sec[k];
     sd_check2<<<grid_for(std::max(s.cap, s.n_live)), 256, 0, c->stream>>>(
         section_dev(s, d), tbl_dev(*tabs[k].t), tabs[k].tt, sc[k]);
     VP_HIP(hipGetLastError());
@@ -566,12 +415,12 @@ int delta_apply(vp_ctx *c, const uint8_t *buf, uint64_t bytes) {
   VP_TRY(read_fixed());
   uint64_t floor[2];
   for (int k = 0; k < nt; k++) {
-    if (h_fix[k][0] != ~0ull) return delta_fail(k, tabs[k].tt, h_fix[k][0]);
-    const Section &s = sec[k].s;
+    if (h_fix[k][0] != ~0ull) return img_refuse(kDelta.who, "idx", k, tabs[k].tt, h_fix[k][0]);
+    const Section &s = sec[k];
     const uint64_t kept = h_fix[k][3];
-    if (kept + s.n_live != sec[k].n_live)
+    if (kept + s.n_live != s.n_table)
       return SD_BAD("table %d: %llu kept entries and n_new %u are not n_live %u", k,
-                    (unsigned long long)kept, s.n_live, sec[k].n_live);
+                    (unsigned long long)kept, s.n_live, s.n_table);
     const int64_t ts0 = s.n_live ? (int64_t)get64(buf + s.ts) : 0;
     if (kept && s.n_live && (int64_t)(h_fix[k][1] - 1) > ts0)
       return SD_BAD("table %d: ts[0] %lld is below a kept entry's stamp %lld", k, (long long)ts0,
@@ -581,38 +430,24 @@ int delta_apply(vp_ctx *c, const uint8_t *buf, uint64_t bytes) {
   // ---- the write: from here on the context's state is the delta's
   uint32_t most = 0;
   for (int k = 0; k < nt; k++) {
-    const Section &s = sec[k].s;
+    const Section &s = sec[k];
     const ImgDev im = section_dev(s, d);
     const TableDev t = tbl_dev(*tabs[k].t);
     sd_erase<<<grid_for(std::max(s.cap, s.n_live)), 256, 0, c->stream>>>(im, t, tabs[k].tt, sc[k]);
     if (s.n_live)
       sd_upsert<<<grid_for(s.n_live), 256, 0, c->stream>>>(
           im, t, tabs[k].tt, SideVals{c->be_rec, c->pol_size, c->pol_time}, c->seq, sc[k]);
-    sd_commit<<<grid_for(std::max(s.n_freed, 1u)), 256, 0, c->stream>>>(im, t, sec[k].n_live,
+    sd_commit<<<grid_for(std::max(s.n_freed, 1u)), 256, 0, c->stream>>>(im, t, s.n_table,
                                                                         sc[k]);
     VP_HIP(hipGetLastError());
     most = std::max(most, s.n_live);
   }
   VP_HIP(hipStreamSynchronize(c->stream));
-  for (int k = 0; k < nt; k++) {
-    FlowTable &t = *tabs[k].t;
-    t.ts_floor = floor[k];
-    t.fs_hint = 0;
-    t.runs_seen = true;
-    t.last_run_tiles = 0;
-    t.ctl_clean = false;
-    t.jr_on = false;
-  }
-  c->jr_want = false;
-  c->last_now = last_now;
   c->seq += most;  // (past every tseq handed out above)
-  c->fold_pending = false;
   c->st_mark = mark;
   c->st_follow_seq = c->seq;
-  for (int k = 0; k < nt; k++) {
-    VP_TRY(tbl_layout_check(c, *tabs[k].t));
-    VP_TRY(tbl_check_tombs(c, *tabs[k].t));
-  }
+  VP_TRY(st_replaced(c, tabs, nt, floor, last_now));
+  for (int k = 0; k < nt; k++) VP_TRY(tbl_check_tombs(c, *tabs[k].t));
   return 0;
 }
 
