@@ -1356,6 +1356,19 @@ int vp_last_stage_ms(vp_ctx *ctx, float *ms, int *stages);
 int vp_probe_slots(void *frames, uint32_t n, uint32_t slot, int store, int reps, float *ms);
 int vp_probe_slots_w(void *frames, uint32_t n, uint32_t slot, int store, int waves, int reps,
                      float *ms);
+/* vp_probe_slots_p: the same pass with the cache policy of its loads and of
+ * its stores given, each one of the VP_POLICY_* values below (the policy
+ * bits of the gfx950 buffer instructions); vp_probe_slots_w is this call
+ * with the tile kernels' own pair. Pairs other than that one run at 64-byte
+ * slots and 4 or 16 waves; any other value or shape is VP_EINVAL. The table
+ * this call measured is in DESIGN.md §5.1 and profiles/r07a_tile_policy.txt. */
+#define VP_POLICY_PLAIN 0
+#define VP_POLICY_NT 2       /* non-temporal */
+#define VP_POLICY_SC1 16     /* loads: past the CU's L1; stores: write-through */
+#define VP_POLICY_SC0_SC1 17 /* loads only */
+#define VP_POLICY_SC1_NT 18  /* stores only */
+int vp_probe_slots_p(void *frames, uint32_t n, uint32_t slot, int store, int waves,
+                     int load_policy, int store_policy, int reps, float *ms);
 
 /* Build identification (e.g. "vigpath gfx950"). */
 const char *vp_version(void);

@@ -264,7 +264,7 @@ EXPORTS = ["vp_nat_create", "vp_bridge_create", "vp_lb_create", "vp_fw_create",
            "vp_kernel_timing", "vp_last_kernel_ms", "vp_version", "vp_table_stats_get",
            "vp_last_error", "vp_register_host", "vp_unregister_host", "vp_process_mbufs",
            "vp_last_stage_ms", "vp_stage_ms", "vp_comm_abort", "vp_probe_slots",
-           "vp_probe_slots_w", "vp_process_one", "vp_last_kernel", "vp_serve_stats_get",
+           "vp_probe_slots_w", "vp_probe_slots_p", "vp_process_one", "vp_last_kernel", "vp_serve_stats_get",
            "vp_serve_expiry_stats_get", "vp_tx_build", "vp_tx_pack", "vp_tx_rebatch",
            "vp_tx_merge", "vp_rx_unpack", "vp_rx_merge", "vp_tx_return", "vp_chain_create", "vp_chain_destroy",
            "vp_chain_run", "vp_chain_view_get", "vp_chain_process_device",
@@ -353,6 +353,9 @@ def lib(path: str | None = None):
     L.vp_probe_slots_w.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int,
                                    C.POINTER(C.c_float)]
     L.vp_probe_slots_w.restype = C.c_int
+    L.vp_probe_slots_p.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int,
+                                   C.c_int, C.c_int, C.POINTER(C.c_float)]
+    L.vp_probe_slots_p.restype = C.c_int
     L.vp_live_count.argtypes = [C.c_void_p]
     L.vp_live_count.restype = C.c_int64
     L.vp_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float),

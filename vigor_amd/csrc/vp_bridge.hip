@@ -157,7 +157,7 @@ __device__ __forceinline__ uint16_t resolve(int32_t fwd, uint32_t in) {
 // Ethernet header words: dst = {w0, w1 & 0xFFFF}, src = {w1 >> 16 | w2 << 16,
 // w2 >> 16} (bridge_main.c:312 borrows 14 bytes with no length check).
 __device__ __forceinline__ uint4 eth_words(const BridgeArgs &a, uint32_t p) {
-  return *reinterpret_cast<const uint4 *>(a.frames + (size_t)p * a.slot);
+  return frame_ld16(a.frames + (size_t)p * a.slot);
 }
 
 // One dynamic-table bucket against a MAC (words 0-1): the index and *port

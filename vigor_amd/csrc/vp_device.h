@@ -182,14 +182,77 @@ __device__ __forceinline__ void st_stream(uint4 *p, uint4 v) { *p = v; }
 // Stores are write-through (sc1: the written line leaves the XCD's L2 at
 // once, so the frame stream leaves fewer dirty lines between the table rows
 // and at the kernel boundary): 3.5 % faster nat_classify64 than write-back
-// stores; non-temporal (evict-first) loads measured 30 % slower (round 2
-// diagnostic builds).
-__device__ __forceinline__ uint4 tile_ld(const uint4 *p) { return *p; }
+// stores (round 2 diagnostic builds). The bytes are read once
+// and written once, so the loads are non-temporal and the stores sc1 nt:
+// 0.472 -> 0.422 ms per headline step, interleaved on one box (DESIGN.md
+// §5.1, profiles/r07a_tile_policy.txt; round 2's diagnostic build of an
+// earlier tile had measured nt loads 30 % slower).
+//
+// The cache policy of both is a compile-time value: the bits of a buffer
+// instruction's aux operand (gfx950: sc0 = 1, nt = 2, sc1 = 16), which
+// vp_probe_slots_p (vp_probe.hip) takes too. A tile policy packs the load
+// bits, the store bits and whether vignat's side streams (the length load
+// and the out-port store of the lean tile) go non-temporal; kTilePolicy is
+// what every tile kernel runs, kTilePolicyParent what ran before the ladder
+// of profiles/r07a_tile_policy.txt (kept for A/B, VIGPATH_TILE_POLICY=0).
+constexpr int kAuxSc0 = 1, kAuxNt = 2, kAuxSc1 = 16;
+constexpr uint32_t tile_policy(int ld, int st, bool side = false) {
+  return (uint32_t)ld | ((uint32_t)st << 8) | ((uint32_t)side << 16);
+}
+constexpr int policy_ld(uint32_t tp) { return (int)(tp & 0xFF); }
+constexpr int policy_st(uint32_t tp) { return (int)((tp >> 8) & 0xFF); }
+constexpr bool policy_side(uint32_t tp) { return ((tp >> 16) & 1) != 0; }
+constexpr uint32_t kTilePolicyParent = tile_policy(0, kAuxSc1);
+constexpr uint32_t kTilePolicy = tile_policy(kAuxNt, kAuxSc1 | kAuxNt);
+
+// 16-byte chunk c of the tile at g (wave-uniform g). Plain loads stay global
+// loads; nt is the same instruction with the bit set; the sc policies go
+// through the tile's buffer resource, as the stores do.
+template <int LD = policy_ld(kTilePolicy)>
+__device__ __forceinline__ uint4 tile_ld(const uint4 *g, uint32_t c) {
+  if constexpr (LD == 0) {
+    return g[c];
+  } else if constexpr (LD == kAuxNt) {
+    typedef unsigned v4u __attribute__((ext_vector_type(4)));
+    const v4u x = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(g + c));
+    return make_uint4(x.x, x.y, x.z, x.w);
+  } else {
+    typedef unsigned v4u __attribute__((ext_vector_type(4)));
+    const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4 *>(g), 0, 4096, 0x00020000);
+    const v4u x = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(c * 16), 0, LD);
+    return make_uint4(x.x, x.y, x.z, x.w);
+  }
+}
+template <int ST = policy_st(kTilePolicy)>
 __device__ __forceinline__ void tile_st(uint4 *g, uint32_t c, uint4 v) {
   typedef unsigned v4u __attribute__((ext_vector_type(4)));
   const auto rs = __builtin_amdgcn_make_buffer_rsrc(g, 0, 4096, 0x00020000);
   const v4u x = {v.x, v.y, v.z, v.w};
-  __builtin_amdgcn_raw_buffer_store_b128(x, rs, (int)(c * 16), 0, 16);
+  __builtin_amdgcn_raw_buffer_store_b128(x, rs, (int)(c * 16), 0, ST);
+}
+// 16 bytes of a frame at a lane's own address (vigbridge reads one chunk per
+// slot, a pure read-once stream): plain or non-temporal, as the tile loads
+__device__ __forceinline__ uint4 frame_ld16(const void *p) {
+  if constexpr (policy_ld(kTilePolicy) == kAuxNt) {
+    typedef unsigned v4u __attribute__((ext_vector_type(4)));
+    const v4u x = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(p));
+    return make_uint4(x.x, x.y, x.z, x.w);
+  } else {
+    return *reinterpret_cast<const uint4 *>(p);
+  }
+}
+// vignat's side streams (2 B per packet each way), NT: non-temporal
+template <bool NT>
+__device__ __forceinline__ uint16_t side_ld(const uint16_t *p) {
+  if constexpr (NT) return __builtin_nontemporal_load(p);
+  return *p;
+}
+template <bool NT>
+__device__ __forceinline__ void side_st(uint16_t *p, uint16_t v) {
+  if constexpr (NT)
+    __builtin_nontemporal_store(v, p);
+  else
+    *p = v;
 }
 
 // Stores of the wide-slot classify tiles: 16 bytes at byte `off` of the tile
@@ -591,7 +654,7 @@ __device__ __forceinline__ void frames64_tiles(uint8_t *frames,
 #pragma unroll
     for (uint32_t j = 0; j < 4; j++) {
       const uint32_t c = 64 * j + lane;
-      r[j] = (c >> 2) < avail ? tile_ld(g + c) : make_uint4(0, 0, 0, 0);
+      r[j] = (c >> 2) < avail ? tile_ld(g, c) : make_uint4(0, 0, 0, 0);
     }
     const uint32_t p = tb + lane;
     m_in = p < n_all ? port_of(in_dev, in0, p) : 0u;
@@ -844,11 +907,12 @@ __device__ __forceinline__ void reprobe_slices(const uint32_t *list, const uint3
 // 32-bit offsets, so no per-lane 64-bit addresses stay live. At a batch's
 // last step the group's partial sums are added by xor shuffles and the
 // frame's sum handed to its own lane. Returns that sum (< 2^27, unfolded).
+// (read-once frame bytes: the tile load policy)
 __device__ __forceinline__ uint4 buf_ld16(const void *base, uint32_t bytes, uint32_t off) {
   typedef unsigned v4u __attribute__((ext_vector_type(4)));
   const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)bytes,
                                                     0x00020000);
-  const v4u x = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0);
+  const v4u x = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, policy_ld(kTilePolicy));
   return make_uint4(x.x, x.y, x.z, x.w);
 }
 constexpr uint32_t kBufOff = 0x80000000u;  // an offset past every tile's resource

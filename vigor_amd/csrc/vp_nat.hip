@@ -713,11 +713,16 @@ __device__ __forceinline__ uint32_t dense128_tail(const uint4 d[8]) {
 // O: owner mode compiled in (false: the single-table kernels, whose owner
 // paths -- pass 1's routing tile, nat_issue's remote keys, route notes --
 // fold away with own.n a constant 0, fewer registers for the lean tile).
+// TP: the 64-byte tile's cache policy (tile_policy, vp_device.h): its frame
+// loads and stores, and (policy_side) the lean tile's length load and
+// out-port store; the bucket-row gathers stay plain, they are reused.
 template <uint32_t G, uint32_t H = 1, bool D = false, bool X = false, uint32_t W = 4,
-          bool ST = false, bool O = true>
+          bool ST = false, bool O = true, uint32_t TP = kTilePolicy>
 __device__ __forceinline__ void nat_tiles(NatArgs a, uint32_t n_all, TouchBins bins,
                                           TileQueue rq) {
   static_assert(!X || G == 0, "header slots (X) are 64-byte slots");
+  constexpr int kLd = policy_ld(TP), kSt = policy_st(TP);
+  constexpr bool kSide = policy_side(TP);
   if constexpr (!O) {
     a.own.n = 0;
     a.own.all = 0;
@@ -782,23 +787,22 @@ __device__ __forceinline__ void nat_tiles(NatArgs a, uint32_t n_all, TouchBins b
       m_len = p < n_all ? a.len[p] : 0u;
       return;
     }
+    const uint4 *g4 = reinterpret_cast<const uint4 *>(g8);  // (G == 0: chunk c at 16 c)
     if (tb + 64 <= n_all) {  // (wave-uniform) a whole tile: no per-lane guards
 #pragma unroll
-      for (uint32_t j = 0; j < 4; j++)
-        r[j] = tile_ld(reinterpret_cast<const uint4 *>(g8 + chunk_at(64 * j + lane)));
+      for (uint32_t j = 0; j < 4; j++) r[j] = tile_ld<kLd>(g4, 64 * j + lane);
       m_in = port_of(a.in_dev, a.in0, p);
-      m_len = a.len[p];
+      m_len = side_ld<kSide>(a.len + p);
       return;
     }
     const uint32_t avail = n_all - tb;  // in the batch
 #pragma unroll
     for (uint32_t j = 0; j < 4; j++) {
       const uint32_t c = 64 * j + lane;
-      r[j] = (c >> 2) < avail ? tile_ld(reinterpret_cast<const uint4 *>(g8 + chunk_at(c)))
-                              : make_uint4(0, 0, 0, 0);
+      r[j] = (c >> 2) < avail ? tile_ld<kLd>(g4, c) : make_uint4(0, 0, 0, 0);
     }
     m_in = p < n_all ? port_of(a.in_dev, a.in0, p) : 0u;
-    m_len = p < n_all ? a.len[p] : 0u;
+    m_len = p < n_all ? side_ld<kSide>(a.len + p) : 0u;
   };
   const uint32_t rb = a.vb0 + blockIdx.x;  // (virtual blocks: the chunked pipeline)
   const uint32_t per_b = a.vper ? a.vper : (tiles + gridDim.x - 1) / gridDim.x;
@@ -1039,7 +1043,7 @@ __device__ __forceinline__ void nat_tiles(NatArgs a, uint32_t n_all, TouchBins b
         f.w[0] = a.wan_macw0;
         f.w[1] = a.wan_macw1;
         f.w[2] = a.wan_macw2;
-        a.out[p] = (uint16_t)a.wan;
+        side_st<kSide>(a.out + p, (uint16_t)a.wan);
       }
       store_all = true;
     } else if (lean_own && __ballot(mine && nat_lan_fast_ok(a, f, in, ln)) == ~0ull) {
@@ -1120,7 +1124,7 @@ __device__ __forceinline__ void nat_tiles(NatArgs a, uint32_t n_all, TouchBins b
 #pragma unroll
         for (uint32_t j = 0; j < 4; j++) {
           const uint32_t c = 64 * j + lane;
-          if ((mm >> (c >> 2)) & 1ull) tile_st(g, c, S[chunk_swz(c)]);
+          if ((mm >> (c >> 2)) & 1ull) tile_st<kSt>(g, c, S[chunk_swz(c)]);
         }
       }
       wave_lds_sync();  // the next tile overwrites S
@@ -1164,7 +1168,7 @@ __device__ __forceinline__ void nat_tiles(NatArgs a, uint32_t n_all, TouchBins b
 #pragma unroll
         for (uint32_t j = 0; j < 4; j++) {
           const uint32_t c = 64 * j + lane;
-          if ((mm >> (c >> 2)) & 1ull) tile_st(g, c, S[chunk_swz(c)]);
+          if ((mm >> (c >> 2)) & 1ull) tile_st<kSt>(g, c, S[chunk_swz(c)]);
         }
         wave_lds_sync();  // the next tile overwrites S
       }
@@ -1180,7 +1184,8 @@ __device__ __forceinline__ void nat_tiles(NatArgs a, uint32_t n_all, TouchBins b
             make_uint4(f.w[4 * k], f.w[4 * k + 1], f.w[4 * k + 2], f.w[4 * k + 3]);
       wave_lds_sync();
 #pragma unroll
-      for (uint32_t j = 0; j < 4; j++) tile_st(g, 64 * j + lane, S[chunk_swz(64 * j + lane)]);
+      for (uint32_t j = 0; j < 4; j++)
+        tile_st<kSt>(g, 64 * j + lane, S[chunk_swz(64 * j + lane)]);
       wave_lds_sync();  // the next tile overwrites S
     }
   }
@@ -1220,6 +1225,12 @@ __global__ __launch_bounds__(1024, 1) void nat_classify64w(NatArgs a, uint32_t n
 __global__ __launch_bounds__(1024, 1) void nat_classify64ws(NatArgs a, uint32_t n_all,
                                                            TouchBins bins, TileQueue rq) {
   nat_tiles<0, 1, false, false, 16, true, false>(a, n_all, bins, rq);
+}
+// The same two kernels under another tile policy (VIGPATH_TILE_POLICY=0, below)
+template <bool ST, uint32_t TP>
+__global__ __launch_bounds__(1024, 1) void nat_classify64w_p(NatArgs a, uint32_t n_all,
+                                                            TouchBins bins, TileQueue rq) {
+  nat_tiles<0, 1, false, false, 16, ST, false, TP>(a, n_all, bins, rq);
 }
 // owner mode's pass 1 on the 1024-thread tile (nat_phase_a_owner)
 __global__ __launch_bounds__(1024, 1) void nat_classify64wo(NatArgs a, uint32_t n_all,
@@ -1270,9 +1281,29 @@ static uint32_t nat_block_waves() {
   return w;
 }
 
+// The tile policy of nat_classify64w/ws (tile_policy, vp_device.h), read
+// once: VIGPATH_TILE_POLICY=0 runs them with the policy from before the
+// ladder (plain loads, sc1 stores: kTilePolicyParent), for A/B; anything else
+// is the default, kTilePolicy.
+struct NatPolicyKernels {
+  NatTileKernel w, ws;
+};
+static NatPolicyKernels nat_policy_kernels() {
+  static const NatPolicyKernels k = [] {
+    const char *e = getenv("VIGPATH_TILE_POLICY");
+    if (e && e[0] == '0' && !e[1])
+      return NatPolicyKernels{nat_classify64w_p<false, kTilePolicyParent>,
+                              nat_classify64w_p<true, kTilePolicyParent>};
+    return NatPolicyKernels{nat_classify64w, nat_classify64ws};
+  }();
+  return k;
+}
+
 static const char *nat_tile_kernel_name(NatTileKernel k) {
   return k == nat_classify64w    ? "nat_classify64w"
          : k == nat_classify64ws ? "nat_classify64ws"
+         : k == nat_policy_kernels().w  ? "nat_classify64w_pp"  // (the parent's policy)
+         : k == nat_policy_kernels().ws ? "nat_classify64ws_pp"
          : k == nat_classify64   ? "nat_classify64"
          : k == nat_classify64x  ? "nat_classify64x"
          : k == nat_classify128  ? "nat_classify128"
@@ -1280,13 +1311,13 @@ static const char *nat_tile_kernel_name(NatTileKernel k) {
 }
 
 static uint32_t nat_tile_waves(NatTileKernel k) {
-  return k == nat_classify64w || k == nat_classify64ws ? 16u : 4u;
+  return k == nat_policy_kernels().w || k == nat_policy_kernels().ws ? 16u : 4u;
 }
 
 static NatTileKernel nat_tile_kernel(uint32_t slot, bool hdr_tail = false,
                                      bool staged = false) {
   if (slot == 64 && !hdr_tail && nat_block_waves() == 16)
-    return staged ? nat_classify64ws : nat_classify64w;
+    return staged ? nat_policy_kernels().ws : nat_policy_kernels().w;
   if (slot == 64) return hdr_tail ? nat_classify64x : nat_classify64;
   if (slot == 128) return nat_classify128;
   const uint32_t nch = (slot - 64) / 16;
