@@ -1248,6 +1248,60 @@ int vp_table_entries(vp_ctx *ctx, int table, uint32_t n, const uint32_t *idx  /*
                      const vp_lookup_out *out, void *stream);
 int vp_table_value_size(vp_ctx *ctx, int table, uint32_t *bytes);
 
+/* -------------------------------------------------------- table erase -- */
+
+/* Take entries out of a context's table from the control plane: kill a
+ * connection, evict a MAC that moved, take a backend out, reset a
+ * subscriber's token bucket. On the device, n queries in one call; the work
+ * follows n, not the capacity.
+ *
+ * `table`, keys, indices, value_size and the vp_lookup_out arrays are exactly
+ * those of vp_table_lookup / vp_table_entries (above). vp_table_erase names
+ * entries by key, vp_table_free by index. The call behaves like this loop:
+ *
+ *   for q = 0 .. n-1 in order: if the query names a live entry, map_erase its
+ *   key and dchain_free_index its index.
+ *
+ * dchain_free_index pushes the index on the front of the free list, as expiry
+ * does: the allocator hands out the index of the last erasing query first.
+ * A query that names nothing live erases nothing and is not an error: a miss,
+ * a key with a non-zero pad bit, an index at or above the capacity or not
+ * allocated, and a key or index that an earlier query of the same call
+ * already erased.
+ *
+ * For an erasing query out->index[q] is the freed index and ts / key / value
+ * are the entry as it was before the erase. For every other query the outputs
+ * are VP_LOOKUP_MISS and zeros, as for a lookup miss. *n_erased (host memory,
+ * may be NULL) is the number of erasing queries. out may be NULL, and so may
+ * any of its arrays.
+ *
+ * The state image after the call is the image before it with the erased
+ * entries removed from lru[], the others keeping their order, and the erased
+ * indices put before the old freed[] in reverse query order; the tail
+ * normalisation of the image then applies. Nothing else changes: no stamp and
+ * no other entry's value moves, last_now stays. viglb flows that point at an
+ * erased backend stay as they are, and the data path finds the backend dead
+ * as it does after a backend expiry.
+ *
+ * A call that erased at least one entry ends a vp_state_follow, as a packet
+ * does, and advances the context's sequence by one, so a mark taken before
+ * names an earlier moment: a delta saved afterwards from such a mark carries
+ * the erasures in its freed[] and applies on a standby that holds that mark.
+ * A call that erased nothing changes neither mark nor following.
+ *
+ * Like the lookups the calls stop the NF's resident kernel and wait for the
+ * context's stream first, then run on `stream` (NULL: the context's own) and
+ * return when done. VP_ENOTSUP on a context attached to a multi-GPU
+ * communicator. VP_EINVAL, with the lookups' texts under these calls' names
+ * in vp_last_error(): a NULL ctx; a table the NF does not have; n > 0 with
+ * NULL keys / idx; a misaligned pointer. A refused call changes and writes
+ * nothing. n == 0 is VP_OK, launches nothing and writes *n_erased = 0. */
+int vp_table_erase(vp_ctx *ctx, int table, uint32_t n, const uint8_t  *keys /* [n][16] device */,
+                   const vp_lookup_out *out /* may be NULL */, uint32_t *n_erased /* host, may be NULL */,
+                   void *stream);
+int vp_table_free (vp_ctx *ctx, int table, uint32_t n, const uint32_t *idx  /* [n] device */,
+                   const vp_lookup_out *out, uint32_t *n_erased, void *stream);
+
 /* Number of live flows / learned MACs / flows+backends. */
 int64_t vp_live_count(vp_ctx *ctx);
 

@@ -271,7 +271,7 @@ EXPORTS = ["vp_nat_create", "vp_bridge_create", "vp_lb_create", "vp_fw_create",
            "vp_state_size", "vp_state_save", "vp_state_load", "vp_state_mark",
            "vp_state_delta_size", "vp_state_delta_save", "vp_state_follow",
            "vp_state_delta_apply", "vp_table_lookup", "vp_table_entries",
-           "vp_table_value_size"]
+           "vp_table_value_size", "vp_table_erase", "vp_table_free"]
 
 _libs = {}
 
@@ -431,6 +431,10 @@ def lib(path: str | None = None):
         getattr(L, name).restype = C.c_int
     L.vp_table_value_size.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint32)]
     L.vp_table_value_size.restype = C.c_int
+    for name in ("vp_table_erase", "vp_table_free"):
+        getattr(L, name).argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p,
+                                     C.POINTER(VpLookupOutC), C.POINTER(C.c_uint32), C.c_void_p]
+        getattr(L, name).restype = C.c_int
     L.vp_last_error.argtypes = []
     L.vp_last_error.restype = C.c_char_p
     _libs[path] = L

@@ -109,6 +109,7 @@ hipError_t preload_chain(hipStream_t s);
 hipError_t preload_state(hipStream_t s);
 hipError_t preload_statedelta(hipStream_t s);
 hipError_t preload_lookup(hipStream_t s);
+hipError_t preload_erase(hipStream_t s);
 
 // vp_txpack.hip's one-block exclusive scan of m 64-bit sums in place, also
 // launched by vp_rx_unpack (vp_rxunpack.hip): <<<1, kTxpScanThreads>>>
@@ -254,6 +255,11 @@ struct FlowTable {
   uint4 *jrec = nullptr;
   uint32_t jr_n = 0;
   bool jr_on = false;
+  // vp_table_erase / vp_table_free (vp_erase.hip): per index the first query
+  // of the running call that names it; all ones between calls (allocated by
+  // the first call; claim_dirty: a call failed midway, the next one clears it)
+  uint32_t *claim = nullptr;
+  bool claim_dirty = false;
   // owner-sharded mode (vp_shard_mode): this rank's buckets
   // hold only the keys it owns; key by index is replicated in kv
   uint4 *kv = nullptr;
@@ -295,6 +301,9 @@ struct Workspace {
   // output position and its queues' sums per wave (u64): one buffer per call,
   // which may be in flight on different streams together
   CallBuf tx_cnt, txp_sum, rxu_sum, rxm_rec;
+  // vp_table_erase / vp_table_free: the winners per wave (u64, scanned by
+  // txp_scan as the others' sums are) and the index each query resolved to
+  CallBuf erase_ws;
   // tbl_new_keys_unsorted: the tagged key set (3 x u64 per slot, never
   // reset: a slot of an older tag is empty), its tag, first-sighting bits
   // per position and their scan, the first sightings' miss ordinals and

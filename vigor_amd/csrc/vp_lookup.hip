@@ -11,7 +11,9 @@
 // slot_of[] set) and reads its entry through slot_of. Both take stamp, key
 // and value from entry_of, the save's reader, and write each output array one
 // entry per lane. The calls start as the state calls do (st_enter) and change
-// nothing in the context or its tables.
+// nothing in the context or its tables. lk_enter, the checks of the arguments
+// behind st_enter, is also how vp_table_erase / vp_table_free start
+// (vp_erase.hip).
 #include <hip/hip_runtime.h>
 
 #include "vp_state_dev.h"
@@ -25,24 +27,6 @@ using namespace stimg;
 namespace {
 
 static_assert(VP_LOOKUP_MISS == kNone, "a miss is the probe's kNone");
-
-struct LkOut {  // vp_lookup_out; any pointer may be null
-  uint32_t *index;
-  int64_t *ts;
-  uint4 *key;
-  uint8_t *value;
-};
-
-// Query q's answer: index i with the entry words raw, or a miss (i == kNone).
-__device__ __forceinline__ void lk_put(const TableDev &t, uint32_t tt, const SideVals &sv,
-                                       const LkOut &o, uint32_t q, uint32_t i, uint4 raw) {
-  Entry e{0, make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)};
-  if (i != kNone) e = entry_of(t, tt, sv, i, raw);
-  if (o.index) o.index[q] = i;
-  if (o.ts) o.ts[q] = e.ts;
-  if (o.key) o.key[q] = e.key;
-  if (o.value) value_put(tt, o.value, q, e.val);
-}
 
 __global__ __launch_bounds__(256) void lk_by_key(TableDev t, uint32_t tt, SideVals sv,
                                                  const uint4 *keys, uint32_t n, LkOut o) {
@@ -81,24 +65,36 @@ int lk_table(const char *fn, int table, const StTable tabs[2], int nt, StTable *
   return 0;
 }
 
-int table_query(const char *fn, vp_ctx *c, int table, uint32_t n, const void *in, bool by_key,
-                const vp_lookup_out *out, void *stream) {
+}  // namespace
+
+int lk_enter(const char *fn, vp_ctx *c, int table, uint32_t n, const void *in, bool by_key,
+             const vp_lookup_out *out, bool need_out, StTable *tb) {
   if (!c) return ST_BAD("%s: ctx is NULL", fn);
-  if (!out) return ST_BAD("%s: out is NULL", fn);
-  StTable tabs[2], tb;
+  if (need_out && !out) return ST_BAD("%s: out is NULL", fn);
+  StTable tabs[2];
   int nt = 0;
   VP_TRY(st_enter(c, tabs, &nt));
-  VP_TRY(lk_table(fn, table, tabs, nt, &tb));
+  VP_TRY(lk_table(fn, table, tabs, nt, tb));
   const char *in_name = by_key ? "keys" : "idx";
-  const uint32_t vsz = kValSize[tb.tt];
+  const uint32_t vsz = kValSize[tb->tt];
   if (n && !in) return ST_BAD("%s: %s is NULL with n = %u", fn, in_name, n);
   if (!aligned(in, by_key ? 16 : 4))
     return ST_BAD("%s: %s is not %d-byte aligned", fn, in_name, by_key ? 16 : 4);
+  if (!out) return 0;
   if (!aligned(out->index, 4)) return ST_BAD("%s: out->index is not 4-byte aligned", fn);
   if (!aligned(out->ts, 8)) return ST_BAD("%s: out->ts is not 8-byte aligned", fn);
   if (!aligned(out->key, 16)) return ST_BAD("%s: out->key is not 16-byte aligned", fn);
   if (vsz && !aligned(out->value, vsz))  // (4, 8 or 16: the width of one entry's store)
     return ST_BAD("%s: out->value is not %u-byte aligned", fn, vsz);
+  return 0;
+}
+
+namespace {
+
+int table_query(const char *fn, vp_ctx *c, int table, uint32_t n, const void *in, bool by_key,
+                const vp_lookup_out *out, void *stream) {
+  StTable tb;
+  VP_TRY(lk_enter(fn, c, table, n, in, by_key, out, true, &tb));
   if (n == 0) return 0;
   // A gather bound by latency: one dependent bucket read per lane, so as many
   // waves as the device holds at once and no more -- grid_for's 2048 blocks
@@ -106,7 +102,7 @@ int table_query(const char *fn, vp_ctx *c, int table, uint32_t n, const void *in
   const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   const TableDev t = tbl_dev(*tb.t);
   const SideVals sv{c->be_rec, c->pol_size, c->pol_time};
-  const LkOut o{out->index, out->ts, reinterpret_cast<uint4 *>(out->key), vsz ? out->value : nullptr};
+  const LkOut o = lk_out(out, tb.tt);
   if (by_key)
     lk_by_key<<<grid_for(n), 256, 0, s>>>(t, tb.tt, sv, (const uint4 *)in, n, o);
   else

@@ -195,7 +195,7 @@ static int preload_units(int gpu, hipStream_t s) {
                  preload_fw, preload_pol, preload_comm, preload_mbuf, preload_tx,
                  preload_txpack, preload_txbatch, preload_txmerge, preload_rxunpack,
                  preload_rxmerge, preload_txreturn, preload_chain, preload_state,
-                 preload_statedelta, preload_lookup})
+                 preload_statedelta, preload_lookup, preload_erase})
     VP_HIP(f(s));
   VP_HIP(hipStreamSynchronize(s));
   done.push_back(gpu);
@@ -249,7 +249,7 @@ static void free_all(vp_ctx *c) {
                   w.reply2,  w.rreply2,  w.lcnt, w.nkset, w.nkbits, w.nkpre,
                   w.nkfirst, w.nkcnt, w.in_fill};
   for (void *p : ptrs) hipFree(p);
-  for (CallBuf *b : {&w.tx_cnt, &w.txp_sum, &w.rxu_sum, &w.rxm_rec}) {
+  for (CallBuf *b : {&w.tx_cnt, &w.txp_sum, &w.rxu_sum, &w.rxm_rec, &w.erase_ws}) {
     hipFree(b->p);
     if (b->ev) hipEventDestroy(b->ev);
   }

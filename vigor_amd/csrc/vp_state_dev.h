@@ -4,6 +4,8 @@
 // hashes, the check of those arrays with its error table (§5.16.1), what a
 // context forgets when its tables are replaced, and the launchers of the save
 // path's free-list writer and gather, whose kernels stay in vp_state.hip.
+// Also what the lookups and the erase (vp_lookup.hip, vp_erase.hip; §5.16,
+// §5.17) share: a query's answer arrays and their writer, and the calls' start.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -143,6 +145,32 @@ __device__ __forceinline__ void value_put(uint32_t tt, uint8_t *val, uint32_t j,
   } else if (tt == TT_POL) {
     reinterpret_cast<uint4 *>(val)[j] = v;
   }
+}
+
+// vp_lookup_out as the lookup and erase kernels take it (vp_lookup.hip,
+// vp_erase.hip); any pointer may be null.
+struct LkOut {
+  uint32_t *index;
+  int64_t *ts;
+  uint4 *key;
+  uint8_t *value;
+};
+// out as the kernels' argument (null: nothing is wanted; a table without a
+// value never has its value pointer looked at).
+inline LkOut lk_out(const vp_lookup_out *out, uint32_t tt) {
+  if (!out) return LkOut{nullptr, nullptr, nullptr, nullptr};
+  return LkOut{out->index, out->ts, reinterpret_cast<uint4 *>(out->key),
+               kValSize[tt] ? out->value : nullptr};
+}
+// Query q's answer: index i with the entry words raw, or a miss (i == kNone).
+__device__ __forceinline__ void lk_put(const TableDev &t, uint32_t tt, const SideVals &sv,
+                                       const LkOut &o, uint32_t q, uint32_t i, uint4 raw) {
+  Entry e{0, make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)};
+  if (i != kNone) e = entry_of(t, tt, sv, i, raw);
+  if (o.index) o.index[q] = i;
+  if (o.ts) o.ts[q] = e.ts;
+  if (o.key) o.key[q] = e.key;
+  if (o.value) value_put(tt, o.value, q, e.val);
 }
 
 // The entry's key words from the image's key and value.
@@ -333,5 +361,11 @@ int st_launch_gather(vp_ctx *c, FlowTable &t, uint32_t tt, const uint32_t *idx,
 // does that itself, before.
 int st_replaced(vp_ctx *c, stimg::StTable tabs[2], int nt, const uint64_t floor[2],
                 int64_t last_now);
+// vp_lookup.hip. How a lookup or an erase call `fn` starts: the context, then
+// st_enter, then the table, the input (keys: 16-byte aligned, idx: 4) and the
+// output pointers' alignments; VP_EINVAL names the argument. need_out: a NULL
+// out is refused. *tb: the table asked about.
+int lk_enter(const char *fn, vp_ctx *c, int table, uint32_t n, const void *in, bool by_key,
+             const vp_lookup_out *out, bool need_out, stimg::StTable *tb);
 
 }  // namespace vp

@@ -230,6 +230,7 @@ void tbl_free(FlowTable &t) {
   hipFree(t.kv);
   hipFree(t.jr);
   hipFree(t.jrec);
+  hipFree(t.claim);
   if (t.h_pin) hipHostFree(t.h_pin);
   if (t.h_pub) hipHostFree(t.h_pub);
   t = FlowTable{};

@@ -630,6 +630,67 @@ class NfBase:
         src = torch.from_numpy(idx.view(np.int32).copy()).to("cuda:%d" % self.gpu)
         return self._table_query_host(self.entries_device, src, idx.shape[0], table)
 
+    def _table_erase(self, call, what, n, src, index, ts, key, value, table, stream) -> int:
+        for t, width, count in ((index, 4, n), (ts, 8, n), (key, 1, 16 * n)):
+            if t is not None:
+                assert t.is_cuda and t.element_size() == width and t.numel() >= count
+        if value is not None:
+            assert value.is_cuda and value.numel() * value.element_size() >= n * self.value_size(table)
+        out = VpLookupOutC(index=_dptr(index), ts=_dptr(ts), key=_dptr(key), value=_dptr(value))
+        s = C.c_void_p(stream.cuda_stream) if stream is not None else None
+        k = C.c_uint32()
+        self._ck(call(self.h, table, n, _dptr(src) if n else None, C.byref(out), C.byref(k), s), what)
+        return int(k.value)
+
+    def erase_device(self, keys, index=None, ts=None, key=None, value=None, table: int = 0,
+                     stream=None) -> int:
+        """vp_table_erase: take out the live entry that holds each 16-byte key
+        of `keys` (as lookup_device takes them), in query order: the index of
+        the last erasing query is the first the allocator hands out again. A
+        query that names nothing live (a miss, a pad byte set, a key an
+        earlier query of the call erased) is a no-op. The outputs are
+        lookup_device's: for an erasing query the freed index and the entry as
+        it was, for any other a miss. Returns the number of entries erased. An
+        erase ends a follow() and moves the context's mark. Stops the resident
+        kernel, runs on `stream` and returns when done."""
+        assert keys.is_cuda and keys.element_size() == 1 and keys.numel() % 16 == 0
+        return self._table_erase(self.L.vp_table_erase, "vp_table_erase", keys.numel() // 16, keys,
+                                 index, ts, key, value, table, stream)
+
+    def free_device(self, idx, index=None, ts=None, key=None, value=None, table: int = 0,
+                    stream=None) -> int:
+        """vp_table_free: erase_device by index (32-bit CUDA tensor of n); an
+        index that is not allocated, or not below the capacity, is a no-op."""
+        assert idx.is_cuda and idx.element_size() == 4
+        return self._table_erase(self.L.vp_table_free, "vp_table_free", idx.numel(), idx,
+                                 index, ts, key, value, table, stream)
+
+    def _table_erase_host(self, call, src, n, table):
+        got = {}
+
+        def query(src, index, ts, key, value, table):
+            got["n_erased"] = call(src, index, ts, key, value, table)
+
+        out = self._table_query_host(query, src, n, table)
+        out["n_erased"] = got["n_erased"]
+        return out
+
+    def erase(self, keys: np.ndarray, table: int = 0) -> dict:
+        """erase_device of uint8[n, 16] keys in host memory: lookup's dict of
+        numpy arrays plus "n_erased"."""
+        import torch
+        keys = np.ascontiguousarray(keys, np.uint8).reshape(-1, 16)
+        src = torch.from_numpy(keys.reshape(-1).copy()).to("cuda:%d" % self.gpu)
+        return self._table_erase_host(self.erase_device, src, keys.shape[0], table)
+
+    def free(self, indices: np.ndarray, table: int = 0) -> dict:
+        """free_device of uint32[n] indices in host memory; the dict erase
+        returns."""
+        import torch
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        src = torch.from_numpy(idx.view(np.int32).copy()).to("cuda:%d" % self.gpu)
+        return self._table_erase_host(self.free_device, src, idx.shape[0], table)
+
     def live_count(self) -> int:
         v = self.L.vp_live_count(self.h)
         if v < 0:
